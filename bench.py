@@ -5,7 +5,9 @@ A step = forward (train mode, dropout on) + backward + gradient all-reduce (N > 
 over one batch of synthetic [B=256, C=8, T=1024] window pairs per GPU, inputs resident in HBM.
 Workload = BASELINE.json configs[2]/[3] (two 1-D-conv streams + bidirectional cross-stream attention fusion, bf16, batch 256
 per GPU: the configuration the 1/2/4/8-GPU metric is quoted on) unless --workload says otherwise.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: set-up, warm-up, the timed steps.
+--full adds what else the benchmark measures: the per-kernel `roofline` from HIP events inside the timed region (and
+--probe-dump), the `f32` leg and the `cpu_baseline`.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 Ranks: under torchrun (WORLD_SIZE set) this process IS one rank.  Started plainly with --gpus N > 1 it becomes a launcher:
 it spawns N fresh rank processes (before touching the GPU itself -- a process that has initialised HIP is never re-executed),
@@ -281,11 +283,11 @@ def run_mm5(args, dev, world=1, rank=0, use_dist=False):
     tr.train_step(img1, img2, x1, x2, y)                      # lazy workspaces, one-time kernel attributes
     engines = tr._engines(B, T, F_, W_)
     for e in engines:
-        e.probe_all = probes
-    tr.train_step(img1, img2, x1, x2, y)
+        e.probe_all = probes if args.full else None
+    tr.train_step(img1, img2, x1, x2, y)                      # (--full: counts the probed launches of a step)
     launches_per_step = len(probes)
     probes.clear()
-    n_probe_steps = min(4, max(1, args.steps // 20), args.steps)
+    n_probe_steps = min(4, max(1, args.steps // 20), args.steps) if args.full else 0
     stream0 = torch.cuda.current_stream(dev)
     pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe_steps * launches_per_step)]
     for a_, b_ in pool:
@@ -319,7 +321,11 @@ def run_mm5(args, dev, world=1, rank=0, use_dist=False):
         elapsed = float(tmax)
     loss = float(out["loss"])
     assert loss == loss, "loss is NaN"
-    eeg = engines[0]
+    eeg, img = engines
+    if rank == 0 and args.dump_outputs:
+        sets = {"eeg": eeg.fp, "gaze": img.fp, "fusion": tr.fus}
+        write_outputs(args.dump_outputs, snapshot(dict(
+            out, **{f"{k}_params": fp_.flat for k, fp_ in sets.items()}, **{f"{k}_grads": fp_.grad for k, fp_ in sets.items()})))
     if rank == 0:
         res = {"metric": "train samples/sec (gaze+EEG windows)", "value": round(world * B * args.steps / elapsed, 2), "unit": "samples/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
@@ -329,9 +335,10 @@ def run_mm5(args, dev, world=1, rank=0, use_dist=False):
                           "step": "fwd(image CNN + EEG, train, dropout) + fuzzy fusion + losses + bwd"
                                   + (" + 3-set gradient all-reduce" if use_dist else "") + " + global clip + per-group AdamW"
                                   + (" + loss scaling" if args.dtype == "fp16" else ""),
-                          "parallelism": f"dp{world}", "final_loss": round(loss, 5)},
-               "roofline": roofline_from_probes(probes, n_probe_steps, args.dtype)}
-        if not args.no_cpu_baseline and world == 1:
+                          "parallelism": f"dp{world}", "final_loss": round(loss, 5)}}
+        if args.full:
+            res["roofline"] = roofline_from_probes(probes, n_probe_steps, args.dtype)
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline_mm5(tr, C, T, F_, W_, Bc=args.cpu_batch)
         emit(res)
     if use_dist:
@@ -366,6 +373,34 @@ def cpu_baseline_mm5(tr, C, T, F_, W_, Bc=256, seconds_budget=30.0):
     return {"value": round(Bc / dt, 3), "unit": "samples/s", "cores": cores, "cores_available": avail, "kind": "port",
             "sample": f"multimodal oracle step (image CNN + EEG oracle + fuzzy fusion + clip + AdamW), eval-mode dropout, B={Bc}, "
                       f"{n} timed steps after 1 warm-up"}
+
+
+DUMP_CAP = 1 << 21   # elements per dumped vector: a longer one (the flat parameter / gradient buffers) is dumped as a fixed sample
+DUMP_SEED = 20261016
+
+
+def snapshot(tensors):
+    """Host float32 copies of what the last timed step left for its caller; a vector longer than DUMP_CAP is reduced to the same
+    seeded sample of indices in every run (so parameters and gradients of one buffer share it)."""
+    import numpy as np
+    out = {}
+    for name, t_ in tensors.items():
+        a = t_.detach().float().cpu().numpy()
+        if a.size > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_CAP, replace=False))
+            a = a.reshape(-1)[idx]
+        out[name] = a
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 _REAL_STDOUT = None
@@ -413,7 +448,17 @@ def main():
     ap.add_argument("--no-f32-leg", action="store_true", help="skip the secondary f32 measurement (the reference's precision)")
     ap.add_argument("--plan-only", action="store_true",
                     help="rehearsal without a GPU: form the process group, report world/rank and exit (CPU test of the launcher)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel roofline (HIP events around the "
+                         "last timed steps' launches), the f32 leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (losses, logits, parameters, gradients; "
+                         "float32 .npy, parameter and gradient buffers as a fixed sample) to DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.probe_dump and not args.full:
+        ap.error("--probe-dump needs --full (the per-launch timings come from the probed steps of a full run)")
     if args.dtype is None:
         args.dtype = "fp16" if args.workload == "mm5" else "bf16"
 
@@ -537,13 +582,13 @@ def main():
         opt.step(eng)
 
     probes = []
-    step(0, probe=True, eager=True)  # first step eagerly: lazy workspace allocation, one-time kernel attributes, launch count
+    step(0, probe=args.full, eager=True)  # first step eagerly: lazy workspace allocation, one-time kernel attributes, launch count
     launches_per_step = len(probes)
     probes.clear()
     # the timed region's probe events are created (and recorded once, which is what materialises a hipEvent) HERE, outside it:
     # inside, a probed launch costs two hipEventRecord calls and the host stays ahead of the GPU
     # a probed step costs the host ~0.6 ms of hipEventRecord calls (the GPU idles meanwhile), so few steps are probed: 4 of 100, 1 of 20
-    n_probe_steps = 0 if graphed is not None else min(4, max(1, args.steps // 20), args.steps)
+    n_probe_steps = 0 if (graphed is not None or not args.full) else min(4, max(1, args.steps // 20), args.steps)
     stream0 = torch.cuda.current_stream(dev)
     pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             for _ in range(n_probe_steps * launches_per_step)]
@@ -574,7 +619,14 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    if graphed is not None:
+    dump = None
+    if rank == 0 and args.dump_outputs:      # what the last timed step left for its caller, before anything else runs
+        named = {"logits": eng.a["logits"], "loss": eng.a["loss"]}
+        if model.cfg.use_ibs:
+            named.update(ibs_logits=eng.a["ibs_logits"], ibs_loss=eng.a["ibs_loss"])
+        named.update(params=fp.flat, grads=fp.grad, grad_norm=torch.tensor([eng.read_state().grad_norm]))
+        dump = snapshot(named)
+    if graphed is not None and args.full:
         for i in range(4):
             step(args.warmup + args.steps + i, probe=True, eager=True)
         torch.cuda.synchronize()
@@ -588,28 +640,8 @@ def main():
     if rank == 0:
         ms = 1e3 * elapsed / args.steps
         value = world * B * args.steps / elapsed
-        # eg_gemm_nt (every forward product -- strided convs, q/k/v/out, heads -- and every backward-data product) routes a launch
-        # to one of its kernels (eg_gemm_nt_route); eg_ffn_chain is the feed-forward pair.  HIP events bracket EVERY such launch
-        # of the timed region's last steps on the launch stream; launches are grouped by the kernel they ran, and `roofline`
-        # describes the group with the most GPU time = the step's dominant kernel (rocprofv3 --kernel-trace --stats of this command
-        # under profiles/ agrees).  Per launch (averaged over that kernel's launches of a step): algorithmic FLOPs = 2*M*N*K,
-        # algorithmic bytes = each distinct operand/output element once (Engine._gemm_bytes).  With d_model = 256 the products
-        # sit BELOW the ridge (FLOP/B < peak_flops/peak_bw), so the binding roofline is HBM; the MFMA fraction is reported beside it.
-        nsteps_probed = (n_probe_steps if graphed is None else 4)
-        roof = roofline_from_probes(probes, nsteps_probed, args.dtype)
-        # HBM traffic per launch of the dominant kernel comes from the separate rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE
-        # cannot share a pass, profiles/collect_r02.sh); the file names the kernel it was measured on.
-        attach_traffic(roof, args.workload, args.dtype, B)
-        per_step = len(probes) // nsteps_probed
-        if args.probe_dump:
-            rows = []
-            for j in range(per_step):
-                sel = probes[j::per_step]
-                us = 1e3 * sum(a.elapsed_time(b) for a, b, *_ in sel) / len(sel)
-                _, _, f, nb, shape, route_ = sel[0]
-                rows.append({"launch": j, "kernel": ROUTES.get(route_, route_), "M": shape[0], "N": shape[1], "K": shape[2],
-                             "us": round(us, 2), "tflops": round(f / us / 1e6, 1), "gbs": round(nb / us / 1e3, 1)})
-            Path(args.probe_dump).write_text(json.dumps(rows, indent=0))
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         out = {
             "metric": "train samples/sec (gaze+EEG windows)", "value": round(value, 2), "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
@@ -619,12 +651,35 @@ def main():
                        "step": "fwd(train,dropout)+bwd+allreduce+clip+AdamW" + ("" if args.h2d == "none" else f" + per-step H2D ({args.h2d})"),
                        "parallelism": f"dp{world}",
                        "final_loss": round(loss, 5)},
-            "roofline": roof,
         }
-        if world == 1 and args.dtype != "f32" and not args.no_f32_leg and not args.no_cpu_baseline and args.h2d == "none":
-            out["f32"] = f32_leg(ctor, B, C, T, dev)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(kw, C, T, Bc=args.cpu_batch)
+        if args.full:
+            # eg_gemm_nt (every forward product -- strided convs, q/k/v/out, heads -- and every backward-data product) routes a launch
+            # to one of its kernels (eg_gemm_nt_route); eg_ffn_chain is the feed-forward pair.  HIP events bracket EVERY such launch
+            # of the timed region's last steps on the launch stream; launches are grouped by the kernel they ran, and `roofline`
+            # describes the group with the most GPU time = the step's dominant kernel (rocprofv3 --kernel-trace --stats of this command
+            # under profiles/ agrees).  Per launch (averaged over that kernel's launches of a step): algorithmic FLOPs = 2*M*N*K,
+            # algorithmic bytes = each distinct operand/output element once (Engine._gemm_bytes).  With d_model = 256 the products
+            # sit BELOW the ridge (FLOP/B < peak_flops/peak_bw), so the binding roofline is HBM; the MFMA fraction is reported beside it.
+            nsteps_probed = (n_probe_steps if graphed is None else 4)
+            roof = roofline_from_probes(probes, nsteps_probed, args.dtype)
+            # HBM traffic per launch of the dominant kernel comes from the separate rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE
+            # cannot share a pass, profiles/collect_r02.sh); the file names the kernel it was measured on.
+            attach_traffic(roof, args.workload, args.dtype, B)
+            per_step = len(probes) // nsteps_probed
+            if args.probe_dump:
+                rows = []
+                for j in range(per_step):
+                    sel = probes[j::per_step]
+                    us = 1e3 * sum(a.elapsed_time(b) for a, b, *_ in sel) / len(sel)
+                    _, _, f, nb, shape, route_ = sel[0]
+                    rows.append({"launch": j, "kernel": ROUTES.get(route_, route_), "M": shape[0], "N": shape[1], "K": shape[2],
+                                 "us": round(us, 2), "tflops": round(f / us / 1e6, 1), "gbs": round(nb / us / 1e3, 1)})
+                Path(args.probe_dump).write_text(json.dumps(rows, indent=0))
+            out["roofline"] = roof
+            if world == 1 and args.dtype != "f32" and not args.no_f32_leg and not args.no_cpu_baseline and args.h2d == "none":
+                out["f32"] = f32_leg(ctor, B, C, T, dev)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(kw, C, T, Bc=args.cpu_batch)
         emit(out)
     if use_dist:
         dist.destroy_process_group()

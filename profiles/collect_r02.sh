@@ -9,7 +9,7 @@ DT=${3:-bf16}
 KERNEL=${KERNEL:-gemm}
 O=gpurun_out/r02_${TAG}_${WL}_${DT}
 mkdir -p $O
-python bench.py --workload $WL --dtype $DT > $O/bench.json 2> $O/bench.err
+python bench.py --full --workload $WL --dtype $DT > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --workload $WL --dtype $DT --no-cpu-baseline > $O/trace.log 2>&1
 python profiles/tools/kernel_summary.py $O/trace 121 > $O/kernel_summary.txt

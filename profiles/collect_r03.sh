@@ -12,7 +12,7 @@ shift 3 || true
 EXTRA="$@"
 O=gpurun_out/r03_${TAG}_${WL}_${DT}
 mkdir -p $O
-python bench.py --workload $WL --dtype $DT $EXTRA > $O/bench.json 2> $O/bench.err
+python bench.py --full --workload $WL --dtype $DT $EXTRA > $O/bench.json 2> $O/bench.err
 tail -c 700 $O/bench.json
 STEPS=${STEPS:-40}
 WARM=${WARM:-10}
