@@ -1,0 +1,698 @@
+// Multi-head attention core for long sequences (1 <= S <= 2048, d_k = 32) on gfx950: flash-style tiling.
+// Same layouts as attention.hip (qkv [NB*S, 3D], ctx [NB*S, D], lse [NB, H, S] natural-log logsumexp of the scaled scores,
+// kv_shift pairs query window b with key / value window (b + kv_shift) mod NB), so the engine's buffers are shared.
+//
+// 16-bit forward: one workgroup per (window, head, 64-query tile); wave w owns queries 16 w .. 16 w + 15 of the tile.
+//   K / V tiles of 64 keys stream through LDS, double-buffered (the next tile's global loads are issued before the current
+//   tile's MFMAs and written to the other buffer after them: one barrier per tile).
+//   scores^T = K_tile * Q^T (v_mfma_f32_16x16x32_{bf16,f16}: key on rows, query on lanes), online soft-max in registers
+//   (running max and a per-lane partial of the running sum; lanes l, l^16, l^32, l^48 share a query), P rounded to the
+//   16-bit type and fed to O^T = V^T * P^T as the B operand without an LDS round trip (the key permutation of attention.hip).
+// 16-bit backward (deterministic: every output element has exactly one writer, no atomics):
+//   delta = rowsum(dO * O) into caller scratch [NB, H, S];
+//   dK / dV: one workgroup per (key window, head, 64-key tile) walks every query tile of the paired query window
+//            (kv_shift is a bijection between windows, so the key tile has exactly one owner);
+//   dQ:      one workgroup per (query window, head, 64-query tile) walks every key tile.
+// fp32 (the parity path): one thread per query / key with fmaf chains and the operation order of attention.hip's fp32
+// kernels (three passes max / sum / output in the forward), K / V / Q / dO tiles streamed through LDS.
+// Dropout: element e = ((w H + h) S + q) Sp2 + key in 64 bits, Sp2 = (S + 1) & ~1 (common.h: eg_hash_pair64); below 2^32
+// the masks equal those of attention.hip bit for bit.
+#include "common.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+template <typename T> using FR = typename H16<T>::frag;
+
+constexpr int LT = 64;                    // rows per tile: queries of a workgroup, keys of a K / V tile
+constexpr int IMG = LT * 64;              // bytes of one 64-row image of a 32-wide 16-bit head slice
+constexpr float kScale = 0.17677669529663687f;  // 1/sqrt(32)
+
+// ---- fragment helpers (the image layout and operand maps of attention.hip) ----
+template <typename T>
+__device__ __forceinline__ FR<T> ld_frag_global(const T* p, bool valid) {
+  u32x4 v = {0u, 0u, 0u, 0u};
+  if (valid) v = *(const u32x4*)p;
+  return __builtin_bit_cast(FR<T>, v);
+}
+// [rows][32 x 16 bit] = 64-B rows; the two 32-B halves of a row are swapped when (row>>2)&1 (conflict-free transposed reads)
+__device__ __forceinline__ int img_chunk_off(int row, int c4) {
+  return row * 64 + ((((c4 >> 1) ^ ((row >> 2) & 1))) << 5) + ((c4 & 1) << 4);
+}
+template <typename T>
+__device__ __forceinline__ FR<T> ld_frag_lds_row(const char* img, int row, int g) {
+  return *(const FR<T>*)(img + img_chunk_off(row, g));
+}
+// transposed fragment: slot 8g+j <-> row rbase + 16*(j>>2) + 4g + (j&3), column 16 dt + (lane&15)
+template <typename T>
+__device__ __forceinline__ FR<T> ld_frag_lds_tr(const char* img, int rbase, int dt, int lane) {
+  const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
+  s16x4 part[2];
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2) {
+    const int row = rbase + 16 * h2 + 4 * g + qq;
+    const int off = row * 64 + ((dt ^ (g & 1)) << 5) + pp * 8;
+    part[h2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(img + off));
+  }
+  s16x8 t = {part[0][0], part[0][1], part[0][2], part[0][3], part[1][0], part[1][1], part[1][2], part[1][3]};
+  return __builtin_bit_cast(FR<T>, t);
+}
+template <typename T>
+__device__ __forceinline__ FR<T> pack_frag(const f32x4& a, const f32x4& b) {
+  u32x4 v;
+  v[0] = H16<T>::pack2(a[0], a[1]);
+  v[1] = H16<T>::pack2(a[2], a[3]);
+  v[2] = H16<T>::pack2(b[0], b[1]);
+  v[3] = H16<T>::pack2(b[2], b[3]);
+  return __builtin_bit_cast(FR<T>, v);
+}
+// one 16-B chunk of a 64-row tile per thread (256 threads: row tid >> 2, chunk tid & 3); rows >= nrows read as zero
+template <typename T>
+__device__ __forceinline__ u32x4 tile_request(const T* src, long long ld, int row0, int S, int tid) {
+  const int row = row0 + (tid >> 2);
+  u32x4 v = {0u, 0u, 0u, 0u};
+  if (row < S) v = *(const u32x4*)(src + (long long)row * ld + (tid & 3) * 8);
+  return v;
+}
+__device__ __forceinline__ void tile_store(char* img, u32x4 v, int tid) { *(u32x4*)(img + img_chunk_off(tid >> 2, tid & 3)) = v; }
+
+// (window, head, tile) of a workgroup: tiles fastest, so the workgroups of one head run side by side and share its K / V in L2
+struct TileIdx { int w, h, t; };
+__device__ __forceinline__ TileIdx tile_idx(int ntile, int H) {
+  const int t = blockIdx.x % ntile, pid = blockIdx.x / ntile;
+  return {pid / H, pid % H, t};
+}
+
+// ------------------------------------------------------------------------------------------------
+// 16-bit forward
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ ctx, float* __restrict__ lse,
+                                                            int NB, int S, int H, int kv_shift, DropCfg dc, const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) char sm[2][2][IMG];    // [buffer][K, V]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  const int ntile = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int b = ti.w, h = ti.h, bk = (b + kv_shift) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const T* qbase = qkv + (long long)b * S * ld + h * 32;
+  const T* kbase = qkv + (long long)bk * S * ld + D + h * 32;
+  const T* vbase = kbase + D;
+  const int q = ti.t * LT + wave * 16 + l15;
+  u32x4 rk = tile_request<T>(kbase, ld, 0, S, tid), rv = tile_request<T>(vbase, ld, 0, S, tid);
+  const FR<T> qf = ld_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const uint64_t rowe = (uint64_t)(((long long)b * H + h) * S + q) * (uint64_t)((S + 1) & ~1);
+  tile_store(sm[0][0], rk, tid);
+  tile_store(sm[0][1], rv, tid);
+  __syncthreads();
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 o[2] = {zero4, zero4};
+  float m = -INFINITY, l = 0.f;                 // running max (shared by the query's 4 lanes), the lane's partial running sum
+  for (int t = 0; t < ntile; ++t) {
+    const int cur = t & 1, kv0 = t * LT;
+    const bool more = t + 1 < ntile;
+    if (more) {
+      rk = tile_request<T>(kbase, ld, kv0 + LT, S, tid);
+      rv = tile_request<T>(vbase, ld, kv0 + LT, S, tid);
+    }
+    const char* kimg = sm[cur][0];
+    const char* vimg = sm[cur][1];
+    const bool full = kv0 + LT <= S;           // workgroup-uniform: only the last tile masks keys
+    f32x4 s[4];
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      s[kt] = H16<T>::mfma(ld_frag_lds_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = (full || kv0 + kt * 16 + 4 * g + r < S) ? s[kt][r] * kScale : -INFINITY;
+        s[kt][r] = v;
+        tmax = fmaxf(tmax, v);
+      }
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mnew = fmaxf(m, tmax);          // finite: every tile holds at least one valid key
+    const float alpha = __expf(m - mnew);       // 0 at the first tile (m = -inf)
+    m = mnew;
+    float psum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(s[kt][r] - m);
+        s[kt][r] = p;
+        psum += p;
+      }
+    l = l * alpha + psum;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) o[dt] *= alpha;
+    if (dc.thresh) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        float pv[4] = {s[kt][0], s[kt][1], s[kt][2], s[kt][3]};
+        eg_dropout_run64<4>(pv, dc, seed_lo, seed_hi, rowe + (uint64_t)(kv0 + kt * 16 + 4 * g));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] = pv[r];
+      }
+    }
+#pragma unroll
+    for (int kp = 0; kp < 2; ++kp) {
+      const FR<T> pf = pack_frag<T>(s[2 * kp], s[2 * kp + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) o[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(vimg, 32 * kp, dt, lane), pf, o[dt]);
+    }
+    if (more) {
+      tile_store(sm[cur ^ 1][0], rk, tid);
+      tile_store(sm[cur ^ 1][1], rv, tid);
+    }
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (q < S) {
+    if (g == 0) lse[((long long)b * H + h) * S + q] = m + __logf(l);
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      float v[4] = {o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv};
+      store4(ctx + ((long long)b * S + q) * D + h * 32 + 16 * dt + 4 * g, v);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// delta = rowsum(dO * O) per (window, head, query), into [NB, H, S] (16-bit and fp32)
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_delta_kernel(const T* __restrict__ ctx, const T* __restrict__ dctx,
+                                                              float* __restrict__ delta, long long n, int S, int H) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int q = (int)(i % S);
+  const long long wh = i / S;
+  const int h = (int)(wh % H);
+  const long long w = wh / H;
+  const long long off = (w * S + q) * (long long)(H * 32) + h * 32;
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float a[8], o[8];
+    load8(dctx + off + 8 * c, a);
+    load8(ctx + off + 8 * c, o);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s = fmaf(a[e], o[e], s);
+  }
+  delta[i] = s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 16-bit dK / dV: one workgroup per (key window, head, 64-key tile); query rows / key lanes (pass B of attention.hip)
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict__ qkv, const T* __restrict__ dctx,
+                                                             const float* __restrict__ lse, const float* __restrict__ delta,
+                                                             T* __restrict__ dqkv, int NB, int S, int H, int kv_shift, DropCfg dc,
+                                                             const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) char sm[2][2][IMG];    // [buffer][Q, dO]
+  __shared__ __attribute__((aligned(16))) float rows[2][2][LT];  // [buffer][lse, delta]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  const int ntile = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int bk = ti.w, h = ti.h, b = (bk - kv_shift + NB) % NB, D = H * 32;   // the one query window that reads key window bk
+  const long long ld = 3ll * D;
+  const T* qbase = qkv + (long long)b * S * ld + h * 32;
+  const T* kbase = qkv + (long long)bk * S * ld + D + h * 32;
+  const T* vbase = kbase + D;
+  const T* dobase = dctx + (long long)b * S * D + h * 32;
+  const float* lrow = lse + ((long long)b * H + h) * S;
+  const float* drow = delta + ((long long)b * H + h) * S;
+  const int key = ti.t * LT + wave * 16 + l15;
+  // this thread's share of a query tile: one chunk of Q, one of dO, and (threads 0..127) one lse / delta value
+  auto request = [&](int q0, u32x4& rq, u32x4& rd, float& rl) {
+    rq = tile_request<T>(qbase, ld, q0, S, tid);
+    rd = tile_request<T>(dobase, D, q0, S, tid);
+    rl = 0.f;
+    const int qr = q0 + (tid & 63);
+    if (tid < 128 && qr < S) rl = tid < 64 ? lrow[qr] : drow[qr];
+  };
+  auto store = [&](int buf, const u32x4& rq, const u32x4& rd, float rl) {
+    tile_store(sm[buf][0], rq, tid);
+    tile_store(sm[buf][1], rd, tid);
+    if (tid < 128) rows[buf][tid >> 6][tid & 63] = rl;
+  };
+  u32x4 rq, rd;
+  float rl;
+  request(0, rq, rd, rl);
+  const FR<T> kfr = ld_frag_global<T>(kbase + (long long)key * ld + g * 8, key < S);
+  const FR<T> vfr = ld_frag_global<T>(vbase + (long long)key * ld + g * 8, key < S);
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const uint64_t Sp2 = (uint64_t)((S + 1) & ~1);
+  const long long headrow = ((long long)b * H + h) * S;
+  store(0, rq, rd, rl);
+  __syncthreads();
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 dk[2] = {zero4, zero4}, dv[2] = {zero4, zero4};
+  for (int t = 0; t < ntile; ++t) {
+    const int cur = t & 1, q0 = t * LT;
+    const bool more = t + 1 < ntile;
+    if (more) request(q0 + LT, rq, rd, rl);
+    const char* qimg = sm[cur][0];
+    const char* doimg = sm[cur][1];
+    const float* lsel = rows[cur][0];
+    const float* dl = rows[cur][1];
+#pragma unroll
+    for (int qp = 0; qp < 2; ++qp) {
+      f32x4 pd2[2], ds2[2];
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+        const int r16 = 32 * qp + 16 * h2;                 // first query of the 16-row block, within the tile
+        const f32x4 s = H16<T>::mfma(ld_frag_lds_row<T>(qimg, r16 + l15, g), kfr, zero4);
+        const f32x4 dp = H16<T>::mfma(ld_frag_lds_row<T>(doimg, r16 + l15, g), vfr, zero4);
+        const f32x4 l4 = *(const f32x4*)(lsel + r16 + 4 * g);
+        const f32x4 d4 = *(const f32x4*)(dl + r16 + 4 * g);
+        // One hash serves the elements (q, key) and (q, key ^ 1), which sit in neighbouring lanes: a lane hashes two of its
+        // four query rows (even keys rows 0-1, odd keys rows 2-3) and takes the other two from lane ^ 1 (as attention.hip).
+        uint32_t hh[4] = {0u, 0u, 0u, 0u};
+        if (dc.thresh) {
+          const uint32_t odd = (uint32_t)key & 1u;
+          const uint64_t ea = (uint64_t)(headrow + q0 + r16 + 4 * g + 2 * (int)odd) * Sp2 + (uint64_t)key;
+          const uint32_t ha = eg_hash_pair64(seed_lo, seed_hi, dc.site, ea >> 1);
+          const uint32_t hb = eg_hash_pair64(seed_lo, seed_hi, dc.site, (ea + Sp2) >> 1);
+          const uint32_t pa = (uint32_t)__shfl_xor((int)ha, 1, 64), pb = (uint32_t)__shfl_xor((int)hb, 1, 64);
+          hh[0] = odd ? pa : ha; hh[1] = odd ? pb : hb;
+          hh[2] = odd ? ha : pa; hh[3] = odd ? hb : pb;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qq = q0 + r16 + 4 * g + r;
+          const float p = (key < S && qq < S) ? __expf(s[r] * kScale - l4[r]) : 0.f;
+          float mk = 1.0f;
+          if (dc.thresh) {
+            const uint32_t half = ((uint32_t)key & 1u) ? (hh[r] >> 16) : (hh[r] & 0xFFFFu);
+            mk = half >= dc.thresh ? dc.scale : 0.0f;
+          }
+          pd2[h2][r] = p * mk;
+          ds2[h2][r] = p * (dp[r] * mk - d4[r]);
+        }
+      }
+      const FR<T> pdf = pack_frag<T>(pd2[0], pd2[1]);
+      const FR<T> dsf = pack_frag<T>(ds2[0], ds2[1]);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {
+        dv[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(doimg, 32 * qp, dt, lane), pdf, dv[dt]);
+        dk[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(qimg, 32 * qp, dt, lane), dsf, dk[dt]);
+      }
+    }
+    if (more) store(cur ^ 1, rq, rd, rl);
+    __syncthreads();
+  }
+  if (key < S) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      float a[4] = {dk[dt][0] * kScale, dk[dt][1] * kScale, dk[dt][2] * kScale, dk[dt][3] * kScale};
+      float c[4] = {dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]};
+      T* row = dqkv + ((long long)bk * S + key) * ld + h * 32 + 16 * dt + 4 * g;
+      store4(row + D, a);
+      store4(row + 2 * D, c);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 16-bit dQ: one workgroup per (query window, head, 64-query tile); key rows / query lanes (pass A of attention.hip)
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ dctx,
+                                                           const float* __restrict__ lse, const float* __restrict__ delta,
+                                                           T* __restrict__ dqkv, int NB, int S, int H, int kv_shift, DropCfg dc,
+                                                           const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) char sm[2][2][IMG];    // [buffer][K, V]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  const int ntile = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int b = ti.w, h = ti.h, bk = (b + kv_shift) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const T* qbase = qkv + (long long)b * S * ld + h * 32;
+  const T* kbase = qkv + (long long)bk * S * ld + D + h * 32;
+  const T* vbase = kbase + D;
+  const T* dobase = dctx + (long long)b * S * D + h * 32;
+  const int q = ti.t * LT + wave * 16 + l15;
+  u32x4 rk = tile_request<T>(kbase, ld, 0, S, tid), rv = tile_request<T>(vbase, ld, 0, S, tid);
+  const FR<T> qf = ld_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
+  const FR<T> dof = ld_frag_global<T>(dobase + (long long)q * D + g * 8, q < S);
+  const long long hq = ((long long)b * H + h) * S + q;
+  const float lq = q < S ? lse[hq] : 0.f, dq = q < S ? delta[hq] : 0.f;
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const uint64_t rowe = (uint64_t)hq * (uint64_t)((S + 1) & ~1);
+  tile_store(sm[0][0], rk, tid);
+  tile_store(sm[0][1], rv, tid);
+  __syncthreads();
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[2] = {zero4, zero4};
+  for (int t = 0; t < ntile; ++t) {
+    const int cur = t & 1, kv0 = t * LT;
+    const bool more = t + 1 < ntile;
+    if (more) {
+      rk = tile_request<T>(kbase, ld, kv0 + LT, S, tid);
+      rv = tile_request<T>(vbase, ld, kv0 + LT, S, tid);
+    }
+    const char* kimg = sm[cur][0];
+    const char* vimg = sm[cur][1];
+    f32x4 ds[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      const f32x4 sT = H16<T>::mfma(ld_frag_lds_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
+      const f32x4 dpT = H16<T>::mfma(ld_frag_lds_row<T>(vimg, kt * 16 + l15, g), dof, zero4);
+      float dpv[4] = {dpT[0], dpT[1], dpT[2], dpT[3]};
+      eg_dropout_run64<4>(dpv, dc, seed_lo, seed_hi, rowe + (uint64_t)(kv0 + kt * 16 + 4 * g));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = kv0 + kt * 16 + 4 * g + r;
+        const float p = key < S ? __expf(sT[r] * kScale - lq) : 0.f;
+        ds[kt][r] = p * (dpv[r] - dq);
+      }
+    }
+#pragma unroll
+    for (int kp = 0; kp < 2; ++kp) {
+      const FR<T> dsf = pack_frag<T>(ds[2 * kp], ds[2 * kp + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) acc[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(kimg, 32 * kp, dt, lane), dsf, acc[dt]);
+    }
+    if (more) {
+      tile_store(sm[cur ^ 1][0], rk, tid);
+      tile_store(sm[cur ^ 1][1], rv, tid);
+    }
+    __syncthreads();
+  }
+  if (q < S) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      float v[4] = {acc[dt][0] * kScale, acc[dt][1] * kScale, acc[dt][2] * kScale, acc[dt][3] * kScale};
+      store4(dqkv + ((long long)b * S + q) * ld + h * 32 + 16 * dt + 4 * g, v);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// fp32: one thread per query (forward, dQ) or key (dK, dV), 128 threads per workgroup, 64-row tiles of the other side in LDS.
+// The arithmetic of every output element is that of attention.hip's fp32 kernels, in the same order.
+// ------------------------------------------------------------------------------------------------
+constexpr int F32_THREADS = 128;
+
+__device__ __forceinline__ float dot32(const float* a, const float* b) {
+  float s = 0.f;
+#pragma unroll
+  for (int d = 0; d < 32; ++d) s = fmaf(a[d], b[d], s);
+  return s;
+}
+// rows [row0, row0 + 64) of a 32-wide fp32 head slice into dst [64][32]; rows >= S read as zero
+__device__ __forceinline__ void f32_tile_load(float* dst, const float* src, long long ld, int row0, int S) {
+  for (int i = threadIdx.x; i < LT * 8; i += F32_THREADS) {
+    const int r = i >> 3, c = i & 7;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row0 + r < S) v = *(const f32x4*)(src + (long long)(row0 + r) * ld + 4 * c);
+    *(f32x4*)(dst + r * 32 + 4 * c) = v;
+  }
+}
+
+__global__ __launch_bounds__(F32_THREADS) void attn_long_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ ctx,
+                                                                        float* __restrict__ lse, int NB, int S, int H, int kv_shift,
+                                                                        DropCfg dc, const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) float Kl[LT * 32];
+  __shared__ __attribute__((aligned(16))) float Vl[LT * 32];
+  const int ntile = (S + F32_THREADS - 1) / F32_THREADS, nkv = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int b = ti.w, h = ti.h, bk = (b + kv_shift) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const float* kbase = qkv + (long long)bk * S * ld + D + h * 32;
+  const float* vbase = kbase + D;
+  const int q = ti.t * F32_THREADS + threadIdx.x;
+  const bool valid = q < S;
+  float qv[32], o[32];
+#pragma unroll
+  for (int d = 0; d < 32; ++d) { qv[d] = valid ? qkv[((long long)b * S + q) * ld + h * 32 + d] : 0.f; o[d] = 0.f; }
+  // pass 1: max, pass 2: sum, pass 3: P V -- as attn_fwd_f32_kernel
+  float mx = -INFINITY, sum = 0.f, inv = 0.f;
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const uint64_t rowe = (uint64_t)(((long long)b * H + h) * S + q) * (uint64_t)((S + 1) & ~1);
+  for (int pass = 0; pass < 3; ++pass) {
+    for (int t = 0; t < nkv; ++t) {
+      const int k0 = t * LT, nk = min(LT, S - k0);
+      __syncthreads();
+      f32_tile_load(Kl, kbase, ld, k0, S);
+      if (pass == 2) f32_tile_load(Vl, vbase, ld, k0, S);
+      __syncthreads();
+      if (pass == 0) {
+        for (int k = 0; k < nk; ++k) mx = fmaxf(mx, dot32(qv, Kl + k * 32) * kScale);
+      } else if (pass == 1) {
+        for (int k = 0; k < nk; ++k) sum += expf(dot32(qv, Kl + k * 32) * kScale - mx);
+      } else {
+        for (int k = 0; k < nk; ++k) {
+          float p = expf(dot32(qv, Kl + k * 32) * kScale - mx) * inv;
+          if (dc.thresh) p = eg_dropout64(p, dc, seed_lo, seed_hi, rowe + (uint64_t)(k0 + k));
+#pragma unroll
+          for (int d = 0; d < 32; ++d) o[d] = fmaf(p, Vl[k * 32 + d], o[d]);
+        }
+      }
+    }
+    if (pass == 1) inv = 1.0f / sum;
+  }
+  if (!valid) return;
+  lse[((long long)b * H + h) * S + q] = mx + logf(sum);
+#pragma unroll
+  for (int d = 0; d < 32; d += 4) *(f32x4*)(ctx + ((long long)b * S + q) * D + h * 32 + d) = (f32x4){o[d], o[d + 1], o[d + 2], o[d + 3]};
+}
+
+__global__ __launch_bounds__(F32_THREADS) void attn_long_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx,
+                                                                       const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                       float* __restrict__ dqkv, int NB, int S, int H, int kv_shift,
+                                                                       DropCfg dc, const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) float Kl[LT * 32];
+  __shared__ __attribute__((aligned(16))) float Vl[LT * 32];
+  const int ntile = (S + F32_THREADS - 1) / F32_THREADS, nkv = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int b = ti.w, h = ti.h, bk = (b + kv_shift) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const float* kbase = qkv + (long long)bk * S * ld + D + h * 32;
+  const float* vbase = kbase + D;
+  const int t_ = ti.t * F32_THREADS + threadIdx.x;
+  const bool valid = t_ < S;
+  const long long hq = ((long long)b * H + h) * S + t_;
+  float qv[32], dov[32], acc[32];
+#pragma unroll
+  for (int d = 0; d < 32; ++d) {
+    qv[d] = valid ? qkv[((long long)b * S + t_) * ld + h * 32 + d] : 0.f;
+    dov[d] = valid ? dctx[((long long)b * S + t_) * D + h * 32 + d] : 0.f;
+    acc[d] = 0.f;
+  }
+  const float lq = valid ? lse[hq] : 0.f, dq = valid ? delta[hq] : 0.f;
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const uint64_t rowe = (uint64_t)hq * (uint64_t)((S + 1) & ~1);
+  for (int t = 0; t < nkv; ++t) {
+    const int k0 = t * LT, nk = min(LT, S - k0);
+    __syncthreads();
+    f32_tile_load(Kl, kbase, ld, k0, S);
+    f32_tile_load(Vl, vbase, ld, k0, S);
+    __syncthreads();
+    for (int k = 0; k < nk; ++k) {
+      const float p = expf(dot32(qv, Kl + k * 32) * kScale - lq);
+      float dp = dot32(dov, Vl + k * 32);
+      if (dc.thresh) dp = eg_dropout64(dp, dc, seed_lo, seed_hi, rowe + (uint64_t)(k0 + k));
+      const float ds = p * (dp - dq);
+#pragma unroll
+      for (int d = 0; d < 32; ++d) acc[d] = fmaf(ds, Kl[k * 32 + d], acc[d]);
+    }
+  }
+  if (!valid) return;
+#pragma unroll
+  for (int d = 0; d < 32; ++d) dqkv[((long long)b * S + t_) * ld + h * 32 + d] = acc[d] * kScale;
+}
+
+__global__ __launch_bounds__(F32_THREADS) void attn_long_dkdv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx,
+                                                                         const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                         float* __restrict__ dqkv, int NB, int S, int H, int kv_shift,
+                                                                         DropCfg dc, const eg_step_state* st) {
+  __shared__ __attribute__((aligned(16))) float Ql[LT * 32];
+  __shared__ __attribute__((aligned(16))) float Dl[LT * 32];
+  __shared__ float lsel[LT], dl[LT];
+  const int ntile = (S + F32_THREADS - 1) / F32_THREADS, nq = (S + LT - 1) / LT;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int bk = ti.w, h = ti.h, b = (bk - kv_shift + NB) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const float* qbase = qkv + (long long)b * S * ld + h * 32;
+  const float* dobase = dctx + (long long)b * S * D + h * 32;
+  const float* lrow = lse + ((long long)b * H + h) * S;
+  const float* drow = delta + ((long long)b * H + h) * S;
+  const int t_ = ti.t * F32_THREADS + threadIdx.x;       // this thread's key
+  const bool valid = t_ < S;
+  float kv[32], vv[32], ak[32], av[32];
+#pragma unroll
+  for (int d = 0; d < 32; ++d) {
+    kv[d] = valid ? qkv[((long long)bk * S + t_) * ld + D + h * 32 + d] : 0.f;
+    vv[d] = valid ? qkv[((long long)bk * S + t_) * ld + 2 * D + h * 32 + d] : 0.f;
+    ak[d] = 0.f;
+    av[d] = 0.f;
+  }
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
+  const long long headrow = ((long long)b * H + h) * S;
+  const uint64_t Sp2 = (uint64_t)((S + 1) & ~1);
+  for (int t = 0; t < nq; ++t) {
+    const int q0 = t * LT, nqr = min(LT, S - q0);
+    __syncthreads();
+    f32_tile_load(Ql, qbase, ld, q0, S);
+    f32_tile_load(Dl, dobase, D, q0, S);
+    if (threadIdx.x < LT) {
+      const int qr = q0 + threadIdx.x;
+      lsel[threadIdx.x] = qr < S ? lrow[qr] : 0.f;
+      dl[threadIdx.x] = qr < S ? drow[qr] : 0.f;
+    }
+    __syncthreads();
+    for (int i = 0; i < nqr; ++i) {
+      const float p = expf(dot32(Ql + i * 32, kv) * kScale - lsel[i]);
+      const float dpr = dot32(Dl + i * 32, vv);
+      float mk = 1.0f;
+      if (dc.thresh) mk = eg_dropout64(1.0f, dc, seed_lo, seed_hi, (uint64_t)(headrow + q0 + i) * Sp2 + (uint64_t)t_);
+      const float pd = p * mk, ds = p * (dpr * mk - dl[i]);
+#pragma unroll
+      for (int d = 0; d < 32; ++d) {
+        av[d] = fmaf(pd, Dl[i * 32 + d], av[d]);
+        ak[d] = fmaf(ds, Ql[i * 32 + d], ak[d]);
+      }
+    }
+  }
+  if (!valid) return;
+#pragma unroll
+  for (int d = 0; d < 32; ++d) {
+    dqkv[((long long)bk * S + t_) * ld + D + h * 32 + d] = ak[d] * kScale;
+    dqkv[((long long)bk * S + t_) * ld + 2 * D + h * 32 + d] = av[d];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Attention probabilities for the analysis hooks: probs[b, h, q, k] = exp(q.k / sqrt(32) - lse[b, h, q]) in fp32, the arithmetic
+// of attn_probs_kernel.  One workgroup per (window, head, 16 query rows); a thread per key, no LDS sized by S; 64-bit offsets.
+// ------------------------------------------------------------------------------------------------
+constexpr int PROBS_ROWS = 16;
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_probs_kernel(const T* __restrict__ qkv, const float* __restrict__ lse,
+                                                              float* __restrict__ probs, int NB, int S, int H, int kv_shift) {
+  __shared__ float Ql[PROBS_ROWS][32];
+  __shared__ float lq[PROBS_ROWS];
+  const int ntile = (S + PROBS_ROWS - 1) / PROBS_ROWS;
+  const TileIdx ti = tile_idx(ntile, H);
+  const int b = ti.w, h = ti.h, bk = (b + kv_shift) % NB, D = H * 32;
+  const long long ld = 3ll * D;
+  const int q0 = ti.t * PROBS_ROWS, nq = min(PROBS_ROWS, S - q0);
+  for (int i = threadIdx.x; i < PROBS_ROWS * 32; i += 256) {
+    const int r = i >> 5, d = i & 31;
+    Ql[r][d] = r < nq ? Elem<T>::ld(qkv + ((long long)b * S + q0 + r) * ld + h * 32 + d) : 0.f;
+  }
+  if (threadIdx.x < PROBS_ROWS) lq[threadIdx.x] = (int)threadIdx.x < nq ? lse[((long long)b * H + h) * S + q0 + threadIdx.x] : 0.f;
+  __syncthreads();
+  float* out = probs + (((long long)b * H + h) * S + q0) * (long long)S;
+  for (int k = threadIdx.x; k < S; k += 256) {
+    float kv[32];
+#pragma unroll
+    for (int d = 0; d < 32; ++d) kv[d] = Elem<T>::ld(qkv + ((long long)bk * S + k) * ld + D + h * 32 + d);
+    for (int r = 0; r < nq; ++r) {
+      float acc = 0.f;
+#pragma unroll
+      for (int d = 0; d < 32; ++d) acc = fmaf(Ql[r][d], kv[d], acc);
+      out[(long long)r * S + k] = expf(acc * kScale - lq[r]);
+    }
+  }
+}
+
+}  // namespace
+
+static int attn_long_check(const char* who, int NB, int S, int H, int kv_shift, int dtype, float p, const void* st) {
+  EG_CHECK(NB > 0 && S > 0 && H > 0, "%s: bad shape NB=%d S=%d H=%d", who, NB, S, H);
+  EG_CHECK(S <= EG_ATTN_LONG_MAX_S, "%s: S=%d exceeds the long-attention limit of %d", who, S, EG_ATTN_LONG_MAX_S);
+  EG_CHECK(kv_shift >= 0 && kv_shift < NB, "%s: kv_shift=%d out of range", who, kv_shift);
+  EG_CHECK(dtype == EG_BF16 || dtype == EG_F32 || dtype == EG_F16, "%s: bad dtype %d", who, dtype);
+  EG_CHECK(p >= 0.f && p < 1.f && (p == 0.f || st), "%s: dropout p=%f needs a step state", who, (double)p);
+  // one workgroup per (window, head, 16-row tile) at most: the grid's x dimension
+  EG_CHECK((long long)NB * H * ((S + PROBS_ROWS - 1) / PROBS_ROWS) < (1ll << 31), "%s: NB*H=%lld heads exceed the grid", who,
+           (long long)NB * H);
+  return 0;
+}
+
+static inline int long_blocks(int NB, int H, int S, int rows) { return NB * H * ((S + rows - 1) / rows); }
+
+extern "C" int eg_attention_long_fwd(const void* qkv, void* ctx, float* lse, int NB, int S, int H, int kv_shift, int dtype,
+                                     float drop_p, uint32_t drop_site, const eg_step_state* state, void* stream) {
+  EG_CHECK(qkv && ctx && lse, "eg_attention_long_fwd: null pointer");
+  if (attn_long_check("eg_attention_long_fwd", NB, S, H, kv_shift, dtype, drop_p, state)) return 1;
+  const DropCfg dc = make_drop(drop_p, drop_site);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == EG_F32)
+    hipLaunchKernelGGL(attn_long_fwd_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
+                       (const float*)qkv, (float*)ctx, lse, NB, S, H, kv_shift, dc, state);
+  else if (dtype == EG_F16)
+    hipLaunchKernelGGL(attn_long_fwd_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
+                       (f16_t*)ctx, lse, NB, S, H, kv_shift, dc, state);
+  else
+    hipLaunchKernelGGL(attn_long_fwd_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
+                       (bf16_t*)ctx, lse, NB, S, H, kv_shift, dc, state);
+  EG_LAUNCH_CHECK("attention_long_fwd");
+  return 0;
+}
+
+extern "C" int eg_attention_long_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int NB,
+                                     int S, int H, int kv_shift, int dtype, float drop_p, uint32_t drop_site,
+                                     const eg_step_state* state, float* scratch, int64_t scratch_elems, void* stream) {
+  EG_CHECK(qkv && ctx && dctx && lse && dqkv && scratch, "eg_attention_long_bwd: null pointer");
+  if (attn_long_check("eg_attention_long_bwd", NB, S, H, kv_shift, dtype, drop_p, state)) return 1;
+  const long long n = (long long)NB * H * S;
+  EG_CHECK(scratch_elems >= n, "eg_attention_long_bwd: scratch holds %lld floats, NB*H*S = %lld are needed",
+           (long long)scratch_elems, n);
+  const DropCfg dc = make_drop(drop_p, drop_site);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 dgrid((unsigned)((n + 255) / 256));
+  if (dtype == EG_F32) {
+    hipLaunchKernelGGL(attn_long_delta_kernel<float>, dgrid, dim3(256), 0, s, (const float*)ctx, (const float*)dctx, scratch, n, S, H);
+    hipLaunchKernelGGL(attn_long_dkdv_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
+                       (const float*)qkv, (const float*)dctx, lse, (const float*)scratch, (float*)dqkv, NB, S, H, kv_shift, dc, state);
+    hipLaunchKernelGGL(attn_long_dq_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
+                       (const float*)qkv, (const float*)dctx, lse, (const float*)scratch, (float*)dqkv, NB, S, H, kv_shift, dc, state);
+  } else if (dtype == EG_F16) {
+    hipLaunchKernelGGL(attn_long_delta_kernel<f16_t>, dgrid, dim3(256), 0, s, (const f16_t*)ctx, (const f16_t*)dctx, scratch, n, S, H);
+    hipLaunchKernelGGL(attn_long_dkdv_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
+                       (const f16_t*)dctx, lse, (const float*)scratch, (f16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+    hipLaunchKernelGGL(attn_long_dq_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
+                       (const f16_t*)dctx, lse, (const float*)scratch, (f16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+  } else {
+    hipLaunchKernelGGL(attn_long_delta_kernel<bf16_t>, dgrid, dim3(256), 0, s, (const bf16_t*)ctx, (const bf16_t*)dctx, scratch, n, S, H);
+    hipLaunchKernelGGL(attn_long_dkdv_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
+                       (const bf16_t*)dctx, lse, (const float*)scratch, (bf16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+    hipLaunchKernelGGL(attn_long_dq_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
+                       (const bf16_t*)dctx, lse, (const float*)scratch, (bf16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+  }
+  EG_LAUNCH_CHECK("attention_long_bwd");
+  return 0;
+}
+
+extern "C" int eg_attention_long_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int kv_shift,
+                                       int dtype, void* stream) {
+  EG_CHECK(qkv && lse && probs, "eg_attention_long_probs: null pointer");
+  if (attn_long_check("eg_attention_long_probs", NB, S, H, kv_shift, dtype, 0.f, nullptr)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(long_blocks(NB, H, S, PROBS_ROWS));
+  if (dtype == EG_F32)
+    hipLaunchKernelGGL(attn_long_probs_kernel<float>, grid, dim3(256), 0, s, (const float*)qkv, lse, probs, NB, S, H, kv_shift);
+  else if (dtype == EG_F16)
+    hipLaunchKernelGGL(attn_long_probs_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)qkv, lse, probs, NB, S, H, kv_shift);
+  else
+    hipLaunchKernelGGL(attn_long_probs_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)qkv, lse, probs, NB, S, H, kv_shift);
+  EG_LAUNCH_CHECK("attention_long_probs");
+  return 0;
+}

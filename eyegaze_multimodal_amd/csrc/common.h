@@ -220,6 +220,27 @@ __device__ __forceinline__ void eg_dropout_run(float (&v)[N], const DropCfg& d, 
     v[j + 1] = (h >> 16) >= d.thresh ? v[j + 1] * d.scale : 0.0f;
   }
 }
+// 64-bit element indices (attention_long.hip: NB*H*S*Sp2 passes 2^32 at long windows).  The pair index's high word moves
+// seed_hi, so for every element index below 2^32 the hash -- and the mask -- is that of eg_dropout / eg_dropout_run.
+__device__ __forceinline__ uint32_t eg_hash_pair64(uint32_t seed_lo, uint32_t seed_hi, uint32_t site, uint64_t pair) {
+  return eg_hash(seed_lo, seed_hi + (uint32_t)(pair >> 32) * 0x9E3779B9u, site, (uint32_t)pair);
+}
+__device__ __forceinline__ float eg_dropout64(float v, const DropCfg& d, uint32_t seed_lo, uint32_t seed_hi, uint64_t e) {
+  if (d.thresh == 0) return v;
+  const uint32_t h = eg_hash_pair64(seed_lo, seed_hi, d.site, e >> 1);
+  const uint32_t half = (e & 1u) ? (h >> 16) : (h & 0xFFFFu);
+  return half >= d.thresh ? v * d.scale : 0.0f;
+}
+template <int N>
+__device__ __forceinline__ void eg_dropout_run64(float (&v)[N], const DropCfg& d, uint32_t seed_lo, uint32_t seed_hi, uint64_t e0) {
+  if (d.thresh == 0) return;
+#pragma unroll
+  for (int j = 0; j < N; j += 2) {
+    const uint32_t h = eg_hash_pair64(seed_lo, seed_hi, d.site, (e0 + j) >> 1);
+    v[j] = (h & 0xFFFFu) >= d.thresh ? v[j] * d.scale : 0.0f;
+    v[j + 1] = (h >> 16) >= d.thresh ? v[j + 1] * d.scale : 0.0f;
+  }
+}
 static inline DropCfg make_drop(float p, uint32_t site) {
   DropCfg d;
   d.thresh = p > 0.f ? (uint32_t)(p * 65536.0f + 0.5f) : 0u;

@@ -50,6 +50,30 @@ def _align(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
 
+ATTN_SHORT_MAX_S = 160      # eg_attention_fwd / _bwd / _probs: a whole window's scores in registers (csrc/attention.hip)
+ATTN_LONG_MAX_S = 2048      # eg_attention_long_*: flash-style tiles (csrc/attention_long.hip, EG_ATTN_LONG_MAX_S)
+
+
+def sequence_length(cfg, T: int) -> int:
+    """Token count S = 1 (CLS) + IBS tokens + spectrogram tokens + T2 of a model config at window length T, after the checks
+    that need no device: S within the positional table and the attention core's limit, and (with IBS) T a power of two in
+    [64, 2048], the synchrony kernels' range.  Raises EgError naming the limit that fails."""
+    k, s = cfg.conv_kernel_size, cfg.conv_stride
+    pad = k // 2
+    T1 = (T + 2 * pad - k) // s + 1
+    T2 = (T1 + 2 * pad - k) // s + 1
+    if T2 < 1:
+        raise L.EgError(f"window length {T} is too short for the two stride-{s} convolutions")
+    S = 1 + cfg.num_ibs_tokens + (cfg.in_channels if cfg.use_spectrogram else 0) + T2
+    if S > cfg.max_len:
+        raise L.EgError(f"sequence length {S} exceeds max_len {cfg.max_len} of the positional table")
+    if S > ATTN_LONG_MAX_S:
+        raise L.EgError(f"sequence length {S} exceeds the attention core's limit of {ATTN_LONG_MAX_S}")
+    if cfg.use_ibs and not (64 <= T <= 2048 and T & (T - 1) == 0):
+        raise L.EgError(f"window length {T}: the IBS synchrony kernels need a power of two in [64, 2048]")
+    return S
+
+
 class FlatParams:
     """All parameters of a module as views of one flat fp32 buffer (+ a flat gradient buffer).
     Segment offsets are multiples of 4 floats so every kernel can use 16-B accesses."""
@@ -144,11 +168,9 @@ class Engine:
         self.n_ibs = cfg.num_ibs_tokens
         self.n_spec = self.C if cfg.use_spectrogram else 0
         self.off = 1 + self.n_ibs + self.n_spec
-        self.S = self.off + self.T2
-        if self.S > cfg.max_len:
-            raise L.EgError(f"sequence length {self.S} exceeds max_len {cfg.max_len} of the positional table")
-        if self.S > 160:
-            raise L.EgError(f"sequence length {self.S} exceeds the attention core's limit of 160")
+        self.S = sequence_length(cfg, T)
+        # S > 160: the long-sequence attention core (eg_attention_long_*) at all four call sites; S <= 160 keeps the short one
+        self.attn_long = self.S > ATTN_SHORT_MAX_S
         self.M = self.NB * self.S
         self._want_attn_block = os.environ.get("EYEGAZE_ATTN_BLOCK", "1") != "0"
         self.fp: FlatParams = model._flat
@@ -309,6 +331,8 @@ class Engine:
         g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
         g["lnpart"] = self._t(self.LN_PARTIAL_BLOCKS * 2 * max(d, 8), dtype=torch.float32)
         g["cspart"] = self._t(512 * max(3 * d, F), dtype=torch.float32)
+        if self.attn_long:          # delta = rowsum(dctx * ctx) of eg_attention_long_bwd, [NB, H, S]
+            g["attn_delta"] = self._t(NB * self.cfg.num_heads * self.S, dtype=torch.float32)
         self.g = g
 
     # ------------------------------------------------------------------------------------------
@@ -460,7 +484,8 @@ class Engine:
             return
         NB, B, S, H = self.NB, self.B, self.S, self.cfg.num_heads
         probs = torch.empty(NB, H, S, S, device=self.device, dtype=torch.float32)
-        call("eg_attention_probs", ptr(qkv), ptr(lse), ptr(probs), NB, S, H, kv_shift, self.dtype, self.stream)
+        call("eg_attention_long_probs" if self.attn_long else "eg_attention_probs", ptr(qkv), ptr(lse), ptr(probs), NB, S, H,
+             kv_shift, self.dtype, self.stream)
         was = drop_module.training
         drop_module.training = False      # the module call is only the hook carrier: identity, no torch RNG use
         try:
@@ -817,6 +842,7 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], train: bool):
         cfg, d, F, H = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_heads
+        attn_fwd = "eg_attention_long_fwd" if self.attn_long else "eg_attention_fwd"
         B, NB, M, S, a, w, fp, es = self.B, self.NB, self.M, self.S, self.a, self.w, self.fp, self.es
         self.stream = self._cur_stream()
         st = self.stream
@@ -851,7 +877,7 @@ class Engine:
                 self._probs_hook(self.model.encoder.layers[l].mha.dropout, a[f"qkv{l}"], a[f"lse{l}"], 0)
             else:
                 self.qkv_proj(x, l)
-                call("eg_attention_fwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(a[f"lse{l}"]), NB, S, H, 0, self.dtype, p,
+                call(attn_fwd, ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(a[f"lse{l}"]), NB, S, H, 0, self.dtype, p,
                      sites["attn"], self.st_ptr, st)
                 self._probs_hook(self.model.encoder.layers[l].mha.dropout, a[f"qkv{l}"], a[f"lse{l}"], 0)
                 self.gemm(ptr(a[f"ctx{l}"]), ptr(w[f"o{l}"]), ptr(a[f"r1_{l}"]), M, d, d, bias=fp.p_ptr(pre + "mha.out_proj.bias"),
@@ -878,7 +904,7 @@ class Engine:
             # D:966-974: both directions in one launch each (kv_shift = B pairs window b with b+B)
             xs = _layer_sites(Lr)
             self.qkv_proj(z, "x")
-            call("eg_attention_fwd", ptr(a["qkvx"]), ptr(a["ctxx"]), ptr(a["lsex"]), NB, S, H, B, self.dtype, p, xs["attn"],
+            call(attn_fwd, ptr(a["qkvx"]), ptr(a["ctxx"]), ptr(a["lsex"]), NB, S, H, B, self.dtype, p, xs["attn"],
                  self.st_ptr, st)
             self._probs_hook(self.model.cross_attn.cross_attn.dropout, a["qkvx"], a["lsex"], B)
             self.gemm(ptr(a["ctxx"]), ptr(w["ox"]), ptr(a["rx"]), M, d, d, bias=fp.p_ptr("cross_attn.cross_attn.out_proj.bias"),
@@ -970,8 +996,12 @@ class Engine:
                 self.wgrad(ptr(drm), ptr(a[f"ctx{l}"]), 0, M, d, d, linear=[pre + "out_proj"])
             if not dctx_done:       # (eg_ln_bwd_proj has written dctx together with dr / drm)
                 self.gemm(ptr(drm), ptr(w[f"oT{l}"]), ptr(g["dctx"]), M, d, d)
-            call("eg_attention_bwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(g["dctx"]), ptr(a[f"lse{l}"]), ptr(dqkv),
-                 NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, st)
+            if self.attn_long:
+                call("eg_attention_long_bwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(g["dctx"]), ptr(a[f"lse{l}"]), ptr(dqkv),
+                     NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, ptr(g["attn_delta"]), g["attn_delta"].numel(), st)
+            else:
+                call("eg_attention_bwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(g["dctx"]), ptr(a[f"lse{l}"]), ptr(dqkv),
+                     NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, st)
             if not defer:
                 self.wgrad(ptr(dqkv), ptr(x_in), 0, M, 3 * d, d, linear=names)
             self.gemm(ptr(dqkv), ptr(w[f"qkvT{l}"]), ptr(dx_out), M, d, 3 * d, residual=ptr(dr))

@@ -336,6 +336,23 @@ int eg_attention_probs(const void* qkv, const float* lse, float* probs, int NB, 
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Long-sequence attention core (1 <= S <= EG_ATTN_LONG_MAX_S): the contract of eg_attention_fwd / _bwd / _probs (same
+ * layouts, same lse, same kv_shift pairing) with flash-style tiling; eg_attention_fwd and friends keep S <= 160.
+ *   bwd: `scratch` holds at least NB*H*S floats (delta = rowsum(dctx * ctx) per window, head and query); deterministic,
+ *        no atomics: two runs give bit-identical dqkv.
+ *   dropout: element ((w*H + h)*S + q)*Sp2 + key (Sp2 = (S+1) & ~1) indexed in 64 bits; for indices below 2^32 the
+ *        masks are those of eg_attention_fwd / _bwd.
+ * ------------------------------------------------------------------------------------------- */
+#define EG_ATTN_LONG_MAX_S 2048
+int eg_attention_long_fwd(const void* qkv, void* ctx, float* lse, int NB, int S, int H, int kv_shift, int dtype,
+                          float drop_p, uint32_t drop_site, const eg_step_state* state, void* stream);
+int eg_attention_long_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int NB, int S,
+                          int H, int kv_shift, int dtype, float drop_p, uint32_t drop_site, const eg_step_state* state,
+                          float* scratch, int64_t scratch_elems, void* stream);
+int eg_attention_long_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int kv_shift, int dtype,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sequence assembly and heads (all [B, d]-sized, latency-bound single launches)
  *   eg_rows_bcast_f32  seq[b, off+r, :] = src[b % src_nb, r, :] + pos[off+r, :]   (cls_token expand + pos, D:1157,1178)
  *   eg_rows_copy       seq[b_dst0+b, off+r, :] = seq[b_src0+b, off+r, :]          (shared IBS tokens, D:1163-1165)
