@@ -2,7 +2,8 @@
 //   * inter-stream synchrony ("IBS") connectivity: per band an FFT-mask band-pass + FFT Hilbert transform, then seven
 //     channel-by-channel reductions over time  (dual_eeg_transformer.py:473-819; scalar variant :178-470)
 //   * STFT log-magnitude image of every channel  (dual_eeg_transformer.py:98-121)
-// FFTs are radix-2 Stockham autosort transforms held entirely in LDS (one workgroup per signal); the pair
+// FFTs are radix-4 Stockham autosort transforms held entirely in LDS (one workgroup per signal), mixed-radix (4, 2, 3, 5, 7,
+// any prime) when the window length is not a power of two; the pair
 // reductions keep both players' band signals and phases of an 8x8 channel tile in LDS (128 KiB).
 #include "common.h"
 
@@ -65,6 +66,139 @@ __device__ cf* fft_stockham(cf* x, cf* y, const cf* tw, int N, bool inverse) {
   return x;
 }
 
+// Mixed-radix plan of a transform length N <= 2048 that is not a power of two: radix-4 stages, at most one radix-2 stage, then the
+// odd prime factors in ascending order (3, 5, 7 have unrolled butterflies, any other prime p a direct p-point DFT per output).
+// The power-of-two stages come first, so their stride s is a power of two; the odd stages divide by s.  2048 = 2^11 bounds the
+// stage count by 11.
+constexpr int FFT_MAX_STAGES = 12;
+struct FftPlan {
+  int nst;
+  int rad[FFT_MAX_STAGES];
+};
+
+// One Stockham stage of radix P in {3, 5, 7}: per j < N/P (q = j % s, k = j / s, m = n / P, n s = N) read a_r = x[q + s (k + r m)],
+// write y[q + s (P k + r)] = w^(r k s) sum_r' a_r' exp(-+2 pi i r r' / P), with the pairs (r', P - r') folded into a sum and a
+// difference, so a butterfly costs 2 ((P-1)/2)^2 complex-by-real multiply-adds.  tw: exp(-2 pi i j / N), j < N.
+// r k s < P m s = N, so the twiddle index needs no reduction.
+template <int P>
+__device__ void fft_stage_odd(const cf* __restrict__ x, cf* __restrict__ y, const cf* tw, int N, int s, bool inverse) {
+  constexpr int H = (P - 1) / 2;
+  const int m = N / (P * s);
+  float cr[H], sr[H];                                            // cos(2 pi r / P), -+sin(2 pi r / P): the P-th roots of unity
+#pragma unroll
+  for (int r = 0; r < H; ++r) {
+    const cf w = tw[(r + 1) * (N / P)];
+    cr[r] = w.x;
+    sr[r] = inverse ? -w.y : w.y;
+  }
+  for (int j = threadIdx.x; j < N / P; j += blockDim.x) {
+    const int k = j / s, q = j - k * s;
+    cf a[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) a[r] = x[q + s * (k + r * m)];
+    cf sp[H], sm[H];
+    cf y0 = a[0];
+#pragma unroll
+    for (int r = 0; r < H; ++r) {
+      sp[r] = make_float2(a[r + 1].x + a[P - 1 - r].x, a[r + 1].y + a[P - 1 - r].y);
+      sm[r] = make_float2(a[r + 1].x - a[P - 1 - r].x, a[r + 1].y - a[P - 1 - r].y);
+      y0.x += sp[r].x; y0.y += sp[r].y;
+    }
+    cf* out = y + q + s * P * k;
+    out[0] = y0;
+#pragma unroll
+    for (int r = 1; r <= H; ++r) {
+      // y_r = a0 + sum_r' cos(r r') sp_r' + i sum_r' sin~(r r') sm_r';  y_(P-r) the same with the second sum negated
+      cf re = a[0], im = make_float2(0.f, 0.f);
+#pragma unroll
+      for (int u = 1; u <= H; ++u) {
+        const int e = (r * u) % P;                               // exponent of the root, folded to [1, H] with the sine's sign
+        const float c = e <= H ? cr[e - 1] : cr[P - e - 1];
+        const float sn = e <= H ? sr[e - 1] : -sr[P - e - 1];
+        re.x = fmaf(c, sp[u - 1].x, re.x); re.y = fmaf(c, sp[u - 1].y, re.y);
+        im.x = fmaf(sn, sm[u - 1].x, im.x); im.y = fmaf(sn, sm[u - 1].y, im.y);
+      }
+      const cf ya = make_float2(re.x - im.y, re.y + im.x);       // re + i im
+      const cf yb = make_float2(re.x + im.y, re.y - im.x);       // re - i im
+      cf wa = tw[r * k * s], wb = tw[(P - r) * k * s];
+      if (inverse) { wa.y = -wa.y; wb.y = -wb.y; }
+      out[r * s] = cmul(ya, wa);
+      out[(P - r) * s] = cmul(yb, wb);
+    }
+  }
+}
+
+// in-LDS mixed-radix Stockham autosort FFT of length N (any N <= 2048 with its plan), same contract as fft_stockham except that
+// tw holds all N entries exp(-2 pi i j / N), j < N.  Every twiddle index is an exact integer below N, reduced before the table
+// was built with sincospif, so the twiddles do not lose accuracy as N grows.
+__device__ cf* fft_mixed(cf* x, cf* y, const cf* tw, int N, const FftPlan& plan, bool inverse) {
+  const float isg = inverse ? 1.f : -1.f;
+  int s = 1;
+  for (int st = 0; st < plan.nst; ++st) {
+    const int P = plan.rad[st];
+    const int m = N / (P * s);
+    if (P == 4) {                                                // s is a power of two here (the radix-4 stages run first)
+      const int ls = __builtin_ctz(s);
+      for (int j = threadIdx.x; j < (N >> 2); j += blockDim.x) {
+        const int k = j >> ls, q = j & (s - 1);
+        cf w1 = tw[k * s], w2 = tw[2 * k * s], w3 = tw[3 * k * s];
+        if (inverse) { w1.y = -w1.y; w2.y = -w2.y; w3.y = -w3.y; }
+        const cf* in = x + q + s * k;
+        const cf a0 = in[0], a1 = in[s * m], a2 = in[2 * s * m], a3 = in[3 * s * m];
+        const cf t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
+        const cf t2 = make_float2(a1.x + a3.x, a1.y + a3.y);
+        const cf d3 = make_float2(a1.x - a3.x, a1.y - a3.y);
+        const cf t3 = make_float2(-isg * d3.y, isg * d3.x);
+        cf* out = y + q + s * 4 * k;
+        out[0] = make_float2(t0.x + t2.x, t0.y + t2.y);
+        out[s] = cmul(make_float2(t1.x + t3.x, t1.y + t3.y), w1);
+        out[2 * s] = cmul(make_float2(t0.x - t2.x, t0.y - t2.y), w2);
+        out[3 * s] = cmul(make_float2(t1.x - t3.x, t1.y - t3.y), w3);
+      }
+    } else if (P == 2) {                                         // s is a power of two
+      const int ls = __builtin_ctz(s);
+      for (int j = threadIdx.x; j < (N >> 1); j += blockDim.x) {
+        const int k = j >> ls, q = j & (s - 1);
+        cf w = tw[k * s];
+        if (inverse) w.y = -w.y;
+        const cf a = x[q + s * k], b = x[q + s * (k + m)];
+        y[q + s * 2 * k] = make_float2(a.x + b.x, a.y + b.y);
+        y[q + s * (2 * k + 1)] = cmul(make_float2(a.x - b.x, a.y - b.y), w);
+      }
+    } else if (P == 3) {
+      fft_stage_odd<3>(x, y, tw, N, s, inverse);
+    } else if (P == 5) {
+      fft_stage_odd<5>(x, y, tw, N, s, inverse);
+    } else if (P == 7) {
+      fft_stage_odd<7>(x, y, tw, N, s, inverse);
+    } else {                                                     // any other prime: a direct P-point DFT per output, O(N P)
+      const int NP = N / P;
+      for (int o = threadIdx.x; o < N; o += blockDim.x) {        // o = q + s (P k + r)
+        const int q = o % s, kr = o / s, k = kr / P, r = kr - k * P;
+        const cf* in = x + q + s * k;
+        cf acc = make_float2(0.f, 0.f);
+        int e = 0;                                               // (r r') mod P, times N / P: an index below N
+        for (int rr = 0; rr < P; ++rr) {
+          cf w = tw[e];
+          if (inverse) w.y = -w.y;
+          const cf a = in[s * m * rr];
+          acc.x = fmaf(a.x, w.x, fmaf(-a.y, w.y, acc.x));
+          acc.y = fmaf(a.x, w.y, fmaf(a.y, w.x, acc.y));
+          e += r * NP;
+          if (e >= N) e -= N;
+        }
+        cf w = tw[r * k * s];
+        if (inverse) w.y = -w.y;
+        y[o] = cmul(acc, w);
+      }
+    }
+    __syncthreads();
+    cf* t = x; x = y; y = t;
+    s *= P;
+  }
+  return x;
+}
+
 // three block sums behind one pair of barriers; per value the order of additions is block_sum's
 __device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float* red) {
   a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
@@ -89,25 +223,29 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 // one block per signal (window, channel):  x [T] -> for every band: band-limited signal xb, instantaneous phase,
 // (mean, 1/(std_unbiased+1e-8)) of xb and of xb^2;  plus the complex spectrum bins [0, nbin) of the raw signal.
+// POW2: T a power of two, radix-4 transforms with a T/2-entry twiddle table (LDS 3.5 T complex);  otherwise any T, mixed-radix
+// transforms by `plan` with a T-entry table (LDS 4 T complex: 64 000 B at T = 2000, 65 504 B at T = 2047; with the 96 B of
+// red[] a workgroup holds up to 65 600 B, past 64 KiB at T = 2046 and 2047, within gfx950's 160 KiB per workgroup).
+template <bool POW2>
 __global__ __launch_bounds__(256) void ibs_analytic_kernel(const float* __restrict__ x, float* __restrict__ xb,
                                                            float* __restrict__ phase, float* __restrict__ stats,
                                                            cf* __restrict__ spec, int nsig, int T, float fs, int nbin,
-                                                           BandTable bt) {
+                                                           BandTable bt, FftPlan plan) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* bufX = (cf*)smem;        // [T] spectrum (kept)
   cf* bufA = bufX + T;         // [T] work
   cf* bufB = bufA + T;         // [T] work
-  cf* tw = bufB + T;           // [T/2]
+  cf* tw = bufB + T;           // [T/2] (POW2) or [T]
   __shared__ float red[24];
   const int sig = blockIdx.x;
-  for (int k = threadIdx.x; k < (T >> 1); k += blockDim.x) {
+  for (int k = threadIdx.x; k < (POW2 ? (T >> 1) : T); k += blockDim.x) {
     float sn, cs;
     sincospif(-2.0f * (float)k / (float)T, &sn, &cs);
     tw[k] = make_float2(cs, sn);
   }
   for (int t = threadIdx.x; t < T; t += blockDim.x) bufA[t] = make_float2(x[(size_t)sig * T + t], 0.f);
   __syncthreads();
-  cf* X = fft_stockham(bufA, bufB, tw, T, false);
+  cf* X = POW2 ? fft_stockham(bufA, bufB, tw, T, false) : fft_mixed(bufA, bufB, tw, T, plan, false);
   for (int k = threadIdx.x; k < T; k += blockDim.x) bufX[k] = X[k];
   __syncthreads();
   for (int k = threadIdx.x; k < nbin; k += blockDim.x) spec[(size_t)sig * nbin + k] = bufX[k];
@@ -117,11 +255,17 @@ __global__ __launch_bounds__(256) void ibs_analytic_kernel(const float* __restri
     for (int k = threadIdx.x; k < T; k += blockDim.x) {
       const float f = (float)k * df;
       float h = 0.f;
-      if (k <= (T >> 1) && f >= bt.lo[b] && f <= bt.hi[b]) h = (k == 0 || k == (T >> 1)) ? 1.f : 2.f;
+      // band-pass (rFFT bins k <= T/2, irfft with n = T) and Hilbert weight in one: 1 at DC and, for even T, at Nyquist; 2 between;
+      // an odd T has no Nyquist bin (k <= T >> 1 = (T - 1) / 2 are all weighted 2)
+      if (POW2) {
+        if (k <= (T >> 1) && f >= bt.lo[b] && f <= bt.hi[b]) h = (k == 0 || k == (T >> 1)) ? 1.f : 2.f;
+      } else {
+        if (k <= (T >> 1) && f >= bt.lo[b] && f <= bt.hi[b]) h = (k == 0 || 2 * k == T) ? 1.f : 2.f;
+      }
       bufA[k] = make_float2(bufX[k].x * h, bufX[k].y * h);
     }
     __syncthreads();
-    cf* a = fft_stockham(bufA, bufB, tw, T, true);
+    cf* a = POW2 ? fft_stockham(bufA, bufB, tw, T, true) : fft_mixed(bufA, bufB, tw, T, plan, true);
     float s1 = 0.f, s2 = 0.f, s4 = 0.f;
     const size_t base = ((size_t)b * nsig + sig) * T;
     for (int t = threadIdx.x; t < T; t += blockDim.x) {
@@ -183,12 +327,16 @@ __device__ __forceinline__ void sincos_atan2(float x, float& s, float& c) {
 constexpr int IBS_RED_FLOATS = 32 * 68;   // per wave: 32 values x (64 lanes + 4 pad)
 constexpr int IBS_TC = 256;          // time steps per LDS tile: 16 channels x 256 x 16 B = 64 KB -> two workgroups per CU;
                                      // one's staging (memory latency) runs beside the other's pair loop
+// POW2: T a power of two, every chunk is full.  Otherwise the LDS row stride Tc is IBS_TC, or for T < IBS_TC the power of two
+// above T, and a chunk holds tn = min(Tc, T - t0) steps (the last one T mod IBS_TC): staging clamps the step to t0 + tn - 1, so
+// no load leaves its row, and the pair loop reads steps t < tn only.  The summation order per lane is that of the POW2 form.
+template <bool POW2>
 __global__ __launch_bounds__(256, 2) void ibs_pairs_kernel(const float* __restrict__ xb, const float* __restrict__ phase,
                                                         const float* __restrict__ stats, const cf* __restrict__ spec,
                                                         float* __restrict__ conn, int B, int C, int T, float fs, int nbin,
                                                         BandTable bt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int Tc = min(T, IBS_TC);
+  const int Tc = POW2 ? min(T, IBS_TC) : (T >= IBS_TC ? IBS_TC : (int)(2u << (31 - __builtin_clz((unsigned)T))));
   f32x4* const lds = (f32x4*)smem;                               // [player * 8 + channel][Tc] quads (a, p, cos p, sin p)
   const int tj = (C + 7) / 8;
   const int tiles = tj * tj;
@@ -221,26 +369,29 @@ __global__ __launch_bounds__(256, 2) void ibs_pairs_kernel(const float* __restri
   // staging: a thread takes one time step of a channel per element -- 4-B loads, coalesced across the wave, and ONE 16-B LDS write at
   // a 16-B lane stride (free of bank conflicts; four time steps per thread would write at a 64-B stride, four ways conflicted).
   // The (signal, phase) values of chunk c + 1 are requested BEFORE the pair loop of chunk c and converted after it, so their memory
-  // latency runs under the loop (T is a power of two >= 64, so every chunk has Tc steps: 16 Tc / 256 <= 16 elements per thread).
+  // latency runs under the loop (Tc <= 256, so 16 Tc / 256 <= 16 elements per thread).
   const int lt = __builtin_ctz(Tc);
   const int nel = 16 * Tc;
   const float* const xbB = xb + (size_t)band * nsig * T;         // this band's rows; element offsets below fit 32 bits (nsig * T < 2^31)
   const float* const phB = phase + (size_t)band * nsig * T;
   float av[16], pv[16];
+  // Extent (any T): row <= (2 B - 1) C + C - 1 = nsig - 1 and the step t0 + min(e & (Tc - 1), tn - 1) <= T - 1, so o < nsig T, the
+  // band's rows.
   auto request = [&](int t0) {
+    const int tl = POW2 ? Tc - 1 : min(Tc, T - t0) - 1;          // last step of the chunk
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int e = min((int)threadIdx.x + 256 * u, nel - 1);
       const int pc = e >> lt, c = pc & 7;                         // pc = player * 8 + channel of the tile
       const uint32_t row = (pc & 8) ? (uint32_t)((b + B) * C + min(j0 + c, C - 1)) : (uint32_t)(b * C + min(i0 + c, C - 1));
-      const uint32_t o = row * (uint32_t)T + (uint32_t)(t0 + (e & (Tc - 1)));
+      const uint32_t o = row * (uint32_t)T + (uint32_t)(t0 + (POW2 ? (e & (Tc - 1)) : min(e & (Tc - 1), tl)));
       av[u] = xbB[o];
       pv[u] = phB[o];
     }
   };
   request(0);
   for (int t0 = 0; t0 < T; t0 += Tc) {
-    const int tn = Tc;
+    const int tn = POW2 ? Tc : min(Tc, T - t0);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
@@ -594,16 +745,35 @@ static int fill_bands(BandTable& bt, const float* lo, const float* hi, int nband
 }
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// radices of a length N <= 2048 in the order fft_mixed wants them: 4s, at most one 2, then the odd primes ascending
+static void fft_plan(FftPlan& plan, int N) {
+  plan.nst = 0;
+  while (N % 4 == 0) { plan.rad[plan.nst++] = 4; N /= 4; }
+  if (N % 2 == 0) { plan.rad[plan.nst++] = 2; N /= 2; }
+  for (int p = 3; N > 1; p += 2)
+    while (N % p == 0) { plan.rad[plan.nst++] = p; N /= p; }
+}
+
 extern "C" int eg_ibs_analytic(const float* x, float* xb, float* phase, float* stats, float* spec, int nsig, int T,
                                float fs, int nbin, const float* band_lo, const float* band_hi, int nbands, void* stream) {
   EG_CHECK(x && xb && phase && stats && spec && band_lo && band_hi, "eg_ibs_analytic: null pointer");
-  EG_CHECK(nsig > 0 && is_pow2(T) && T >= 64 && T <= 2048, "eg_ibs_analytic: T=%d must be a power of two in [64, 2048]", T);
+  EG_CHECK(nsig > 0 && T >= 64 && T <= 2048, "eg_ibs_analytic: T=%d must be in [64, 2048]", T);
   EG_CHECK(nbin > 0 && nbin <= T / 2 + 1, "eg_ibs_analytic: nbin=%d", nbin);
   BandTable bt;
   EG_CHECK(fill_bands(bt, band_lo, band_hi, nbands) == 0, "eg_ibs_analytic: nbands=%d", nbands);
-  const int lds = (3 * T + T / 2) * (int)sizeof(float2);
-  hipLaunchKernelGGL(ibs_analytic_kernel, dim3(nsig), dim3(256), lds, (hipStream_t)stream, x, xb, phase, stats, (cf*)spec,
-                     nsig, T, fs, nbin, bt);
+  FftPlan plan = {};
+  if (is_pow2(T)) {
+    const int lds = (3 * T + T / 2) * (int)sizeof(float2);
+    hipLaunchKernelGGL(ibs_analytic_kernel<true>, dim3(nsig), dim3(256), lds, (hipStream_t)stream, x, xb, phase, stats,
+                       (cf*)spec, nsig, T, fs, nbin, bt, plan);
+  } else {
+    fft_plan(plan, T);
+    // dynamic LDS <= 65 504 B (T = 2047): within the 64 KiB dynamic default; with the 96 B static red[] the workgroup holds up to
+    // 65 600 B, which gfx950 (160 KiB per workgroup) launches as it is (tested at T = 2046 and 2047)
+    const int lds = 4 * T * (int)sizeof(float2);
+    hipLaunchKernelGGL(ibs_analytic_kernel<false>, dim3(nsig), dim3(256), lds, (hipStream_t)stream, x, xb, phase, stats,
+                       (cf*)spec, nsig, T, fs, nbin, bt, plan);
+  }
   EG_LAUNCH_CHECK("ibs_analytic");
   return 0;
 }
@@ -613,23 +783,30 @@ extern "C" int eg_ibs_pairs(const float* xb, const float* phase, const float* st
                             void* stream) {
   EG_CHECK(xb && phase && stats && spec && conn, "eg_ibs_pairs: null pointer");
   EG_CHECK(B > 0 && C > 0 && T > 0, "eg_ibs_pairs: bad shape");
-  EG_CHECK(is_pow2(T) && T >= 64 && T <= 2048, "eg_ibs_pairs: T=%d must be a power of two in [64, 2048]", T);
+  EG_CHECK(T >= 64 && T <= 2048, "eg_ibs_pairs: T=%d must be in [64, 2048]", T);
   EG_CHECK((int64_t)2 * B * C * T < ((int64_t)1 << 31), "eg_ibs_pairs: 2 B C T = %lld elements per band exceed 32-bit offsets", (long long)2 * B * C * T);
   BandTable bt;
   EG_CHECK(fill_bands(bt, band_lo, band_hi, nbands) == 0, "eg_ibs_pairs: nbands=%d", nbands);
-  const int Tc = T < IBS_TC ? T : IBS_TC;
+  const bool pow2 = is_pow2(T);
+  int Tc = IBS_TC;                               // LDS row stride: T itself, or for other T < IBS_TC the power of two above T
+  if (T < IBS_TC) for (Tc = 64; Tc < T; Tc *= 2) {}
   const int lds_time = 16 * Tc * 16;             // 16 channels x Tc quads (a, phase, cos, sin)
   const int lds_tail = 16 * nbin * 8 + (4 * IBS_RED_FLOATS + 4 * 128) * 4;   // spectra + transposed sums + totals
   const int lds = lds_time > lds_tail ? lds_time : lds_tail;
   EG_CHECK(nbin > 0 && lds <= 160 * 1024, "eg_ibs_pairs: nbin=%d needs %d bytes of LDS", nbin, lds);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)ibs_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)ibs_pairs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)ibs_pairs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const int tiles = ((C + 7) / 8) * ((C + 7) / 8);
-  hipLaunchKernelGGL(ibs_pairs_kernel, dim3(B * nbands * tiles), dim3(256), lds, (hipStream_t)stream, xb, phase, stats,
-                     (const cf*)spec, conn, B, C, T, fs, nbin, bt);
+  if (pow2)
+    hipLaunchKernelGGL(ibs_pairs_kernel<true>, dim3(B * nbands * tiles), dim3(256), lds, (hipStream_t)stream, xb, phase, stats,
+                       (const cf*)spec, conn, B, C, T, fs, nbin, bt);
+  else
+    hipLaunchKernelGGL(ibs_pairs_kernel<false>, dim3(B * nbands * tiles), dim3(256), lds, (hipStream_t)stream, xb, phase, stats,
+                       (const cf*)spec, conn, B, C, T, fs, nbin, bt);
   EG_LAUNCH_CHECK("ibs_pairs");
   return 0;
 }

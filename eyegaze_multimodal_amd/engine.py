@@ -56,8 +56,8 @@ ATTN_LONG_MAX_S = 2048      # eg_attention_long_*: flash-style tiles (csrc/atten
 
 def sequence_length(cfg, T: int) -> int:
     """Token count S = 1 (CLS) + IBS tokens + spectrogram tokens + T2 of a model config at window length T, after the checks
-    that need no device: S within the positional table and the attention core's limit, and (with IBS) T a power of two in
-    [64, 2048], the synchrony kernels' range.  Raises EgError naming the limit that fails."""
+    that need no device: S within the positional table and the attention core's limit, and (with IBS) 64 <= T <= 2048, the
+    synchrony kernels' range.  Raises EgError naming the limit that fails."""
     k, s = cfg.conv_kernel_size, cfg.conv_stride
     pad = k // 2
     T1 = (T + 2 * pad - k) // s + 1
@@ -69,8 +69,8 @@ def sequence_length(cfg, T: int) -> int:
         raise L.EgError(f"sequence length {S} exceeds max_len {cfg.max_len} of the positional table")
     if S > ATTN_LONG_MAX_S:
         raise L.EgError(f"sequence length {S} exceeds the attention core's limit of {ATTN_LONG_MAX_S}")
-    if cfg.use_ibs and not (64 <= T <= 2048 and T & (T - 1) == 0):
-        raise L.EgError(f"window length {T}: the IBS synchrony kernels need a power of two in [64, 2048]")
+    if cfg.use_ibs and not 64 <= T <= 2048:
+        raise L.EgError(f"window length {T}: the IBS synchrony kernels need 64 <= T <= 2048")
     return S
 
 

@@ -6,6 +6,7 @@ from __future__ import annotations
 import os
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -29,7 +30,21 @@ def _bands(eng: Engine, bands):
 
 
 def _nbin(eng: Engine, bands) -> int:
-    return min(eng.T // 2 + 1, int(max(b[1] for b in bands) * eng.T / eng.cfg.sampling_rate) + 1)
+    return nbin_for(eng.T, eng.cfg.sampling_rate, max(b[1] for b in bands))
+
+
+def nbin_for(T: int, fs: float, hi: float) -> int:
+    """Spectrum bins kept per signal.  At a power-of-two T: the formula used since before other lengths were accepted, kept as
+    it was (for an integer fs it covers every admitted bin: fs / T and k * fs / T are exact in fp32).  At any other T: every
+    rFFT bin k whose fp32 frequency k * float32(fs / T) (the band test of the kernels and of torch.fft.rfftfreq) is <= hi; the
+    double-precision estimate can fall one bin short when that product rounds down onto hi, and the loop adds such bins."""
+    n = min(T // 2 + 1, int(hi * T / fs) + 1)
+    if T & (T - 1) == 0:
+        return n
+    df, h = np.float32(np.float32(fs) / np.float32(T)), np.float32(hi)
+    while n < T // 2 + 1 and np.float32(n) * df <= h:
+        n += 1
+    return n
 
 
 # ------------------------------------------------------------------------------------------------
