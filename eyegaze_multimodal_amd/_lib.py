@@ -81,6 +81,12 @@ class PackEntry(C.Structure):
                 ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32)]
 
 
+class PackEntryEx(C.Structure):
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("rows", C.c_int32), ("cols", C.c_int32), ("ldd", C.c_int32),
+                ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32), ("p0", C.c_int32), ("p1", C.c_int32),
+                ("p2", C.c_int32), ("p3", C.c_int32), ("src_elems", C.c_int64), ("dst_elems", C.c_int64)]
+
+
 class TNProblem(C.Structure):
     _fields_ = [("dY", C.c_uint64), ("X", C.c_uint64), ("partial", C.c_uint64), ("ldy", C.c_int64), ("ldx", C.c_int64),
                 ("N", C.c_int32), ("K", C.c_int32), ("part_rows", C.c_int32), ("has_bias", C.c_int32), ("blk0", C.c_int32),
@@ -105,6 +111,8 @@ SIGNATURES = {
     "eg_device_info": [C.POINTER(C.c_int), C.c_char_p, _I],
     "eg_window_pack": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_pack_table": [_P, _I, _I, _I, _P],
+    "eg_pack_table_ex_check": [_P, _I, _I, C.POINTER(C.c_int)],
+    "eg_pack_table_ex": [_P, _I, _I, _I, _P],
     "eg_cast": [_P, _P, _L, _I, _P],
     "eg_transpose_cast": [_P, _P, _I, _I, _I, _I, _P],
     "eg_pack_conv_weight": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -140,6 +148,11 @@ SIGNATURES = {
     "eg_classifier_ce_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "eg_batch_rowsum": [_P, _P, _I, _I, _I, _I, _I, _P],
     "eg_rows_gather_gate": [_P, _P, _P, RowMap, _I, _I, _I, _I, _I, _I, _F, _I, _P],
+    "eg_heads_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U, _P, _I, _P],
+    "eg_classifier_ce_bwd_fused": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
+    "eg_heads_bwd_chain": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "eg_heads_bwd_pool": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "eg_token_grad_tail": [_P, _P, _P, RowMap, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "eg_grad_sqnorm": [_P, _L, _P, _I, _P],
     "eg_clip_coef": [_P, _I, _F, _P, _P],
     "eg_adamw": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _P],

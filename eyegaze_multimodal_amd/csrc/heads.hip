@@ -67,11 +67,11 @@ __global__ void pool_fuse_fwd_kernel(const T* __restrict__ z, float* __restrict_
 
 // backward of the above: writes the full dz [2B, S, D] (zeros where nothing flows)
 template <typename T>
-__global__ void pool_fuse_bwd_kernel(const T* __restrict__ z, const T* __restrict__ dcomb, const T* __restrict__ dzf,
-                                     const float* __restrict__ gcls1, const float* __restrict__ gcls2,
-                                     const T* __restrict__ dibs_pool, const float* __restrict__ gibs_pool,
-                                     T* __restrict__ dz, int B, int S, int D, int off, int n_ibs, int ibs_first) {
-  const int b = blockIdx.x;
+__device__ __forceinline__ void pool_fuse_bwd_sample(const int b, const T* __restrict__ z, const T* __restrict__ dcomb,
+                                                     const T* __restrict__ dzf, const float* __restrict__ gcls1,
+                                                     const float* __restrict__ gcls2, const T* __restrict__ dibs_pool,
+                                                     const float* __restrict__ gibs_pool, T* __restrict__ dz, int B, int S, int D,
+                                                     int off, int n_ibs, int ibs_first) {
   const T* z1 = z + (size_t)b * S * D;
   const T* z2 = z + (size_t)(b + B) * S * D;
   T* d1 = dz + (size_t)b * S * D;
@@ -105,22 +105,26 @@ __global__ void pool_fuse_bwd_kernel(const T* __restrict__ z, const T* __restric
     }
   }
 }
+template <typename T>
+__global__ void pool_fuse_bwd_kernel(const T* __restrict__ z, const T* __restrict__ dcomb, const T* __restrict__ dzf,
+                                     const float* __restrict__ gcls1, const float* __restrict__ gcls2,
+                                     const T* __restrict__ dibs_pool, const float* __restrict__ gibs_pool,
+                                     T* __restrict__ dz, int B, int S, int D, int off, int n_ibs, int ibs_first) {
+  pool_fuse_bwd_sample<T>(blockIdx.x, z, dcomb, dzf, gcls1, gcls2, dibs_pool, gibs_pool, dz, B, S, D, off, n_ibs, ibs_first);
+}
 
 // logits = h W^T + b  (ncls <= 16), per-sample CE; one wave per sample (D:1104-1105 / 1078 + D:1244 / 1250)
+// one wave, one sample b whose K hidden values start at hrow (global or LDS)
 template <typename T>
-__global__ __launch_bounds__(256) void classifier_ce_fwd_kernel(const T* __restrict__ h, const float* __restrict__ W,
-                                                                const float* __restrict__ bias,
-                                                                const long long* __restrict__ labels,
-                                                                float* __restrict__ logits, float* __restrict__ sample_loss,
-                                                                int B, int K, int ncls) {
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;
+__device__ __forceinline__ void classifier_ce_fwd_row(const T* hrow, const float* __restrict__ W, const float* __restrict__ bias,
+                                                      const long long* __restrict__ labels, float* __restrict__ logits,
+                                                      float* __restrict__ sample_loss, const int b, int K, int ncls,
+                                                      const int lane) {
   float lg[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) lg[c] = 0.f;
   for (int k = lane; k < K; k += 64) {
-    const float x = Elem<T>::ld(h + (size_t)b * K + k);
+    const float x = Elem<T>::ld(hrow + k);
 #pragma unroll
     for (int c = 0; c < 16; ++c)
       if (c < ncls) lg[c] += x * W[(size_t)c * K + k];
@@ -151,10 +155,25 @@ __global__ __launch_bounds__(256) void classifier_ce_fwd_kernel(const T* __restr
   }
 }
 
-__global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out, int n) {
-  __shared__ float red[256];
+template <typename T>
+__global__ __launch_bounds__(256) void classifier_ce_fwd_kernel(const T* __restrict__ h, const float* __restrict__ W,
+                                                                const float* __restrict__ bias,
+                                                                const long long* __restrict__ labels,
+                                                                float* __restrict__ logits, float* __restrict__ sample_loss,
+                                                                int B, int K, int ncls) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  classifier_ce_fwd_row<T>(h + (size_t)b * K, W, bias, labels, logits, sample_loss, b, K, ncls, lane);
+}
+
+// *out = mean(v[0..n)) by one 256-thread workgroup.  COHERENT: v was written by other workgroups of the same launch (the loads
+// bypass this CU's vector cache).
+template <bool COHERENT>
+__device__ __forceinline__ void block_mean256(const float* v, float* __restrict__ out, int n, float* red) {
   float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += v[i];
+  for (int i = threadIdx.x; i < n; i += 256)
+    s += COHERENT ? __hip_atomic_load(v + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : v[i];
   red[threadIdx.x] = s;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -164,19 +183,16 @@ __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out
   if (threadIdx.x == 0) *out = red[0] / (float)n;
 }
 
+__global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out, int n) {
+  __shared__ float red[256];
+  block_mean256<false>(v, out, n, red);
+}
+
 // dlogits[b,c] = gloss * (softmax - onehot)/B + glogits[b,c];  dh[b,k] = (sum_c dlogits[b,c] W[c,k]) * gate(h>0)*gate_scale
-template <typename T>
-__global__ __launch_bounds__(256) void classifier_ce_bwd_kernel(const T* __restrict__ h, const float* __restrict__ W,
-                                                                const float* __restrict__ logits,
-                                                                const long long* __restrict__ labels,
-                                                                const float* __restrict__ gloss,
-                                                                const float* __restrict__ glogits,
-                                                                float* __restrict__ dlogits, T* __restrict__ dh, int B,
-                                                                int K, int ncls, int use_gate, float gate_scale) {
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;
-  float dl[16];
+// dl[c] = d loss / d logits[b, c] (0 for c >= ncls)
+__device__ __forceinline__ void classifier_dlogits_row(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                       const float* __restrict__ gloss, const float* __restrict__ glogits,
+                                                       const int b, int B, int ncls, float (&dl)[16]) {
   float mx = -INFINITY;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
@@ -198,8 +214,24 @@ __global__ __launch_bounds__(256) void classifier_ce_bwd_kernel(const T* __restr
       float d = gl * (dl[c] / se - (c == y ? 1.f : 0.f));
       if (glogits) d += glogits[(size_t)b * ncls + c];
       dl[c] = d;
-      if (lane == 0) dlogits[(size_t)b * ncls + c] = d;
     }
+}
+
+// one wave, one sample: dlogits row and the gated dh row
+template <typename T>
+__device__ __forceinline__ void classifier_ce_bwd_row(const int b, const int lane, const T* __restrict__ h,
+                                                      const float* __restrict__ W, const float* __restrict__ logits,
+                                                      const long long* __restrict__ labels, const float* __restrict__ gloss,
+                                                      const float* __restrict__ glogits, float* __restrict__ dlogits,
+                                                      T* __restrict__ dh, int B, int K, int ncls, int use_gate,
+                                                      float gate_scale) {
+  float dl[16];
+  classifier_dlogits_row(logits, labels, gloss, glogits, b, B, ncls, dl);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+      if (c < ncls) dlogits[(size_t)b * ncls + c] = dl[c];
+  }
   for (int k = lane; k < K; k += 64) {
     float s = 0.f;
 #pragma unroll
@@ -208,6 +240,20 @@ __global__ __launch_bounds__(256) void classifier_ce_bwd_kernel(const T* __restr
     if (use_gate) s = Elem<T>::ld(h + (size_t)b * K + k) > 0.f ? s * gate_scale : 0.f;
     Elem<T>::st(dh + (size_t)b * K + k, s);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void classifier_ce_bwd_kernel(const T* __restrict__ h, const float* __restrict__ W,
+                                                                const float* __restrict__ logits,
+                                                                const long long* __restrict__ labels,
+                                                                const float* __restrict__ gloss,
+                                                                const float* __restrict__ glogits,
+                                                                float* __restrict__ dlogits, T* __restrict__ dh, int B,
+                                                                int K, int ncls, int use_gate, float gate_scale) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  classifier_ce_bwd_row<T>(b, lane, h, W, logits, labels, gloss, glogits, dlogits, dh, B, K, ncls, use_gate, gate_scale);
 }
 
 // dW[c,k] = sum_b dlogits[b,c] h[b,k];  db[c] = sum_b dlogits[b,c]      grid = (ncls, ceil(K/64)); 64 columns x 4 batch lanes
@@ -462,6 +508,397 @@ __global__ __launch_bounds__(128) void fuzzy_gate_bwd_kernel(const float* __rest
   if (threadIdx.x < 12) partial[(size_t)blockIdx.x * 12 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x];
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Fused forms of the step's [B, d]-sized tail (d_model == 256, 16-bit compute dtypes).  Each replaces several of the launches
+// above with one; the arithmetic keeps their order (same MFMA shape and K order as gemm_nt_kernel / tn_body, same rounding
+// points, same summation trees), so every output has the bits the separate launches give.
+// ------------------------------------------------------------------------------------------------
+
+// eg_token_grad_tail: ONE pass over dseq [NB, S, D] gives out[s, :] = sum_b dseq[b, s, :] (batch_rowsum_kernel's sum: sixteen
+// chains over b mod 16 -- lane bl of that kernel keeps chains bl, bl + 4, bl + 8, bl + 12 and folds its tail rows into the first
+// -- combined as ((c0 + c4) + (c8 + c12)) per lane and then lane 0 + 1 + 2 + 3), the cls_token copy of row 0, and the gated
+// rows dst[b, s - off, :] of rows_gather_gate_kernel.  grid = (S, D / 64); 256 threads = 16 chains x 16 four-column lanes.
+template <typename T>
+__global__ __launch_bounds__(256) void token_grad_tail_kernel(const T* __restrict__ dseq, const T* __restrict__ gate,
+                                                              T* __restrict__ dst, RowMap dmap, float* __restrict__ out,
+                                                              float* __restrict__ cls_out, int NB, int S, int D, int R, int off,
+                                                              float gate_scale) {
+  __shared__ float red[16][64];
+  const int s = blockIdx.x, tx = threadIdx.x & 15, r = threadIdx.x >> 4;
+  const int n = blockIdx.y * 64 + tx * 4;
+  const int bl = r & 3, j = r >> 2;
+  const int iters = NB - 12 - bl > 0 ? (NB - 12 - bl + 15) / 16 : 0;   // trips of batch_rowsum_kernel's 16-row loop for lane bl
+  const bool gather = s >= off && s - off < R;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  // rows b0, b0 + step, ... (cnt <= 8 of them): every load is requested before the first sum or store, the sums then run in row order
+  auto rows8 = [&](int b0, int step, int cnt) {
+    u32x2 dv[8], gv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int b = b0 + step * min(u, cnt - 1);
+      dv[u] = *(const u32x2*)(dseq + ((size_t)b * S + s) * D + n);
+      if (gather) gv[u] = *(const u32x2*)(gate + ((size_t)b * R + (s - off)) * D + n);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (u < cnt) {
+        const int b = b0 + step * u;
+        float v[4];
+        load4((const T*)&dv[u], v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += v[e];
+        if (gather) {
+          float g4[4];
+          load4((const T*)&gv[u], g4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = g4[e] > 0.f ? v[e] * gate_scale : 0.f;
+          store4(dst + row_off(dmap, b * R + (s - off)) + n, v);
+        }
+      }
+    }
+  };
+  for (int i = 0; i < iters; i += 8) rows8(r + 16 * i, 16, min(8, iters - i));
+  if (j == 0) {
+    const int b0 = bl + 16 * iters;
+    if (b0 < NB) rows8(b0, 4, (NB - b0 + 3) / 4);      // at most three rows
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[r][tx * 4 + e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int c = threadIdx.x;
+    float a[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) a[l] = (red[l][c] + red[l + 4][c]) + (red[l + 8][c] + red[l + 12][c]);
+    const float t = a[0] + a[1] + a[2] + a[3];
+    const int col = blockIdx.y * 64 + c;
+    out[(size_t)s * D + col] = t;
+    if (s == 0 && cls_out) cls_out[col] = t;
+  }
+}
+
+constexpr int HD = 256;            // d_model of the fused head kernels
+constexpr int HK = 3 * HD;         // width of comb / zf
+constexpr int HP = HD + 8;         // LDS pitch (elements) of a 16-row operand image: 528 B, 16-B aligned, conflict-free b128 reads
+
+// acc[t] += X[16 rows, K] * W[n, K]^T for the wave's NT column tiles (W rows n0 + 16 t + l15), k-steps [ks0, ks1) of 32.
+// The operand order (weights first) and the ascending k-steps are gemm_nt_kernel's, so the sums carry its bits.  X rows are read
+// at xrow (this lane's row, 8 g elements in), advancing 32 elements per step; W straight from global memory (L2-resident).
+// These launches have a handful of workgroups and one dependent pass over the weights each, so what they cost is load round trips:
+// a wave requests ALL its weight fragments of a product (NT x KS 16-B loads per lane) before the first MFMA and pays one trip.
+template <typename T, int NT, int KS>
+__device__ __forceinline__ void head_mma(f32x4 (&acc)[NT], const T* xrow, const T* __restrict__ W, const int ldw, const int n0,
+                                         const int lane) {
+  typedef typename H16<T>::frag frag;
+  const int l15 = lane & 15, g = lane >> 4;
+  const T* wp = W + (size_t)(n0 + l15) * ldw + 8 * g;
+  frag wf[KS][NT];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) wf[ks][t] = *(const frag*)(wp + (size_t)16 * t * ldw + 32 * ks);
+  __builtin_amdgcn_sched_barrier(0);      // keep the loads above in one clause (the scheduler would sink them to their uses)
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const frag xf = *(const frag*)(xrow + 32 * ks);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = H16<T>::mfma(wf[ks][t], xf, acc[t]);
+  }
+}
+
+template <typename T>
+struct HeadsFwd {
+  const T* comb; T* zf; T* hcl; const T* Wsf; const T* Wc0;
+  const float* bsf; const float* bc0; const float* W3; const float* b3;
+  const long long* labels; float* logits; float* sloss; float* loss; unsigned int* counter;
+  const eg_step_state* st;
+  int B, ncls;
+  DropCfg d1;
+};
+
+// eg_heads_fwd: zf[:, :256] = comb Wsf^T + b -> hcl = dropout(relu(zf Wc0^T + b)) -> logits, per-sample CE, mean loss.
+// One 512-thread workgroup per 16 samples; wave w owns output columns 32 w .. + 31 of both products.  The 16 x 768 operand rows
+// sit in LDS (comb, then zf: its first 256 columns are product 1's output, the pooled rest eg_pool_fuse_fwd's), the weights come
+// from L2 as MFMA operands in one trip per product; zf and hcl are also stored (the backward reads them).  The workgroup that
+// finishes last (a device counter, reset for the next launch) takes the mean of the per-sample losses in mean_kernel's order.
+constexpr int HKP = HK + 8;        // LDS pitch (elements) of a 768-wide operand row: 1552 B
+template <typename T>
+__global__ __launch_bounds__(512) void heads_fwd_kernel(HeadsFwd<T> p) {
+  __shared__ __attribute__((aligned(16))) T xs[2][16][HKP];     // [0] comb rows, [1] zf rows
+  __shared__ __attribute__((aligned(16))) T hs[16][HP];
+  __shared__ float red[256];
+  __shared__ int last_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * 16;
+  const int m = m0 + l15;                            // rows beyond B: operands clamped, nothing stored
+  const int n0 = 32 * wave;
+  for (int c = tid; c < 16 * (HK / 8); c += 512) {   // 16-B chunks: comb whole, zf's pooled columns
+    const int r = c / (HK / 8), ch = c % (HK / 8);
+    const size_t row = (size_t)min(m0 + r, p.B - 1) * HK;
+    *(u32x4*)&xs[0][r][ch * 8] = *(const u32x4*)(p.comb + row + ch * 8);
+    if (ch >= HD / 8) *(u32x4*)&xs[1][r][ch * 8] = *(const u32x4*)(p.zf + row + ch * 8);
+  }
+  __syncthreads();
+
+  f32x4 acc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  head_mma<T, 2, HK / 32>(acc, &xs[0][l15][8 * g], p.Wsf, HK, n0, lane);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int n = n0 + 16 * t + 4 * g;
+    float bv[4], v[4];
+    load4(p.bsf + n, bv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = acc[t][e] + bv[e];
+    store4(&xs[1][l15][n], v);
+    if (m < p.B) store4(p.zf + (size_t)m * HK + n, v);
+    acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  __syncthreads();
+  head_mma<T, 2, HK / 32>(acc, &xs[1][l15][8 * g], p.Wc0, HK, n0, lane);
+  uint32_t seed_lo = 0, seed_hi = 0;
+  if (p.d1.thresh) {
+    seed_lo = p.st->seed_lo;
+    seed_hi = p.st->seed_hi;
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int n = n0 + 16 * t + 4 * g;
+    float bv[4], v[4];
+    load4(p.bc0 + n, bv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[t][e] + bv[e], 0.f);
+    eg_dropout_run<4>(v, p.d1, seed_lo, seed_hi, (uint32_t)m * (uint32_t)HD + (uint32_t)n);
+    store4(&hs[l15][n], v);
+    if (m < p.B) store4(p.hcl + (size_t)m * HD + n, v);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = 2 * wave + i;
+    if (m0 + r < p.B)
+      classifier_ce_fwd_row<T>(&hs[r][0], p.W3, p.b3, p.labels, p.logits, p.sloss, m0 + r, HD, p.ncls, lane);
+  }
+  if (!p.labels) return;
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) last_s = atomicAdd(p.counter, 1u) == gridDim.x - 1;
+  __syncthreads();
+  if (!last_s || tid >= 256) return;                 // (the waves that leave take no further part in a barrier)
+  __threadfence();
+  block_mean256<true>(p.sloss, p.loss, p.B, red);
+  if (tid == 0) *p.counter = 0u;
+}
+
+// dW[n0 .. n0+63][k0 .. k0+63] = sum_m dY[m, n] X[m, k] (+ db = column sums of dY, from the k0 == 0 tiles) for M <= 256 rows,
+// with the bits of eg_gemm_tn + eg_reduce_partials at that size: rows [0, 128) and [128, M) are two slabs, each one MFMA chain
+// over ascending 32-row steps (tn_body's operand order: X first), the slabs added last; the bias sums run over 16-row halves of
+// every 32-row step as tn_tile_colsum's do.  Rows >= M are staged as zeros (exact).  smem: 2 x 64 x TNP elements.
+constexpr int TNP = 128 + 8;       // pitch (elements) of the transposed [64 columns][128 rows] operand images
+template <typename T>
+__device__ __forceinline__ void small_tn_tile(const T* __restrict__ dY, const int ldy, const T* __restrict__ X, const int ldx,
+                                              float* __restrict__ dW, float* __restrict__ db, const int M, const int K,
+                                              const int tile, char* smem) {
+  typedef typename H16<T>::frag frag;
+  T (*Yt)[TNP] = (T(*)[TNP])smem;
+  T (*Xt)[TNP] = (T(*)[TNP])(smem + 64 * TNP * sizeof(T));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int tiles_k = K / 64;
+  const int n0 = (tile / tiles_k) * 64, k0 = (tile % tiles_k) * 64;
+  const int nsplit = M > 128 ? 2 : 1;
+  // 4 waves: wave w takes k rows 16 w .. + 15 and all four 16-column tiles; 8 waves: tiles 2 (w / 4) and 2 (w / 4) + 1 only
+  const int kw = wave & 3, t0 = (wave >> 2) * 2, t1 = blockDim.x == 512 ? t0 + 2 : 4;
+  f32x4 acc[2][4];
+#pragma unroll
+  for (int sp = 0; sp < 2; ++sp)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[sp][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float bsplit[2] = {0.f, 0.f};
+  for (int sp = 0; sp < nsplit; ++sp) {
+    if (sp) __syncthreads();
+    for (int c = tid; c < 1024; c += blockDim.x) {
+      const int row = c >> 3, ch = c & 7;
+      const int m = 128 * sp + row;
+      u32x4 y = {0u, 0u, 0u, 0u}, x = {0u, 0u, 0u, 0u};
+      if (m < M) {
+        y = *(const u32x4*)(dY + (size_t)m * ldy + n0 + ch * 8);
+        x = *(const u32x4*)(X + (size_t)m * ldx + k0 + ch * 8);
+      }
+      const uint16_t* ye = (const uint16_t*)&y;
+      const uint16_t* xe = (const uint16_t*)&x;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        *(uint16_t*)&Yt[ch * 8 + e][row] = ye[e];
+        *(uint16_t*)&Xt[ch * 8 + e][row] = xe[e];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const frag xf = *(const frag*)&Xt[16 * kw + l15][32 * ks + 8 * g];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (t >= t0 && t < t1) {
+          const frag yf = *(const frag*)&Yt[16 * t + l15][32 * ks + 8 * g];
+          acc[sp][t] = H16<T>::mfma(xf, yf, acc[sp][t]);
+        }
+    }
+    if (db && k0 == 0 && tid < 64) {
+      float bh[2] = {0.f, 0.f};
+      for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          float cs = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) cs += H16<T>::ld(Yt[tid][32 * sub + 16 * half + i]);
+          bh[half] += cs;
+        }
+      bsplit[sp] = bh[0] + bh[1];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (t >= t0 && t < t1) {
+      const int n = n0 + 16 * t + l15, k = k0 + 16 * kw + 4 * g;
+      f32x4 o = acc[0][t];
+      if (nsplit == 2) o += acc[1][t];
+      *(f32x4*)(dW + (size_t)n * K + k) = o;
+    }
+  if (db && k0 == 0 && tid < 64) db[n0 + tid] = nsplit == 2 ? bsplit[0] + bsplit[1] : bsplit[0];
+}
+constexpr int TN_SMEM = 2 * 64 * TNP * 2;    // 34 816 B
+
+// eg_classifier_ce_bwd_fused: classifier_ce_bwd_kernel's rows (blocks [0, nce)) and classifier_wgrad_kernel's sums (blocks
+// [nce, ..): one per 64 columns of h, all classes) in ONE launch.  A weight-gradient block derives the dlogits itself (the same
+// function of logits / labels / upstream gradients the row blocks store) instead of waiting for another launch to have written
+// them, and stages its [B, 64] slice of h in LDS with every load in flight at once; the sums keep classifier_wgrad_kernel's order
+// (four lanes over b mod 4, ascending b, then lane 0 + 1 + 2 + 3).  B <= 256.
+template <typename T>
+__global__ __launch_bounds__(256) void classifier_ce_bwd_fused_kernel(const T* __restrict__ h, const float* __restrict__ W,
+                                                                      const float* __restrict__ logits,
+                                                                      const long long* __restrict__ labels,
+                                                                      const float* __restrict__ gloss,
+                                                                      const float* __restrict__ glogits,
+                                                                      float* __restrict__ dlogits, T* __restrict__ dh,
+                                                                      float* __restrict__ dW, float* __restrict__ db, int B,
+                                                                      int K, int ncls, int use_gate, float gate_scale, int nce) {
+  __shared__ __attribute__((aligned(16))) T hts[256][64];
+  __shared__ float dls[256][16];
+  __shared__ float red[4][64], redb[4];
+  const int lane = threadIdx.x & 63, bl = threadIdx.x >> 6;
+  if ((int)blockIdx.x < nce) {
+    const int b = blockIdx.x * 4 + bl;
+    if (b < B) classifier_ce_bwd_row<T>(b, lane, h, W, logits, labels, gloss, glogits, dlogits, dh, B, K, ncls, use_gate, gate_scale);
+    return;
+  }
+  const int kb = (blockIdx.x - nce) * 64, k = kb + lane;
+  const bool wide = kb + 64 <= K && K % 8 == 0;
+  for (int c = threadIdx.x; c < B * 8; c += 256) {           // 16-B chunks of the [B, 64] slice
+    const int b = c >> 3, ch = c & 7;
+    if (wide) *(u32x4*)&hts[b][ch * 8] = *(const u32x4*)(h + (size_t)b * K + kb + ch * 8);
+    else
+      for (int e = 0; e < 8; ++e)
+        if (kb + ch * 8 + e < K) hts[b][ch * 8 + e] = h[(size_t)b * K + kb + ch * 8 + e];
+  }
+  for (int b = threadIdx.x; b < B; b += 256) {
+    float dl[16];
+    classifier_dlogits_row(logits, labels, gloss, glogits, b, B, ncls, dl);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) dls[b][c] = dl[c];
+  }
+  __syncthreads();
+  float s[16], sb[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) s[c] = sb[c] = 0.f;
+  for (int b = bl; b < B; b += 4) {
+    const float hv = H16<T>::ld(hts[b][lane]);
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+      if (c < ncls) {
+        const float dl = dls[b][c];
+        if (k < K) s[c] = fmaf(dl, hv, s[c]);
+        sb[c] += dl;
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < 16; ++c)
+    if (c < ncls) {
+      red[bl][lane] = s[c];
+      if (lane == 0) redb[bl] = sb[c];
+      __syncthreads();
+      if (bl == 0) {
+        if (k < K) dW[(size_t)c * K + k] = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+        if (kb == 0 && lane == 0) db[c] = redb[0] + redb[1] + redb[2] + redb[3];
+      }
+      __syncthreads();
+    }
+}
+
+// eg_heads_bwd_chain: blocks [0, nrt): 16 samples each (512 threads, wave w owns columns 96 w .. + 95), dzf = dhcl Wc0 (all 768
+// columns, stored) then dcomb = dzf[:, :256] Wsf with both 16 x 256 operands in LDS and each product's weights requested in one
+// trip; blocks [nrt, nrt + 48): classifier.0's weight and bias gradient tiles (dhcl^T zf).
+template <typename T>
+__global__ __launch_bounds__(512) void heads_bwd_chain_kernel(const T* __restrict__ dhcl, const T* __restrict__ c0T,
+                                                              const T* __restrict__ sfT, const T* __restrict__ zf,
+                                                              T* __restrict__ dzf, T* __restrict__ dcomb, float* __restrict__ dWc0,
+                                                              float* __restrict__ dbc0, int B, int nrt) {
+  __shared__ __attribute__((aligned(16))) char smem[TN_SMEM];
+  if ((int)blockIdx.x >= nrt) {
+    small_tn_tile<T>(dhcl, HD, zf, HK, dWc0, dbc0, B, HK, blockIdx.x - nrt, smem);
+    return;
+  }
+  T (*xs)[16][HP] = (T(*)[16][HP])smem;          // [0] dhcl rows, [1] dzf[:, :256] rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * 16;
+  const int m = m0 + l15;
+  {
+    const int r = tid >> 5, ch = tid & 31;       // 16 rows x 32 chunks of 16 B
+    *(u32x4*)&xs[0][r][ch * 8] = *(const u32x4*)(dhcl + (size_t)min(m0 + r, B - 1) * HD + ch * 8);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int prod = 0; prod < 2; ++prod) {
+    const T* W = prod ? sfT : c0T;
+    T* out = prod ? dcomb : dzf;
+    const int n0 = 96 * wave;
+    f32x4 acc[6];
+#pragma unroll
+    for (int t = 0; t < 6; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    head_mma<T, 6, HD / 32>(acc, &xs[prod][l15][8 * g], W, HD, n0, lane);
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      const int n = n0 + 16 * t + 4 * g;
+      float v[4] = {acc[t][0] + 0.f, acc[t][1] + 0.f, acc[t][2] + 0.f, acc[t][3] + 0.f};   // (gemm_nt's bias-free epilogue adds 0)
+      if (!prod && n < HD) store4(&xs[1][l15][n], v);
+      if (m < B) store4(out + (size_t)m * HK + n, v);
+    }
+    __syncthreads();
+  }
+}
+
+// eg_heads_bwd_pool: blocks [0, B): pool_fuse_bwd_kernel's samples; blocks [B, B + 48): symmetric_fusion.proj's weight and
+// bias gradient tiles (dzf[:, :256]^T comb).
+template <typename T>
+__global__ __launch_bounds__(256) void heads_bwd_pool_kernel(const T* __restrict__ z, const T* __restrict__ dcomb,
+                                                             const T* __restrict__ dzf, const float* __restrict__ gcls1,
+                                                             const float* __restrict__ gcls2, const T* __restrict__ dibs_pool,
+                                                             const float* __restrict__ gibs_pool, T* __restrict__ dz,
+                                                             const T* __restrict__ comb, float* __restrict__ dWsf,
+                                                             float* __restrict__ dbsf, int B, int S, int D, int off, int n_ibs,
+                                                             int ibs_first) {
+  __shared__ __attribute__((aligned(16))) char smem[TN_SMEM];
+  if ((int)blockIdx.x >= B) {
+    small_tn_tile<T>(dzf, HK, comb, HK, dWsf, dbsf, B, HK, blockIdx.x - B, smem);
+    return;
+  }
+  pool_fuse_bwd_sample<T>(blockIdx.x, z, dcomb, dzf, gcls1, gcls2, dibs_pool, gibs_pool, dz, B, S, D, off, n_ibs, ibs_first);
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_BF16, CALL_F16, CALL_F32, who) \
@@ -590,6 +1027,118 @@ extern "C" int eg_rows_gather_gate(const void* src, const void* gate, void* dst,
              hipLaunchKernelGGL(rows_gather_gate_kernel<float>, grid, dim3(64), 0, s, (const float*)src, (const float*)gate, (float*)dst, to_rowmap(dmap), S, D, R, off, pair_shift, gate_scale),
              "eg_rows_gather_gate");
   EG_LAUNCH_CHECK("rows_gather_gate");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// fused tail entry points (16-bit compute dtypes, d_model == 256)
+// ------------------------------------------------------------------------------------------------
+#define DISPATCH_H16(dtype, CALL_BF16, CALL_F16, who)         \
+  if ((dtype) == EG_BF16) { CALL_BF16; }                      \
+  else if ((dtype) == EG_F16) { CALL_F16; }                   \
+  else return eg_fail("%s: dtype %d (bf16 / fp16 only)", who, (int)(dtype));
+
+extern "C" int eg_token_grad_tail(const void* dseq, const void* gate, void* dst, eg_rowmap dmap, float* pos_grad,
+                                  float* cls_grad, int NB, int S, int D, int R, int off, float gate_scale, int dtype,
+                                  void* stream) {
+  EG_CHECK(dseq && gate && dst && pos_grad, "eg_token_grad_tail: null pointer");
+  EG_CHECK(NB > 0 && S > 0 && R > 0 && off >= 0 && off + R <= S, "eg_token_grad_tail: bad shape NB=%d S=%d R=%d off=%d", NB, S, R, off);
+  EG_CHECK(D > 0 && D % 64 == 0, "eg_token_grad_tail: D=%d must be a multiple of 64", D);
+  EG_CHECK(dmap.row_stride % 4 == 0 && dmap.group_stride % 4 == 0, "eg_token_grad_tail: destination rows must be 8-B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(S, D / 64);
+  DISPATCH_H16(dtype,
+               hipLaunchKernelGGL(token_grad_tail_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dseq, (const bf16_t*)gate, (bf16_t*)dst, to_rowmap(dmap), pos_grad, cls_grad, NB, S, D, R, off, gate_scale),
+               hipLaunchKernelGGL(token_grad_tail_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)dseq, (const f16_t*)gate, (f16_t*)dst, to_rowmap(dmap), pos_grad, cls_grad, NB, S, D, R, off, gate_scale),
+               "eg_token_grad_tail");
+  EG_LAUNCH_CHECK("token_grad_tail");
+  return 0;
+}
+
+template <typename T>
+static void launch_heads_fwd(const void* comb, void* zf, void* hcl, const void* Wsf, const float* bsf, const void* Wc0,
+                             const float* bc0, const float* W3, const float* b3, const int64_t* labels, float* logits,
+                             float* sloss, float* loss, uint32_t* counter, int B, int ncls, float drop_p, uint32_t drop_site,
+                             const eg_step_state* state, hipStream_t s) {
+  HeadsFwd<T> p;
+  p.comb = (const T*)comb; p.zf = (T*)zf; p.hcl = (T*)hcl; p.Wsf = (const T*)Wsf; p.Wc0 = (const T*)Wc0;
+  p.bsf = bsf; p.bc0 = bc0; p.W3 = W3; p.b3 = b3;
+  p.labels = (const long long*)labels; p.logits = logits; p.sloss = sloss; p.loss = loss; p.counter = counter;
+  p.st = state; p.B = B; p.ncls = ncls; p.d1 = make_drop(drop_p, drop_site);
+  hipLaunchKernelGGL(heads_fwd_kernel<T>, dim3((B + 15) / 16), dim3(512), 0, s, p);
+}
+
+extern "C" int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* Wsf, const float* bsf, const void* Wc0,
+                            const float* bc0, const float* W3, const float* b3, const int64_t* labels, float* logits,
+                            float* sample_loss, float* loss, uint32_t* counter, int B, int D, int ncls, float drop_p,
+                            uint32_t drop_site, const eg_step_state* state, int dtype, void* stream) {
+  EG_CHECK(comb && zf && hcl && Wsf && bsf && Wc0 && bc0 && W3 && b3 && logits, "eg_heads_fwd: null pointer");
+  EG_CHECK(D == HD, "eg_heads_fwd: d_model=%d (the fused heads are built for 256)", D);
+  EG_CHECK(B > 0 && ncls > 0 && ncls <= 16, "eg_heads_fwd: B=%d, ncls=%d must be in [1,16]", B, ncls);
+  EG_CHECK(!labels || (sample_loss && loss && counter), "eg_heads_fwd: labels need sample_loss, loss and the launch counter");
+  EG_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || state), "eg_heads_fwd: dropout needs the step state");
+  EG_CHECK(((uintptr_t)comb | (uintptr_t)zf | (uintptr_t)hcl | (uintptr_t)Wsf | (uintptr_t)Wc0 | (uintptr_t)bsf | (uintptr_t)bc0) % 16 == 0,
+           "eg_heads_fwd: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  DISPATCH_H16(dtype,
+               launch_heads_fwd<bf16_t>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B, ncls, drop_p, drop_site, state, s),
+               launch_heads_fwd<f16_t>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B, ncls, drop_p, drop_site, state, s),
+               "eg_heads_fwd");
+  EG_LAUNCH_CHECK("heads_fwd");
+  return 0;
+}
+
+extern "C" int eg_classifier_ce_bwd_fused(const void* h, const float* W, const float* logits, const int64_t* labels,
+                                          const float* gloss, const float* glogits, float* dlogits, void* dh, float* dW,
+                                          float* db, int B, int K, int ncls, int use_gate, float gate_scale, int dtype,
+                                          void* stream) {
+  EG_CHECK(h && W && logits && dlogits && dh && dW && db, "eg_classifier_ce_bwd_fused: null pointer");
+  EG_CHECK(B > 0 && B <= 256 && K > 0 && ncls > 0 && ncls <= 16, "eg_classifier_ce_bwd_fused: bad shape B=%d (<= 256) K=%d ncls=%d", B, K, ncls);
+  EG_CHECK((uintptr_t)h % 16 == 0, "eg_classifier_ce_bwd_fused: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  const int nce = (B + 3) / 4;
+  dim3 grid(nce + (K + 63) / 64);
+  DISPATCH_H16(dtype,
+               hipLaunchKernelGGL(classifier_ce_bwd_fused_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (bf16_t*)dh, dW, db, B, K, ncls, use_gate, gate_scale, nce),
+               hipLaunchKernelGGL(classifier_ce_bwd_fused_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (f16_t*)dh, dW, db, B, K, ncls, use_gate, gate_scale, nce),
+               "eg_classifier_ce_bwd_fused");
+  EG_LAUNCH_CHECK("classifier_ce_bwd_fused");
+  return 0;
+}
+
+extern "C" int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void* sfT, const void* zf, void* dzf, void* dcomb,
+                                  float* dWc0, float* dbc0, int B, int D, int dtype, void* stream) {
+  EG_CHECK(dhcl && c0T && sfT && zf && dzf && dcomb && dWc0 && dbc0, "eg_heads_bwd_chain: null pointer");
+  EG_CHECK(D == HD, "eg_heads_bwd_chain: d_model=%d (the fused heads are built for 256)", D);
+  EG_CHECK(B > 0 && B <= 256, "eg_heads_bwd_chain: B=%d (the in-launch weight gradients sum at most 256 rows)", B);
+  EG_CHECK(((uintptr_t)dhcl | (uintptr_t)c0T | (uintptr_t)sfT | (uintptr_t)zf | (uintptr_t)dzf | (uintptr_t)dcomb | (uintptr_t)dWc0) % 16 == 0,
+           "eg_heads_bwd_chain: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  const int nrt = (B + 15) / 16;
+  dim3 grid(nrt + (HD / 64) * (HK / 64));
+  DISPATCH_H16(dtype,
+               hipLaunchKernelGGL(heads_bwd_chain_kernel<bf16_t>, grid, dim3(512), 0, s, (const bf16_t*)dhcl, (const bf16_t*)c0T, (const bf16_t*)sfT, (const bf16_t*)zf, (bf16_t*)dzf, (bf16_t*)dcomb, dWc0, dbc0, B, nrt),
+               hipLaunchKernelGGL(heads_bwd_chain_kernel<f16_t>, grid, dim3(512), 0, s, (const f16_t*)dhcl, (const f16_t*)c0T, (const f16_t*)sfT, (const f16_t*)zf, (f16_t*)dzf, (f16_t*)dcomb, dWc0, dbc0, B, nrt),
+               "eg_heads_bwd_chain");
+  EG_LAUNCH_CHECK("heads_bwd_chain");
+  return 0;
+}
+
+extern "C" int eg_heads_bwd_pool(const void* z, const void* dcomb, const void* dzf, const float* gcls1, const float* gcls2,
+                                 const void* dibs_pool, const float* gibs_pool, void* dz, const void* comb, float* dWsf,
+                                 float* dbsf, int B, int S, int D, int off, int n_ibs, int ibs_first, int dtype, void* stream) {
+  EG_CHECK(z && dcomb && dzf && dz && comb && dWsf && dbsf, "eg_heads_bwd_pool: null pointer");
+  EG_CHECK(D == HD, "eg_heads_bwd_pool: d_model=%d (the fused heads are built for 256)", D);
+  EG_CHECK(B > 0 && B <= 256 && off > 0 && off < S, "eg_heads_bwd_pool: bad shape B=%d (<= 256) S=%d off=%d", B, S, off);
+  EG_CHECK(n_ibs == 0 || (ibs_first >= 1 && ibs_first + n_ibs <= S), "eg_heads_bwd_pool: ibs range");
+  EG_CHECK(((uintptr_t)dzf | (uintptr_t)comb | (uintptr_t)dWsf) % 16 == 0, "eg_heads_bwd_pool: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(B + (HD / 64) * (HK / 64));
+  DISPATCH_H16(dtype,
+               hipLaunchKernelGGL(heads_bwd_pool_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)z, (const bf16_t*)dcomb, (const bf16_t*)dzf, gcls1, gcls2, (const bf16_t*)dibs_pool, gibs_pool, (bf16_t*)dz, (const bf16_t*)comb, dWsf, dbsf, B, S, D, off, n_ibs, ibs_first),
+               hipLaunchKernelGGL(heads_bwd_pool_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)z, (const f16_t*)dcomb, (const f16_t*)dzf, gcls1, gcls2, (const f16_t*)dibs_pool, gibs_pool, (f16_t*)dz, (const f16_t*)comb, dWsf, dbsf, B, S, D, off, n_ibs, ibs_first),
+               "eg_heads_bwd_pool");
+  EG_LAUNCH_CHECK("heads_bwd_pool");
   return 0;
 }
 

@@ -115,21 +115,14 @@ __global__ void pack_convT_weight_kernel(const float* __restrict__ w, T* __restr
 // mode 2: like 0 but the destination is fp32 (bias vectors gathered into fused buffers); modes 3-6: eg_ffn_chain's fragment
 // order (16-bit dtypes).  Each block handles one 32x32 tile (mode 1), 1024 elements (modes 0/2) or 2048 elements (modes 3-6);
 // blk0 is the entry's first block.
+// one block of one table entry (modes 0-8); `lb` is the block's index within the entry.  Shared by pack_table_kernel and
+// pack_table_ex_kernel, so both write the same bytes.
+struct PackArgs {
+  uint64_t src, dst;
+  int rows, cols, ldd, mode;
+};
 template <typename T>
-__global__ __launch_bounds__(256) void pack_table_kernel(const eg_pack_entry* __restrict__ tab, int nent) {
-  __shared__ float tile[32][33];
-  __shared__ int ent_s;
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = nent - 1;
-    while (lo < hi) {  // last entry with blk0 <= blockIdx.x
-      const int mid = (lo + hi + 1) >> 1;
-      if (tab[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    ent_s = lo;
-  }
-  __syncthreads();
-  const eg_pack_entry e = tab[ent_s];
-  const int lb = blockIdx.x - e.blk0;
+__device__ __forceinline__ void pack_block(const PackArgs& e, const int lb, float (*tile)[33]) {
   const float* src = (const float*)e.src;
   if (e.mode == 1) {
     const int tiles_c = (e.cols + 31) / 32;
@@ -213,7 +206,164 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const eg_pack_entry* __
   }
 }
 
+// last entry with blk0 <= blockIdx.x (thread 0 searches, everyone reads the answer after the barrier)
+template <typename E>
+__device__ __forceinline__ int pack_find_entry(const E* __restrict__ tab, int nent, int* ent_s) {
+  if (threadIdx.x == 0) {
+    int lo = 0, hi = nent - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (tab[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    *ent_s = lo;
+  }
+  __syncthreads();
+  return *ent_s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pack_table_kernel(const eg_pack_entry* __restrict__ tab, int nent) {
+  __shared__ float tile[32][33];
+  __shared__ int ent_s;
+  const eg_pack_entry e = tab[pack_find_entry(tab, nent, &ent_s)];
+  const PackArgs a = {e.src, e.dst, e.rows, e.cols, e.ldd, e.mode};
+  pack_block<T>(a, blockIdx.x - e.blk0, tile);
+}
+
+// eg_pack_table_ex: the modes above plus the two convolution weight layouts (1024 destination elements per block, four per
+// thread at stride 256 so that a wave's stores stay contiguous):
+//   mode 9  = pack_conv_weight_kernel:  rows = N, cols = Cin, p0 = k, p1 = Cp, p2 = Kp
+//   mode 10 = pack_convT_weight_kernel: rows = N, cols = Cin, p0 = k, p1 = stride, p2 = J
+template <typename T>
+__global__ __launch_bounds__(256) void pack_table_ex_kernel(const eg_pack_entry_ex* __restrict__ tab, int nent) {
+  __shared__ float tile[32][33];
+  __shared__ int ent_s;
+  const eg_pack_entry_ex e = tab[pack_find_entry(tab, nent, &ent_s)];
+  const int lb = blockIdx.x - e.blk0;
+  if (e.mode < 9) {
+    const PackArgs a = {e.src, e.dst, e.rows, e.cols, e.ldd, e.mode};
+    pack_block<T>(a, lb, tile);
+    return;
+  }
+  const float* w = (const float*)e.src;
+  T* dst = (T*)e.dst;
+  const int N = e.rows, Cin = e.cols, k = e.p0;
+  if (e.mode == 9) {
+    const int Cp = e.p1, Kp = e.p2;
+    const long long total = (long long)N * Kp;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = (long long)lb * 1024 + u * 256 + threadIdx.x;
+      if (i >= total) break;
+      const int n = (int)(i / Kp), kk = (int)(i % Kp);
+      const int tap = kk / Cp, c = kk % Cp;
+      const float v = (tap < k && c < Cin) ? w[((size_t)n * Cin + c) * k + tap] : 0.f;
+      Elem<T>::st(dst + i, v);
+    }
+  } else {
+    const int s = e.p1, J = e.p2;
+    const long long per_phase = (long long)Cin * J * N;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = (long long)lb * 1024 + u * 256 + threadIdx.x;
+      if (i >= per_phase * s) break;
+      const int p = (int)(i / per_phase);
+      const long long rem = i % per_phase;
+      const int c = (int)(rem / (J * N));
+      const int jn = (int)(rem % (J * N));
+      const int j = jn / N, n = jn % N;
+      const int tap = s * (J - 1 - j) + p;
+      const float v = tap < k ? w[((size_t)n * Cin + c) * k + tap] : 0.f;
+      Elem<T>::st(dst + i, v);
+    }
+  }
+}
+
 }  // namespace
+
+// Host-side audit of an eg_pack_table_ex table (a HOST copy of it), run when the table is built: block ranges, per-mode shape
+// rules, alignment, and -- wherever the caller states the extents of the buffers behind src / dst -- that no block reads or
+// writes past them.  The convolution modes must state both extents.
+extern "C" int eg_pack_table_ex_check(const eg_pack_entry_ex* table, int nentries, int dtype, int* total_blocks) {
+  EG_CHECK(table && nentries > 0 && total_blocks, "eg_pack_table_ex_check: bad arguments");
+  EG_CHECK(dtype == EG_BF16 || dtype == EG_F16 || dtype == EG_F32, "eg_pack_table_ex_check: bad dtype %d", dtype);
+  long long blk = 0;
+  for (int i = 0; i < nentries; ++i) {
+    const eg_pack_entry_ex& e = table[i];
+    EG_CHECK(e.src && e.dst, "eg_pack_table_ex_check: entry %d: null src / dst", i);
+    EG_CHECK(e.rows > 0 && e.cols > 0, "eg_pack_table_ex_check: entry %d: bad shape rows=%d cols=%d", i, e.rows, e.cols);
+    EG_CHECK(e.mode >= 0 && e.mode <= 10, "eg_pack_table_ex_check: entry %d: unknown mode %d", i, e.mode);
+    EG_CHECK(e.src_elems >= 0 && e.dst_elems >= 0, "eg_pack_table_ex_check: entry %d: negative extent", i);
+    const long long rc = (long long)e.rows * e.cols;
+    long long need_src = rc, need_dst = rc, nblk = 0;
+    unsigned src_al = 4, dst_al = 2;
+    if (e.mode == 0 || e.mode == 2) {
+      nblk = (rc + 1023) / 1024;
+      if (e.mode == 0 && rc >= 4) { src_al = 16; dst_al = dtype == EG_F32 ? 16 : 8; }
+      if (e.mode == 2) dst_al = 4;
+    } else if (e.mode == 1) {
+      EG_CHECK(e.ldd >= e.rows, "eg_pack_table_ex_check: entry %d: transpose ldd=%d < rows=%d", i, e.ldd, e.rows);
+      nblk = (long long)((e.rows + 31) / 32) * ((e.cols + 31) / 32);
+      need_dst = (long long)(e.cols - 1) * e.ldd + e.rows;
+    } else if (e.mode <= 8) {
+      EG_CHECK(dtype != EG_F32, "eg_pack_table_ex_check: entry %d: fragment mode %d needs a 16-bit dtype", i, e.mode);
+      src_al = 16; dst_al = 16;
+      nblk = rc / 2048;
+      if (e.mode == 3 || e.mode == 6)
+        EG_CHECK(e.cols == 256 && e.rows % 128 == 0, "eg_pack_table_ex_check: entry %d: mode %d needs src [F, 256], F %% 128 == 0", i, e.mode);
+      else if (e.mode == 4 || e.mode == 5)
+        EG_CHECK(e.rows == 256 && e.cols % 128 == 0, "eg_pack_table_ex_check: entry %d: mode %d needs src [256, F], F %% 128 == 0", i, e.mode);
+      else {
+        EG_CHECK(e.rows == 256 && e.cols == 256, "eg_pack_table_ex_check: entry %d: mode %d needs src [256, 256]", i, e.mode);
+        if (e.mode == 7) {
+          EG_CHECK(e.ldd >= 0 && e.ldd <= 2, "eg_pack_table_ex_check: entry %d: mode 7 part %d not in 0..2", i, e.ldd);
+          need_dst = 3 * rc;      // the shared q|k|v image
+        }
+      }
+    } else {
+      const int N = e.rows, Cin = e.cols, k = e.p0;
+      EG_CHECK(k > 0, "eg_pack_table_ex_check: entry %d: kernel size %d", i, k);
+      EG_CHECK(e.src_elems > 0 && e.dst_elems > 0, "eg_pack_table_ex_check: entry %d: mode %d must state src_elems and dst_elems", i, e.mode);
+      need_src = (long long)N * Cin * k;
+      if (e.mode == 9) {
+        const int Cp = e.p1, Kp = e.p2;
+        EG_CHECK(Cp >= Cin && Kp >= (long long)k * Cp, "eg_pack_table_ex_check: entry %d: Cp=%d Kp=%d too small", i, Cp, Kp);
+        need_dst = (long long)N * Kp;
+      } else {
+        const int s = e.p1, J = e.p2;
+        EG_CHECK(s > 0 && J == (k + s - 1) / s, "eg_pack_table_ex_check: entry %d: stride=%d J=%d do not match k=%d", i, s, J, k);
+        need_dst = (long long)s * Cin * J * N;
+      }
+      EG_CHECK(need_dst < (1ll << 31), "eg_pack_table_ex_check: entry %d: %lld destination elements", i, need_dst);
+      nblk = (need_dst + 1023) / 1024;
+    }
+    EG_CHECK(nblk > 0 && e.nblk == nblk, "eg_pack_table_ex_check: entry %d: nblk=%d, mode %d at this shape takes %lld", i, e.nblk, e.mode, nblk);
+    EG_CHECK(e.blk0 == blk, "eg_pack_table_ex_check: entry %d: blk0=%d, expected %lld", i, e.blk0, blk);
+    EG_CHECK(e.src % src_al == 0 && e.dst % dst_al == 0, "eg_pack_table_ex_check: entry %d: alignment (mode %d)", i, e.mode);
+    EG_CHECK(e.src_elems == 0 || need_src <= e.src_elems, "eg_pack_table_ex_check: entry %d: reads %lld elements of a %lld-element source",
+             i, need_src, (long long)e.src_elems);
+    EG_CHECK(e.dst_elems == 0 || need_dst <= e.dst_elems, "eg_pack_table_ex_check: entry %d: writes %lld elements of a %lld-element destination",
+             i, need_dst, (long long)e.dst_elems);
+    blk += nblk;
+    EG_CHECK(blk < (1ll << 31), "eg_pack_table_ex_check: too many blocks");
+  }
+  *total_blocks = (int)blk;
+  return 0;
+}
+
+extern "C" int eg_pack_table_ex(const eg_pack_entry_ex* table, int nentries, int total_blocks, int dtype, void* stream) {
+  EG_CHECK(table && nentries > 0 && total_blocks > 0, "eg_pack_table_ex: bad arguments");
+  if (dtype == EG_BF16)
+    hipLaunchKernelGGL(pack_table_ex_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
+  else if (dtype == EG_F16)
+    hipLaunchKernelGGL(pack_table_ex_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
+  else if (dtype == EG_F32)
+    hipLaunchKernelGGL(pack_table_ex_kernel<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
+  else
+    return eg_fail("eg_pack_table_ex: bad dtype %d", dtype);
+  EG_LAUNCH_CHECK("pack_table_ex");
+  return 0;
+}
 
 extern "C" int eg_pack_table(const eg_pack_entry* table, int nentries, int total_blocks, int dtype, void* stream) {
   EG_CHECK(table && nentries > 0 && total_blocks > 0, "eg_pack_table: bad arguments");

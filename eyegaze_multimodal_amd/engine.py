@@ -206,6 +206,12 @@ class Engine:
         # two launches (the gain / bias partials are grouped by tile instead of by LayerNorm block: equal to fp32 rounding)
         self.ln_proj = (dtype != EG_F32 and cfg.d_model == 256 and os.environ.get("EYEGAZE_LN_PROJ", "1") != "0")
         self.ln_proj_blocks = L.lib().eg_ln_bwd_proj_blocks(self.M) if self.ln_proj else 0
+        # the step's small-launch tail on its fused kernels (16-bit compute dtypes): the convolution weight layouts inside the
+        # one table-driven pack launch, the heads' forward as pooling + ONE chained launch, their backward as three, and the
+        # position / cls / conv-1 gradient rows from ONE pass over dseq.  Same bits as the separate launches, which remain the
+        # route for fp32 and for the shapes the fused kernels do not cover (see _fused_heads); tests set this attribute to
+        # False to compare the two routes.
+        self.fused_tail = dtype != EG_F32
         self._alloc()
         self.packed_version = -1
         self._recording = False
@@ -287,6 +293,7 @@ class Engine:
         a["logits"] = self._t(B, cfg.num_classes, dtype=f32)
         a["sloss"] = self._t(B, dtype=f32)
         a["loss"] = self._t(1, dtype=f32)
+        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)   # eg_heads_fwd's last-workgroup counter
         if cfg.use_ibs:
             a["ibs_pool_f"] = self._t(B, d, dtype=f32)
             a["ibs_pool"] = self._t(B, d)
@@ -771,33 +778,76 @@ class Engine:
         if self._recording:
             self._plan.append((src, dst, R, Cc, part, mode))
 
+    def p_conv(self, src, dst, N, Cin, k, Cp, Kp):
+        """eg_pack_conv_weight as an entry of the pack table (fused route) or as its own launch"""
+        if self._plan_ex:
+            if self._recording:
+                self._plan.append((src, dst, N, Cin, 0, 9, k, Cp, Kp))
+        else:
+            call("eg_pack_conv_weight", src, dst, N, Cin, k, Cp, Kp, self.dtype, self.stream)
+
+    def p_convT(self, src, dst, N, Cin, k, s):
+        """eg_pack_convT_weight, likewise"""
+        if self._plan_ex:
+            if self._recording:
+                self._plan.append((src, dst, N, Cin, 0, 10, k, s, (k + s - 1) // s))
+        else:
+            call("eg_pack_convT_weight", src, dst, N, Cin, k, s, self.dtype, self.stream)
+
+    def _extent_after(self, addr: int, elsize: int) -> int:
+        """elements of size `elsize` between `addr` and the end of the engine / parameter buffer that holds it (0: not found)"""
+        bufs = list(self.w.values()) + [self.fp.flat]
+        for t in bufs:
+            lo = t.data_ptr()
+            hi = lo + t.numel() * t.element_size()
+            if lo <= addr < hi:
+                return (hi - addr) // elsize
+        return 0
+
     def pack_params(self):
-        key = (self.fp.flat.data_ptr(), self.stream)
-        if getattr(self, "_plan_key", None) != key[0]:
+        ex = bool(getattr(self, "fused_tail", False))       # (the image engine shares this method and keeps eg_pack_table)
+        key = (self.fp.flat.data_ptr(), ex)
+        self._plan_ex = ex
+        if getattr(self, "_plan_key", None) != key:
             self._plan, self._recording = [], True
             self._pack_body()
             self._recording = False
-            ents = (L.PackEntry * len(self._plan))()
+            ents = ((L.PackEntryEx if ex else L.PackEntry) * len(self._plan))()
             blk = 0
-            for e, (src, dst, R, Cc, ldd, mode) in zip(ents, self._plan):
-                nb = (((R + 31) // 32) * ((Cc + 31) // 32) if mode == 1 else (R * Cc) // 2048 if mode >= 3 else
-                      (R * Cc + 1023) // 1024)
+            for e, ent in zip(ents, self._plan):
+                src, dst, R, Cc, ldd, mode = ent[:6]
+                if mode == 9:
+                    nb = (R * ent[8] + 1023) // 1024
+                elif mode == 10:
+                    nb = (ent[7] * Cc * ent[8] * R + 1023) // 1024
+                else:
+                    nb = (((R + 31) // 32) * ((Cc + 31) // 32) if mode == 1 else (R * Cc) // 2048 if mode >= 3 else
+                          (R * Cc + 1023) // 1024)
                 e.src, e.dst, e.rows, e.cols, e.ldd, e.mode, e.blk0, e.nblk = src, dst, R, Cc, ldd, mode, blk, nb
+                if ex:
+                    if mode >= 9:
+                        e.p0, e.p1, e.p2 = ent[6:9]
+                    e.src_elems = self._extent_after(src, 4)
+                    e.dst_elems = self._extent_after(dst, 4 if mode == 2 else self.es)
                 blk += nb
+            if ex:      # host-side audit of every entry (block ranges, shapes, alignment, extents) before the table is ever launched
+                total = C.c_int(0)
+                call("eg_pack_table_ex_check", C.cast(ents, C.c_void_p), len(self._plan), self.dtype, C.byref(total))
+                if total.value != blk:
+                    raise L.EgError(f"pack table: {total.value} blocks audited, {blk} planned")
             raw = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8)
             self._plan_dev = raw.to(self.device)
-            self._plan_n, self._plan_blocks, self._plan_key = len(self._plan), blk, key[0]
+            self._plan_n, self._plan_blocks, self._plan_key = len(self._plan), blk, key
         else:
             self._pack_body()
-        call("eg_pack_table", ptr(self._plan_dev), self._plan_n, self._plan_blocks, self.dtype, self.stream)
+        call("eg_pack_table_ex" if ex else "eg_pack_table", ptr(self._plan_dev), self._plan_n, self._plan_blocks, self.dtype,
+             self.stream)
 
     def _pack_body(self):
         cfg, d, F, fp, w, dt, st = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.fp, self.w, self.dtype, self.stream
-        call("eg_pack_conv_weight", fp.p_ptr("temporal_conv.convs.0.weight"), ptr(w["conv0"]), d, self.C, self.k, self.Cp,
-             self.K0, dt, st)
-        call("eg_pack_conv_weight", fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1"]), d, d, self.k, d, self.k * d,
-             dt, st)
-        call("eg_pack_convT_weight", fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1T"]), d, d, self.k, self.s, dt, st)
+        self.p_conv(fp.p_ptr("temporal_conv.convs.0.weight"), ptr(w["conv0"]), d, self.C, self.k, self.Cp, self.K0)
+        self.p_conv(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1"]), d, d, self.k, d, self.k * d)
+        self.p_convT(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1T"]), d, d, self.k, self.s)
         self.p_cast(fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["pos"]), cfg.max_len * d)
 
         def attn_pack(pre, l):
@@ -916,13 +966,19 @@ class Engine:
         # heads (D:1193-1213)
         call("eg_pool_fuse_fwd", ptr(z), ptr(a["cls1"]), ptr(a["cls2"]), ptr(a["comb"]), ptr(a["zf"]),
              ptr(a.get("ibs_pool_f")), ptr(a.get("ibs_pool")), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
-        self.gemm(ptr(a["comb"]), ptr(w["sf"]), ptr(a["zf"]), B, d, 3 * d, c=rowmap(3 * d),
-                  bias=fp.p_ptr("symmetric_fusion.proj.bias"))
-        self.gemm(ptr(a["zf"]), ptr(w["c0"]), ptr(a["hcl"]), B, d, 3 * d, bias=fp.p_ptr("classifier.0.bias"),
-                  act=L.ACT_RELU, drop1=(p, SITE_CLS))
         lab = ptr(labels) if labels is not None else 0
-        call("eg_classifier_ce_fwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
-             ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), B, d, cfg.num_classes, self.dtype, st)
+        if self._fused_heads():     # both products, the class projection, the per-sample CE and its mean: one launch
+            call("eg_heads_fwd", ptr(a["comb"]), ptr(a["zf"]), ptr(a["hcl"]), ptr(w["sf"]), fp.p_ptr("symmetric_fusion.proj.bias"),
+                 ptr(w["c0"]), fp.p_ptr("classifier.0.bias"), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
+                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), ptr(a["heads_ctr"]), B, d, cfg.num_classes, p, SITE_CLS,
+                 self.st_ptr, self.dtype, st)
+        else:
+            self.gemm(ptr(a["comb"]), ptr(w["sf"]), ptr(a["zf"]), B, d, 3 * d, c=rowmap(3 * d),
+                      bias=fp.p_ptr("symmetric_fusion.proj.bias"))
+            self.gemm(ptr(a["zf"]), ptr(w["c0"]), ptr(a["hcl"]), B, d, 3 * d, bias=fp.p_ptr("classifier.0.bias"),
+                      act=L.ACT_RELU, drop1=(p, SITE_CLS))
+            call("eg_classifier_ce_fwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
+                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), B, d, cfg.num_classes, self.dtype, st)
         if cfg.use_ibs:
             p3 = 0.3 if train else 0.0
             self.gemm(ptr(a["ibs_pool"]), ptr(w["i0"]), ptr(a["hib"]), B, d // 2, d, bias=fp.p_ptr("ibs_classifier.0.bias"),
@@ -930,6 +986,17 @@ class Engine:
             call("eg_classifier_ce_fwd", ptr(a["hib"]), fp.p_ptr("ibs_classifier.3.weight"), fp.p_ptr("ibs_classifier.3.bias"),
                  lab, ptr(a["ibs_logits"]), ptr(a["ibs_sloss"]), ptr(a["ibs_loss"]), B, d // 2, cfg.num_classes, self.dtype, st)
         self.labels = labels
+
+    def _fused_heads(self, backward: bool = False) -> bool:
+        """the fused head kernels cover 16-bit compute dtypes at d_model == 256 with at most 16 classes; their in-launch weight
+        gradients (backward) sum at most 256 samples, and need classifier.0 / symmetric_fusion.proj each laid out as weight then
+        bias in the flat gradient buffer (as eg_gemm_tn's fused-bias reduce does)"""
+        ok = bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model == 256 and self.cfg.num_classes <= 16
+        if ok and backward:
+            o, d = self.fp.offsets, self.cfg.d_model
+            ok = self.B <= 256 and all(o[n + ".bias"] == o[n + ".weight"] + 3 * d * d
+                                       for n in ("classifier.0", "symmetric_fusion.proj"))
+        return ok
 
     # ------------------------------------------------------------------------------------------
     # backward.  g* arguments are optional fp32 device tensors (gradients of the module's outputs);
@@ -956,13 +1023,23 @@ class Engine:
             gloss, gloss_ibs, glogits, gcls1, gcls2 = sc_(gloss), sc_(gloss_ibs), sc_(glogits), sc_(gcls1), sc_(gcls2)
             gibs_logits, gibs_token = sc_(gibs_logits), sc_(gibs_token)
         # ---- heads ----
-        call("eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), ptr(a["logits"]), lab, ptr(gloss),
-             ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"), fp.g_ptr("classifier.3.bias"),
-             B, d, cfg.num_classes, 1, sc, self.dtype, st)
-        self.gemm(ptr(g["dhcl"]), ptr(w["c0T"]), ptr(g["dzf"]), B, 3 * d, d)
-        self.wgrad(ptr(g["dhcl"]), ptr(a["zf"]), 0, B, d, 3 * d, linear=["classifier.0"])
-        self.gemm(ptr(g["dzf"]), ptr(w["sfT"]), ptr(g["dcomb"]), B, 3 * d, d, a=rowmap(3 * d))
-        self.wgrad(ptr(g["dzf"]), ptr(a["comb"]), 0, B, d, 3 * d, y=rowmap(3 * d), linear=["symmetric_fusion.proj"])
+        fused_heads = self._fused_heads(backward=True)
+        if fused_heads:
+            # launch 1: CE backward rows + classifier.3's gradients; launch 2: both backward-data products chained per 16
+            # samples + classifier.0's gradients; (launch 3, below: pool backward + symmetric_fusion.proj's gradients)
+            call("eg_classifier_ce_bwd_fused", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), ptr(a["logits"]), lab, ptr(gloss),
+                 ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
+                 fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
+            call("eg_heads_bwd_chain", ptr(g["dhcl"]), ptr(w["c0T"]), ptr(w["sfT"]), ptr(a["zf"]), ptr(g["dzf"]), ptr(g["dcomb"]),
+                 fp.g_ptr("classifier.0.weight"), fp.g_ptr("classifier.0.bias"), B, d, self.dtype, st)
+        else:
+            call("eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), ptr(a["logits"]), lab, ptr(gloss),
+                 ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
+                 fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
+            self.gemm(ptr(g["dhcl"]), ptr(w["c0T"]), ptr(g["dzf"]), B, 3 * d, d)
+            self.wgrad(ptr(g["dhcl"]), ptr(a["zf"]), 0, B, d, 3 * d, linear=["classifier.0"])
+            self.gemm(ptr(g["dzf"]), ptr(w["sfT"]), ptr(g["dcomb"]), B, 3 * d, d, a=rowmap(3 * d))
+            self.wgrad(ptr(g["dzf"]), ptr(a["comb"]), 0, B, d, 3 * d, y=rowmap(3 * d), linear=["symmetric_fusion.proj"])
         dibs = None
         if cfg.use_ibs:
             sc3 = 1.0 / 0.7 if train else 1.0
@@ -977,8 +1054,13 @@ class Engine:
             dibs = g["dibs_pool"]
         z = self.z_final
         dz = g["dzA"]
-        call("eg_pool_fuse_bwd", ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gcls1), ptr(gcls2), ptr(dibs), ptr(gibs_token),
-             ptr(dz), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
+        if fused_heads:
+            call("eg_heads_bwd_pool", ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gcls1), ptr(gcls2), ptr(dibs), ptr(gibs_token),
+                 ptr(dz), ptr(a["comb"]), fp.g_ptr("symmetric_fusion.proj.weight"), fp.g_ptr("symmetric_fusion.proj.bias"),
+                 B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
+        else:
+            call("eg_pool_fuse_bwd", ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gcls1), ptr(gcls2), ptr(dibs), ptr(gibs_token),
+                 ptr(dz), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
         seg("heads")
         Lr = cfg.num_layers
         other = g["dzB"]
@@ -1090,14 +1172,20 @@ class Engine:
                     seg(f"layer{l}")
         dseq = dz
         # positional table / cls token (A:120-126, D:1157)
-        call("eg_batch_rowsum", ptr(dseq), fp.g_ptr("pos_embed.pos_embed.weight"), NB, S, d, S, self.dtype, st)
-        call("eg_cast", fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), d, EG_F32, st)
-        self.model._extra_tokens_bwd(self, dseq)
-        seg("tokens")           # positions, token generators, the extra heads: everything registered between conv-1 and the encoder
         # conv1 backward: dY = dseq[:, off:, :] * relu/dropout gate
         ymap = rowmap(d, self.RY * d, self.T2)
-        call("eg_rows_gather_gate", ptr(dseq), ptr(a["h1"]), ptr(g["dy1pad"]) + (self.J - 1) * d * es, ymap, NB, S, d,
-             self.T2, self.off, 0, sc01, self.dtype, st)
+        fused_tokens = bool(self.fused_tail) and self.dtype != EG_F32 and d % 64 == 0
+        if fused_tokens:        # ONE pass over dseq: position sums, the cls_token copy and conv-1's gated dY rows
+            call("eg_token_grad_tail", ptr(dseq), ptr(a["h1"]), ptr(g["dy1pad"]) + (self.J - 1) * d * es, ymap,
+                 fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), NB, S, d, self.T2, self.off, sc01, self.dtype, st)
+        else:
+            call("eg_batch_rowsum", ptr(dseq), fp.g_ptr("pos_embed.pos_embed.weight"), NB, S, d, S, self.dtype, st)
+            call("eg_cast", fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), d, EG_F32, st)
+        self.model._extra_tokens_bwd(self, dseq)
+        seg("tokens")           # positions, token generators, the extra heads: everything registered between conv-1 and the encoder
+        if not fused_tokens:
+            call("eg_rows_gather_gate", ptr(dseq), ptr(a["h1"]), ptr(g["dy1pad"]) + (self.J - 1) * d * es, ymap, NB, S, d,
+                 self.T2, self.off, 0, sc01, self.dtype, st)
         dy1 = ptr(g["dy1pad"]) + (self.J - 1) * d * es
         self.wgrad(dy1, ptr(a["h0pad"]), fp.g_ptr("temporal_conv.convs.1.weight"), NB * self.T2, d, self.k * d, y=ymap,
                    x=rowmap(self.s * d, self.R0 * d, self.T2), out_b=fp.g_ptr("temporal_conv.convs.1.bias"),

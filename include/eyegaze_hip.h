@@ -111,6 +111,22 @@ typedef struct eg_pack_entry {
   int32_t rows, cols, ldd, mode, blk0, nblk;
 } eg_pack_entry;
 int eg_pack_table(const eg_pack_entry* table, int nentries, int total_blocks, int dtype, void* stream);
+/* eg_pack_table_ex: eg_pack_table's modes 0-8 (same bytes) plus the two convolution weight layouts, so that ONE launch stages
+ * every weight of a step:
+ *   mode 9  = eg_pack_conv_weight:  rows = N, cols = Cin, p0 = k, p1 = Cp, p2 = Kp       (N * Kp destination elements)
+ *   mode 10 = eg_pack_convT_weight: rows = N, cols = Cin, p0 = k, p1 = stride, p2 = J    (stride * Cin * J * N elements)
+ * both at 1024 destination elements per block.  src_elems / dst_elems are the extents (fp32 source elements, destination
+ * elements) of the buffers behind src / dst from those addresses on, 0 = not stated (modes 9 / 10 must state both).
+ * eg_pack_table_ex_check audits a HOST copy of the table when it is built -- block ranges, per-mode shape rules, alignment and
+ * the stated extents -- and returns the launch's block count; eg_pack_table_ex launches the DEVICE copy. */
+typedef struct eg_pack_entry_ex {
+  uint64_t src, dst;
+  int32_t rows, cols, ldd, mode, blk0, nblk;
+  int32_t p0, p1, p2, p3;
+  int64_t src_elems, dst_elems;
+} eg_pack_entry_ex;
+int eg_pack_table_ex_check(const eg_pack_entry_ex* table, int nentries, int dtype, int* total_blocks);
+int eg_pack_table_ex(const eg_pack_entry_ex* table, int nentries, int total_blocks, int dtype, void* stream);
 int eg_cast(const float* src, void* dst, int64_t n, int dtype, void* stream);
 int eg_transpose_cast(const float* src, void* dst, int R, int Cc, int ldd, int dtype, void* stream);
 int eg_pack_conv_weight(const float* w, void* dst, int N, int Cin, int k, int Cp, int Kp, int dtype, void* stream);
@@ -377,6 +393,36 @@ int eg_classifier_ce_bwd(const void* h, const float* W, const float* logits, con
 int eg_batch_rowsum(const void* dseq, float* out, int NB, int S, int D, int rows, int dtype, void* stream);
 int eg_rows_gather_gate(const void* src, const void* gate, void* dst, eg_rowmap dmap, int nb, int S, int D, int R,
                         int off, int pair_shift, float gate_scale, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused forms of the launches above for the training step's tail (bf16 / fp16, d_model == 256).  Each gives the bits of the
+ * launches it replaces: same MFMA shape and K order as eg_gemm_nt / eg_gemm_tn, same rounding points, same summation trees.
+ *   eg_heads_fwd       after eg_pool_fuse_fwd: zf[:, :256] = comb Wsf^T + bsf; hcl = dropout(relu(zf Wc0^T + bc0)) (site
+ *                      drop_site, the state's seed); logits = hcl W3^T + b3; with labels the per-sample CE and its mean.
+ *                      Wsf / Wc0 [256, 768] in the compute dtype, W3 [ncls, 256] fp32.  `counter` is one zero-initialised
+ *                      device word the launch uses to find its last workgroup (left at zero again).
+ *   eg_classifier_ce_bwd_fused  eg_classifier_ce_bwd (rows and the last Linear's weight / bias gradient) in one launch; B <= 256
+ *   eg_heads_bwd_chain dzf [B, 768] = dhcl c0T^T, dcomb [B, 768] = dzf[:, :256] sfT^T (c0T / sfT [768, 256]) and
+ *                      dWc0 [256, 768] = dhcl^T zf, dbc0 = colsum(dhcl), summed in-launch; B <= 256
+ *   eg_heads_bwd_pool  eg_pool_fuse_bwd plus dWsf [256, 768] = dzf[:, :256]^T comb, dbsf = colsum(dzf[:, :256]); B <= 256
+ *   eg_token_grad_tail ONE pass over dseq [NB, S, D]: pos_grad[s, :] = sum_b dseq[b, s, :] (eg_batch_rowsum's order), cls_grad =
+ *                      pos_grad row 0 (may be NULL), and eg_rows_gather_gate's rows dst[b, r, :] = dseq[b, off + r, :] gated by
+ *                      gate[b, r, :] > 0.  D % 64 == 0.
+ * ------------------------------------------------------------------------------------------- */
+int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* Wsf, const float* bsf, const void* Wc0, const float* bc0,
+                 const float* W3, const float* b3, const int64_t* labels, float* logits, float* sample_loss, float* loss,
+                 uint32_t* counter, int B, int D, int ncls, float drop_p, uint32_t drop_site, const eg_step_state* state,
+                 int dtype, void* stream);
+int eg_classifier_ce_bwd_fused(const void* h, const float* W, const float* logits, const int64_t* labels, const float* gloss,
+                               const float* glogits, float* dlogits, void* dh, float* dW, float* db, int B, int K, int ncls,
+                               int use_gate, float gate_scale, int dtype, void* stream);
+int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void* sfT, const void* zf, void* dzf, void* dcomb, float* dWc0,
+                       float* dbc0, int B, int D, int dtype, void* stream);
+int eg_heads_bwd_pool(const void* z, const void* dcomb, const void* dzf, const float* gcls1, const float* gcls2,
+                      const void* dibs_pool, const float* gibs_pool, void* dz, const void* comb, float* dWsf, float* dbsf, int B,
+                      int S, int D, int off, int n_ibs, int ibs_first, int dtype, void* stream);
+int eg_token_grad_tail(const void* dseq, const void* gate, void* dst, eg_rowmap dmap, float* pos_grad, float* cls_grad, int NB,
+                       int S, int D, int R, int off, float gate_scale, int dtype, void* stream);
 
 /* Batch-level auxiliary losses (3_Models/backbones/dual_eeg_transformer.py:1255-1371), fp32, each with the gradient of the
  * loss w.r.t. the [B, D] tokens it reads (upstream gradient 1; the caller scales).  B <= 1024.
