@@ -112,6 +112,36 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// Gradient accumulation over micro-batches: acc = first ? g : acc + g on a range of the flat buffers, one IEEE fp32 addition per
+// element (nothing for the compiler to contract), so the sum equals torch.add bit for bit and inf / NaN travel on to eg_clip_coef.
+// Streaming, 12 B/element (8 when FIRST: acc is not read, stale contents cannot leak): one f32x4 per lane and trip, two trips in
+// flight, grid-stride over a grid the host sizes from the CU count.  NORM adds eg_grad_sqnorm's partials of the new acc to the same
+// pass: block b writes sq_partial[b], block 0 clears the entries beyond the grid.
+template <bool FIRST, bool NORM>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long long n4,
+                                                              float* __restrict__ sq_partial, int nblk) {
+  f32x4* __restrict__ a4 = (f32x4*)acc;
+  const f32x4* __restrict__ g4 = (const f32x4*)g;
+  const long long stride = (long long)gridDim.x * 256;
+  float s = 0.f;
+#pragma unroll 2
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 v = g4[i];
+    if (!FIRST) v = a4[i] + v;
+    a4[i] = v;
+    if (NORM) s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  }
+  if (NORM) {
+    __shared__ float red[4];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) sq_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    if (blockIdx.x == 0)
+      for (int b = (int)gridDim.x + threadIdx.x; b < nblk; b += 256) sq_partial[b] = 0.f;
+  }
+}
+
 __global__ void fill_kernel(float* __restrict__ p, long long n, float val) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = val;
@@ -124,6 +154,36 @@ extern "C" int eg_grad_sqnorm(const float* g, int64_t n, float* partial, int nbl
   EG_CHECK((uintptr_t)g % 16 == 0, "eg_grad_sqnorm: alignment");
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, g, (long long)n, partial);
   EG_LAUNCH_CHECK("grad_sqnorm");
+  return 0;
+}
+
+extern "C" int eg_grad_accumulate(float* acc, const float* g, int64_t n, int first, float* sq_partial, int nblk, void* stream) {
+  EG_CHECK(acc && g && n > 0 && n % 4 == 0, "eg_grad_accumulate: bad arguments (acc=%p g=%p n=%lld: n must be a positive multiple of 4)",
+           (void*)acc, (const void*)g, (long long)n);
+  EG_CHECK(((uintptr_t)acc | (uintptr_t)g) % 16 == 0, "eg_grad_accumulate: alignment (acc and g must be 16-B aligned)");
+  EG_CHECK(!sq_partial || (nblk >= 1 && nblk <= 1024), "eg_grad_accumulate: bad arguments (nblk=%d outside [1, 1024])", nblk);
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    const bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
+    cus = ok && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  // memory-bound: 8 blocks (32 waves) per CU cover the chip, the grid-stride loop takes the rest; the norm partials allow at
+  // most one block per entry
+  const long long n4 = n / 4;
+  long long grid = std::min<long long>((n4 + 255) / 256, 8ll * cus);
+  if (sq_partial) grid = std::min<long long>(grid, nblk);
+  const dim3 gd((unsigned)grid), bd(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (sq_partial) {
+    if (first) hipLaunchKernelGGL((grad_accumulate_kernel<true, true>), gd, bd, 0, s, acc, g, n4, sq_partial, nblk);
+    else hipLaunchKernelGGL((grad_accumulate_kernel<false, true>), gd, bd, 0, s, acc, g, n4, sq_partial, nblk);
+  } else {
+    if (first) hipLaunchKernelGGL((grad_accumulate_kernel<true, false>), gd, bd, 0, s, acc, g, n4, sq_partial, nblk);
+    else hipLaunchKernelGGL((grad_accumulate_kernel<false, false>), gd, bd, 0, s, acc, g, n4, sq_partial, nblk);
+  }
+  EG_LAUNCH_CHECK("grad_accumulate");
   return 0;
 }
 

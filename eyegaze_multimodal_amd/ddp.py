@@ -104,6 +104,21 @@ class GradAllReducer:
         else:
             self.works.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
+    def reduce_all(self):
+        """The whole buffer as ONE collective behind everything queued so far: no overlap (a flushed, short accumulation
+        group has no backward left to hide it under).  finish() as usual afterwards."""
+        if self.world == 1 and not self.force:
+            return
+        self.collectives += 1
+        if self.cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.g.device))
+            self.comm_stream.wait_event(ev)
+            with torch.cuda.stream(self.comm_stream):
+                self.works.append(dist.all_reduce(self.g, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        else:
+            self.works.append(dist.all_reduce(self.g, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+
     def finish(self):
         """Makes the compute stream wait for every bucket (no host sync on GPU)."""
         for w in self.works:
@@ -115,6 +130,72 @@ class GradAllReducer:
     @property
     def grad_scale(self) -> float:
         return 1.0 / self.world
+
+
+class AccumulatingReducer:
+    """Gradient accumulation under data parallelism: k micro-batches per rank, ONE exchange per optimiser step.
+
+    Every micro-batch's backward fills the flat gradient buffer; the ranks sum them into their accumulators locally and only the
+    accumulator is ever reduced, so a group of k micro-steps issues exactly the collectives of one plain step:
+      * micro-steps 1 .. k-1: accumulate() after backward -- no collective;
+      * micro-step k of a full group: final_hook(first) is backward's on_segment.  As each bucket is released it is added into
+        the accumulator and that range of the ACCUMULATOR goes to the reducer, which was built over the accumulator with the
+        gradient buffer's ranges, groups and side stream: the overlap with the rest of the backward is the plain step's;
+      * a short group (flush at the end of an epoch): flush() reduces the whole accumulator at once, no overlap.
+    finish(), then the optimiser steps on the accumulator with grad_scale(n) = 1 / (n micro-steps x world).  Each rank's
+    squared-norm partials cover its own sum only, so the norm is taken from the reduced accumulator (eg_grad_sqnorm).
+
+    accumulate_fn(first, segment_or_None) adds device buffers (Engine.accumulate: eg_grad_accumulate); host tensors (the gloo
+    rehearsal) take a torch add instead, as GradAllReducer branches on `cuda` for its streams."""
+
+    def __init__(self, flat_grad: torch.Tensor, accumulator: torch.Tensor, ranges: Dict[str, Tuple[int, int]],
+                 accumulate_fn=None, group=None, force: bool = False, comm_stream=None,
+                 groups: Optional[List[List[str]]] = None):
+        if accumulator.shape != flat_grad.shape or accumulator.device != flat_grad.device:
+            raise ValueError("the accumulator must match the flat gradient buffer")
+        if flat_grad.is_cuda and accumulate_fn is None:
+            raise ValueError("device buffers accumulate through Engine.accumulate: pass accumulate_fn")
+        self.grad, self.acc, self.ranges = flat_grad, accumulator, ranges
+        self.reducer = GradAllReducer(accumulator, ranges, group, force, comm_stream, groups)
+        self._fn = accumulate_fn
+        self.world, self.cuda = self.reducer.world, flat_grad.is_cuda
+
+    def _add(self, first: bool, segment: Optional[str]):
+        if self.cuda:
+            self._fn(first, segment)
+            return
+        b, e = (0, self.grad.numel()) if segment is None else self.ranges[segment]
+        if first:
+            self.acc[b:e].copy_(self.grad[b:e])
+        else:
+            self.acc[b:e].add_(self.grad[b:e])
+
+    def accumulate(self, first: bool):
+        """A micro-step that does not end its group: the whole buffer, no collective."""
+        self._add(first, None)
+
+    def final_hook(self, first: bool):
+        """on_segment of the LAST micro-step of a full group."""
+        def hook(name: str):
+            if name not in self.ranges:
+                return
+            self._add(first, name)
+            self.reducer.on_segment(name)
+        return hook
+
+    def flush(self):
+        """Exchange of a group that ended early: everything accumulated so far, one collective."""
+        self.reducer.reduce_all()
+
+    def finish(self):
+        self.reducer.finish()
+
+    @property
+    def collectives(self) -> int:
+        return self.reducer.collectives
+
+    def grad_scale(self, micro_steps: int) -> float:
+        return 1.0 / (micro_steps * self.world)
 
 
 class MultimodalReducers:

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -92,6 +92,7 @@ class FlatParams:
         self.total = off
         self.flat: Optional[torch.Tensor] = None
         self.grad: Optional[torch.Tensor] = None
+        self.acc: Optional[torch.Tensor] = None      # gradient accumulator over micro-batches (accumulator(): made on first use)
 
     def ensure(self, device: torch.device):
         """(Re)flattens when the module was moved / re-created since the last call."""
@@ -111,6 +112,14 @@ class FlatParams:
             p.data = flat[o:o + p.numel()].view(p.shape)
         self.flat = flat
         self.grad = torch.zeros(self.total, device=device, dtype=torch.float32)
+        self.acc = None                # belongs to the buffers it was made beside: re-made on the next accumulator()
+
+    def accumulator(self) -> torch.Tensor:
+        """fp32 buffer of the gradient buffer's length and device that Engine.accumulate sums micro-batch gradients into.  It
+        exists only once gradient accumulation is used, and never outlives a re-flatten."""
+        if self.acc is None:
+            self.acc = torch.zeros_like(self.grad)
+        return self.acc
 
     def p_ptr(self, name: str) -> int:
         return self.flat.data_ptr() + 4 * self.offsets[name]
@@ -129,6 +138,7 @@ class FlatParams:
 class Engine:
     """Workspace + kernel sequencing for a fixed (B, T) shape."""
     LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
+    SQ_BLOCKS = 1024              # squared-norm partials of the flat gradient buffer (g["sqpart"]) that eg_clip_coef sums
 
     def __init__(self, model, B: int, T: int, device: torch.device, dtype: int, state_dev: Optional[torch.Tensor] = None):
         """state_dev: the model's shared eg_step_state.  Every engine of one model (one per batch shape: the ragged tail batch
@@ -216,6 +226,7 @@ class Engine:
         self.packed_version = -1
         self._recording = False
         self._plan = []
+        self._acc_norm_ready = False   # g["sqpart"] holds the norm partials of the whole accumulator (accumulate(norm=True))
 
     # ------------------------------------------------------------------------------------------
     def _t(self, *shape, dtype=None):
@@ -370,6 +381,7 @@ class Engine:
         nblk = 1024
         if "sqpart" not in self.g:
             self.g["sqpart"] = self._t(nblk, dtype=torch.float32)
+        self._acc_norm_ready = False
         call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
         call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, 0.0, self.st_ptr, self.stream)
         c = self.scaler_cfg
@@ -1202,18 +1214,71 @@ class Engine:
         seg("frontend")
 
     # ------------------------------------------------------------------------------------------
+    # gradient accumulation: one optimiser step from several micro-batches (no reference counterpart: T is one batch per step)
+    # ------------------------------------------------------------------------------------------
+    def bucket_ranges(self) -> Dict[str, Tuple[int, int]]:
+        """ddp.bucket_ranges of this model: segment name (as backward's on_segment emits it) -> [begin, end) in floats."""
+        key = self.fp.grad.data_ptr()
+        if getattr(self, "_ranges_key", None) != key:
+            from .ddp import bucket_ranges
+            fp = self.fp
+            self._ranges = bucket_ranges(fp.names, fp.offsets, fp.total, self.cfg.num_layers, self.cfg.use_cross_attention)
+            self._ranges_key = key
+        return self._ranges
+
+    def accumulate(self, first: bool, segment: Optional[str] = None, norm: bool = False) -> torch.Tensor:
+        """Adds the flat gradient buffer (the last backward's gradients) into the model's accumulator, or overwrites the
+        accumulator with it when `first` (its previous contents are then never read) -- eg_grad_accumulate, on the current stream.
+        segment: one bucket of bucket_ranges() instead of the whole buffer (the data-parallel hook of the last micro-step
+        accumulates each bucket as backward releases it).  norm: the same pass leaves the squared-norm partials of the NEW
+        accumulator for optimizer_step(accumulated=True, norm_ready=True); whole buffer only.  Returns the accumulator."""
+        self._alloc_bwd()
+        self.stream = self._cur_stream()
+        acc = self.fp.accumulator()
+        if segment is None:
+            b, e = 0, self.fp.total
+        else:
+            rg = self.bucket_ranges()
+            if segment not in rg:
+                raise L.EgError(f"accumulate: no gradient bucket named {segment!r} (have {sorted(rg)})")
+            b, e = rg[segment]
+            if norm:
+                raise L.EgError("accumulate: the fused norm partials cover the whole buffer, not one bucket")
+        sq = 0
+        if norm:
+            if "sqpart" not in self.g:
+                self.g["sqpart"] = self._t(self.SQ_BLOCKS, dtype=torch.float32)
+            sq = ptr(self.g["sqpart"])
+        self._acc_norm_ready = False
+        if e > b:
+            call("eg_grad_accumulate", ptr(acc) + 4 * b, ptr(self.fp.grad) + 4 * b, e - b, int(bool(first)), sq,
+                 self.SQ_BLOCKS if norm else 0, self.stream)
+        self._acc_norm_ready = bool(norm)
+        return acc
+
+    # ------------------------------------------------------------------------------------------
     # optimiser: clip_grad_norm_(max_norm) + AdamW on the flat buffers (T:221-222)
     # ------------------------------------------------------------------------------------------
     def optimizer_step(self, m: torch.Tensor, v: torch.Tensor, max_norm: float = 1.0, betas=(0.9, 0.999), eps=1e-8,
-                       weight_decay=0.01):
+                       weight_decay=0.01, accumulated: bool = False, norm_ready: bool = False):
+        """accumulated: the gradients are the accumulator's (Engine.accumulate) instead of the last backward's.
+        norm_ready: this engine's last accumulate(norm=True) has left the squared-norm partials of exactly those gradients, so
+        eg_grad_sqnorm's pass over the buffer is not repeated."""
         self._alloc_bwd()
         self.stream = self._cur_stream()
-        nblk = 1024
+        nblk = self.SQ_BLOCKS
         if "sqpart" not in self.g:
             self.g["sqpart"] = self._t(nblk, dtype=torch.float32)
-        call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
+        if accumulated and self.fp.acc is None:
+            raise L.EgError("optimizer_step(accumulated=True) without a preceding Engine.accumulate")
+        if norm_ready and not (accumulated and self._acc_norm_ready):
+            raise L.EgError("optimizer_step(norm_ready=True): no norm partials of the whole accumulator from this engine")
+        grad = self.fp.acc if accumulated else self.fp.grad
+        if not norm_ready:
+            call("eg_grad_sqnorm", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
+        self._acc_norm_ready = False
         call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr, self.stream)
-        call("eg_adamw", ptr(self.fp.flat), ptr(self.fp.grad), ptr(m), ptr(v), self.fp.total, betas[0], betas[1], eps,
+        call("eg_adamw", ptr(self.fp.flat), ptr(grad), ptr(m), ptr(v), self.fp.total, betas[0], betas[1], eps,
              weight_decay, self.st_ptr, self.stream)
         if self.scaler_on:      # GradScaler.update(): back off after an overflow, grow after growth_interval clean steps
             c = self.scaler_cfg

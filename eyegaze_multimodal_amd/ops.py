@@ -11,7 +11,8 @@ REGISTERED operators, visible to the dispatcher / profiler / torch.compile graph
       the native training step without an autograd graph (train_art.py:175-220): forward in train mode + backward of
       loss_ce + lambda_ibs_cls * loss_ibs_cls into the flat gradient buffer; returns [loss_ce, loss_ibs_cls]
   eyegaze::clip_adamw_step(Tensor flat_params, Tensor flat_grads, Tensor exp_avg, Tensor exp_avg_sq, int handle) -> ()
-      clip_grad_norm_(max_norm) + AdamW of train_art.py:221-222 on the flat buffers (mutates all but the gradients)
+      clip_grad_norm_(max_norm) + AdamW of train_art.py:221-222 on the flat buffers (mutates all but the gradients);
+      flat_grads is the module's gradient buffer or, under gradient accumulation, its accumulator (Engine.accumulate)
 
 `handle` names the Python-side engine owner (a module instance): operators carry tensors and scalars only.
 Both operators are CUDA(HIP)-only: there is no CPU kernel behind them, calling them with host tensors raises.

@@ -25,23 +25,36 @@ class HipAdamW:
             self.m = torch.zeros_like(fp.flat)
             self.v = torch.zeros_like(fp.flat)
 
-    def begin_step(self, eng, seed: int, grad_scale: float = 1.0):
-        """Publishes this step's scalars (dropout seed, lr, bias corrections) to the device-resident state."""
-        self.t += 1
+    def begin_step(self, eng, seed: int, grad_scale: float = 1.0, advance: bool = True):
+        """Publishes this step's scalars (dropout seed, lr, bias corrections) to the device-resident state.
+        advance=False: a further micro-batch of the optimiser step already begun (gradient accumulation) -- its own dropout
+        seed and the grad_scale that holds if the group ends with it, under the same t and bias corrections."""
+        if advance:
+            self.t += 1
+        elif self.t < 1:
+            raise RuntimeError("begin_step(advance=False) continues an optimiser step: the group's first micro-batch advances t")
         eng.set_state(seed=seed, lr=self.lr, step=self.t, grad_scale=grad_scale, beta1=self.betas[0], beta2=self.betas[1])
 
-    def step(self, eng):
-        """clip_grad_norm_(max_grad_norm) + AdamW through the registered operator eyegaze::clip_adamw_step (ops.py)."""
+    def step(self, eng, accumulated: bool = False, norm_ready: bool = False):
+        """clip_grad_norm_(max_grad_norm) + AdamW through the registered operator eyegaze::clip_adamw_step (ops.py).
+        accumulated: step on the module's gradient accumulator (Engine.accumulate) instead of the last backward's gradients;
+        norm_ready: eng's last accumulate(norm=True) already produced the norm partials (Engine.optimizer_step)."""
         self._ensure()
         self._eng = eng
         fp = self.model._flat
-        torch.ops.eyegaze.clip_adamw_step(fp.flat, fp.grad, self.m, self.v, self._op_handle)
+        if accumulated and fp.acc is None:
+            raise RuntimeError("HipAdamW.step(accumulated=True): nothing was accumulated (Engine.accumulate)")
+        self._norm_ready = bool(norm_ready)
+        torch.ops.eyegaze.clip_adamw_step(fp.flat, fp.acc if accumulated else fp.grad, self.m, self.v, self._op_handle)
 
     def _native_step(self, flat_params, flat_grads, exp_avg, exp_avg_sq):
         fp = self.model._flat
-        if flat_params.data_ptr() != fp.flat.data_ptr() or flat_grads.data_ptr() != fp.grad.data_ptr():
+        accumulated = fp.acc is not None and flat_grads.data_ptr() == fp.acc.data_ptr()
+        if flat_params.data_ptr() != fp.flat.data_ptr() or not (accumulated or flat_grads.data_ptr() == fp.grad.data_ptr()):
             raise RuntimeError("eyegaze::clip_adamw_step works on the module's own flat parameter / gradient buffers")
-        self._eng.optimizer_step(exp_avg, exp_avg_sq, self.max_grad_norm, self.betas, self.eps, self.weight_decay)
+        norm_ready, self._norm_ready = getattr(self, "_norm_ready", False) and accumulated, False
+        self._eng.optimizer_step(exp_avg, exp_avg_sq, self.max_grad_norm, self.betas, self.eps, self.weight_decay,
+                                 accumulated=accumulated, norm_ready=norm_ready)
 
     def set_epoch(self, epoch: int, t_max: int):
         """CosineAnnealingLR(T_max=t_max, eta_min=0) evaluated at `epoch` (closed form)."""

@@ -11,7 +11,9 @@ Differences, all additive:
     all-reduce overlapped with backward (ddp.py);
   * `data.synthetic: true` (or a missing EEG directory) trains on the class-conditional synthetic windows of
     data.py — the reference's CSVs are not distributed with it;
-  * wandb is optional (imported only when training.report_to == ['wandb'] and the module exists).
+  * wandb is optional (imported only when training.report_to == ['wandb'] and the module exists);
+  * `training.gradient_accumulation_steps: k` (absent = 1 = the reference's one batch per step): every k-th train_step ends
+    in the optimiser step, on the sum of the k micro-batches' gradients divided by k (Trainer.train_step / Trainer.flush).
 """
 from __future__ import annotations
 
@@ -34,7 +36,7 @@ if __package__ in (None, ""):
 
 from . import DualEEGTransformer, HipAdamW  # noqa: E402
 from .data import WindowShards, build_window_shards, synth_windows  # noqa: E402
-from .ddp import GradAllReducer, broadcast_params, bucket_ranges, shard_indices  # noqa: E402
+from .ddp import AccumulatingReducer, GradAllReducer, broadcast_params, bucket_ranges, shard_indices  # noqa: E402
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
 logger = logging.getLogger("train_art")
@@ -59,6 +61,14 @@ def build_model(config: Dict[str, Any], compute_dtype=None) -> DualEEGTransforme
         use_ibs=ab.get("use_ibs", True), use_cross_attention=ab.get("use_cross_attention", True),
         ibs_instance_norm=ab.get("ibs_instance_norm", True), ibs_feature_type=ab.get("ibs_feature_type", "all"),
         compute_dtype=compute_dtype or config.get("system", {}).get("compute_dtype"))
+
+
+def accumulation_steps(config: Dict[str, Any]) -> int:
+    """training.gradient_accumulation_steps: micro-batches per optimiser step, an integer >= 1; absent means 1."""
+    k = (config.get("training") or {}).get("gradient_accumulation_steps", 1)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"training.gradient_accumulation_steps must be an integer >= 1 (got {k!r})")
+    return k
 
 
 def macro_metrics(y_true: np.ndarray, y_pred: np.ndarray) -> Dict[str, float]:
@@ -88,8 +98,13 @@ class Trainer:
         t = config["training"]
         self.opt = HipAdamW(self.model, lr=t["learning_rate"], weight_decay=t["weight_decay"])
         self.epochs = t["num_train_epochs"]
-        self.step_no = 0
-        self.reducer = None
+        self.step_no = 0                 # optimiser steps taken
+        self.micro_no = 0                # micro-batches seen: the dropout seed counter (== step_no without accumulation)
+        self.accum = accumulation_steps(config)
+        self.pending = 0                 # micro-batches in the accumulator since the last optimiser step
+        self.reducer = None              # data parallel, one batch per step: reduces the gradient buffer
+        self.accred = None               # data parallel with accumulation: reduces the accumulator, once per optimiser step
+        self._last_eng = None
         ab = config.get("ablation", {})
         self.has_ibs = ab.get("use_ibs", True)
         self.lam_ibs_cls = t.get("lambda_ibs_cls", 0.5) if (t.get("use_ibs_cls_loss", True) and self.has_ibs) else 0.0
@@ -100,22 +115,80 @@ class Trainer:
 
     def _engine(self, B, T):
         eng = self.model.engine(B, T, self.device)
-        if self.world > 1 and (self.reducer is None or self.reducer.g is not self.model._flat.grad):
-            fp = self.model._flat
+        self._last_eng = eng
+        fp = self.model._flat
+        if self.world > 1 and self.accum == 1 and (self.reducer is None or self.reducer.g is not fp.grad):
             broadcast_params(fp.flat)
             rg = bucket_ranges(fp.names, fp.offsets, fp.total, self.model.cfg.num_layers, self.model.cfg.use_cross_attention)
             self.reducer = GradAllReducer(fp.grad, rg)
+        if self.world > 1 and self.accum > 1 and (self.accred is None or self.accred.grad is not fp.grad):
+            broadcast_params(fp.flat)
+            self.accred = AccumulatingReducer(fp.grad, fp.accumulator(), eng.bucket_ranges(),
+                                              accumulate_fn=lambda first, seg: self._last_eng.accumulate(first, seg))
         return eng
 
+    def _begin_micro(self, eng):
+        """Publishes this micro-batch's scalars; returns (first, last, on_segment hook).  Without accumulation a micro-batch
+        is the whole step.  With it, t advances on a group's first micro-batch only, every micro-batch draws its own dropout
+        seed, and grad_scale is the one that holds if the group ended here -- 1 / (micro-batches so far x world); only the
+        optimiser kernels read it -- so a short final group steps with the right divisor (flush)."""
+        self.micro_no += 1
+        seed = self.config["system"]["seed"] * 7919 + self.micro_no * self.world + self.rank
+        if self.accum == 1:
+            self.opt.begin_step(eng, seed=seed, grad_scale=1.0 / self.world)
+            return True, True, (self.reducer.on_segment if self.reducer else None)
+        first = self.pending == 0
+        self.pending += 1
+        last = self.pending == self.accum
+        self.opt.begin_step(eng, seed=seed, grad_scale=1.0 / (self.pending * self.world), advance=first)
+        return first, last, (self.accred.final_hook(first) if (self.accred and last) else None)
+
+    def _end_micro(self, eng, first: bool, last: bool):
+        """After backward: the exchange / accumulation of this micro-batch and, when it ends its group, the optimiser step."""
+        if self.accum == 1:
+            if self.reducer:
+                self.reducer.finish()
+            self.opt.step(eng)
+            self.step_no += 1
+            return
+        if self.accred:
+            if last:
+                self.accred.finish()          # the hook accumulated and reduced bucket by bucket under the backward
+            else:
+                self.accred.accumulate(first)
+        else:
+            eng.accumulate(first, norm=last)  # the group's last pass also leaves the norm partials: no eg_grad_sqnorm
+        if last:
+            self.opt.step(eng, accumulated=True, norm_ready=self.accred is None)
+            self.pending = 0
+            self.step_no += 1
+
+    def flush(self) -> bool:
+        """Optimiser step on whatever is pending (a group cut short by the end of an epoch), divided by the number of
+        micro-batches actually accumulated: the last of them published that grad_scale.  Returns whether a step was taken."""
+        if self.pending == 0:
+            return False
+        eng = self._last_eng
+        if self.accred:
+            self.accred.flush()
+            self.accred.finish()
+        self.opt.step(eng, accumulated=True)
+        self.pending = 0
+        self.step_no += 1
+        return True
+
     def train_step(self, eeg1, eeg2, labels) -> Dict[str, float]:
-        """One optimiser step (train_art.py:171-222).  Returns device scalars (no host sync here)."""
+        """One micro-batch (train_art.py:171-222): forward, backward and -- every gradient_accumulation_steps-th call, which
+        without accumulation is every call -- the optimiser step.  Returns device scalars (no host sync here).
+
+        Accumulation convention: the k micro-batches of a group carry equal weight, i.e. the update is that of the loss
+        (l_1 + ... + l_k) / k.  A ragged tail batch therefore weighs as much as a full one (its samples more than the others'),
+        and the batch-level auxiliary losses see one micro-batch at a time, as they already see one rank's batch under data
+        parallelism.  The returned losses are this micro-batch's own, undivided."""
         self.model.train()
         B, _, T = eeg1.shape
         eng = self._engine(B, T)
-        self.step_no += 1
-        gs = 1.0 / self.world
-        self.opt.begin_step(eng, seed=self.config["system"]["seed"] * 7919 + self.step_no * self.world + self.rank, grad_scale=gs)
-        hook = self.reducer.on_segment if self.reducer else None
+        first, last, hook = self._begin_micro(eng)
         need_aux = any(self.aux.values())
         zero = torch.zeros((), device=self.device)
         if not need_aux:
@@ -125,9 +198,7 @@ class Trainer:
             loss_ce, loss_ibs = torch.ops.eyegaze.dual_eeg_train_step(eeg1, eeg2, labels, fp.flat, fp.grad,
                                                                      float(self.lam_ibs_cls if self.has_ibs else 0.0),
                                                                      self.model._op_handle)
-            if self.reducer:
-                self.reducer.finish()
-            self.opt.step(eng)
+            self._end_micro(eng, first, last)
             li = loss_ibs if (self.has_ibs and self.lam_ibs_cls != 0.0) else zero
             return {"loss": (loss_ce + self.lam_ibs_cls * li).detach(), "loss_ce": loss_ce, "loss_sym": zero, "loss_ibs": zero,
                     "loss_ibs_cls": li, "loss_ibs_contrastive": zero}
@@ -160,9 +231,7 @@ class Trainer:
                 aux.backward()
                 kw.update(gcls1=cls1.grad, gcls2=cls2.grad, gibs_token=(ibs.grad if ibs is not None else None))
         eng.backward(gloss=one, on_segment=hook, **kw)
-        if self.reducer:
-            self.reducer.finish()
-        self.opt.step(eng)
+        self._end_micro(eng, first, last)
         losses["loss"] = (losses["loss_ce"] + self.lams["sym"] * losses["loss_sym"] + self.lams["ibs"] * losses["loss_ibs"] +
                           self.lam_ibs_cls * losses["loss_ibs_cls"] + self.lams["contrastive"] * losses["loss_ibs_contrastive"])
         return {k: v.detach() for k, v in losses.items()}
@@ -341,6 +410,7 @@ def main(args):
             for k, v in losses.items():
                 sums[k] = sums.get(k, 0.0) + v.float()
             nb += 1
+        tr.flush()      # gradient accumulation: no gradient crosses an epoch, no learning-rate change falls inside a group
         train_metrics = {f"train/{k}": float(sums.get(k, 0.0)) / max(nb, 1) for k in TRAIN_KEYS}   # train_art.py:248-255
         if shards is not None:
             test_ld = WindowShards(shards["test"], ebs, device, rank, world, preprocessing=d.get("enable_preprocessing", False))

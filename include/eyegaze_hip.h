@@ -468,6 +468,14 @@ int eg_fuzzy_gate_bwd(const float* z_img, const float* z_eeg, const float* param
  *             the whole step is skipped when state->scaler_on && state->found_inf (GradScaler.step)
  * ------------------------------------------------------------------------------------------- */
 int eg_grad_sqnorm(const float* g, int64_t n, float* partial, int nblk, void* stream);
+/* Gradient accumulation over micro-batches: acc[i] = first ? g[i] : acc[i] + g[i] for i < n, one fp32 addition per element
+ * (bit-identical to torch.add; inf / NaN propagate, which is what lets one overflowing micro-batch skip the whole update).
+ *   first != 0: acc is overwritten without being read (stale contents, NaN included, do not leak through).
+ *   sq_partial != NULL: the same pass writes sq_partial[blk] = sum of acc_new[i]^2 for all nblk entries (blocks without
+ *     elements write 0) -- eg_grad_sqnorm's contract, so eg_clip_coef(sq_partial, nblk, ...) consumes it unchanged.
+ *   n is a positive multiple of 4 and both pointers are 16-B aligned (any bucket range of the flat buffers qualifies);
+ *   1 <= nblk <= 1024 when sq_partial is given.  The grid is sized from the CU count, not from n. */
+int eg_grad_accumulate(float* acc, const float* g, int64_t n, int first, float* sq_partial, int nblk, void* stream);
 int eg_clip_coef(const float* partial, int nblk, float max_norm, eg_step_state* state, void* stream);
 int eg_adamw(float* p, const float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
              float weight_decay, const eg_step_state* state, void* stream);
