@@ -156,6 +156,7 @@ SIGNATURES = {
     "eg_grad_sqnorm": [_P, _L, _P, _I, _P],
     "eg_grad_accumulate": [_P, _P, _L, _I, _P, _I, _P],
     "eg_clip_coef": [_P, _I, _F, _P, _P],
+    "eg_grad_sqnorm_clip": [_P, _L, _P, _I, _F, _P, _P, _P],
     "eg_adamw": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _P],
     "eg_fill_f32": [_P, _L, _F, _P],
     "eg_adamw_group": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P],

@@ -5,9 +5,8 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, long long n,
-                                                             float* __restrict__ partial) {
-  __shared__ float red[4];
+// one block's squared-norm partial (256 threads; the value is returned to thread 0)
+__device__ __forceinline__ float sqnorm_block(const float* __restrict__ g, long long n, float* red) {
   float s = 0.f;
   const long long stride = (long long)gridDim.x * 256 * 4;
   for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
@@ -21,11 +20,18 @@ __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __rest
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  return red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void clip_coef_kernel(const float* __restrict__ partial, int n, float max_norm, eg_step_state* st) {
-  __shared__ double red[256];
+__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, long long n,
+                                                             float* __restrict__ partial) {
+  __shared__ float red[4];
+  const float s = sqnorm_block(g, n, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// the n partials -> global norm, clip coefficient and overflow flag of the step state (one block of 256 threads)
+__device__ __forceinline__ void clip_coef_block(const float* partial, int n, float max_norm, eg_step_state* st, double* red) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
   red[threadIdx.x] = s;
@@ -42,6 +48,32 @@ __global__ void clip_coef_kernel(const float* __restrict__ partial, int n, float
     st->clip_coef = fminf(coef, 1.0f);
     st->found_inf = (st->scaler_on && !(fabsf(norm) <= 3.0e38f)) ? 1u : 0u;   // inf or NaN
   }
+}
+
+__global__ void clip_coef_kernel(const float* __restrict__ partial, int n, float max_norm, eg_step_state* st) {
+  __shared__ double red[256];
+  clip_coef_block(partial, n, max_norm, st, red);
+}
+
+// sqnorm_partial_kernel + clip_coef_kernel in one launch: every block leaves its partial, and the block that finishes LAST (a
+// device counter tells it; nobody waits for anybody) does clip_coef_kernel's sums over all of them and clears the counter for the
+// next launch.  Same thread-to-element map, same partials, same double-precision tree: the state fields get the same bits.
+__global__ __launch_bounds__(256) void sqnorm_clip_kernel(const float* __restrict__ g, long long n, float* partial,
+                                                          float max_norm, eg_step_state* st, unsigned* counter) {
+  __shared__ float red[4];
+  __shared__ double dred[256];
+  __shared__ bool last_s;
+  const float s = sqnorm_block(g, n, red);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = s;
+    __threadfence();
+    last_s = atomicAdd(counter, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last_s) return;
+  __threadfence();
+  clip_coef_block(partial, (int)gridDim.x, max_norm, st, dred);
+  if (threadIdx.x == 0) *counter = 0u;
 }
 
 __global__ void set_step_state_kernel(eg_step_state* st, uint32_t seed_lo, uint32_t seed_hi, float lr, float bc1, float bc2,
@@ -154,6 +186,16 @@ extern "C" int eg_grad_sqnorm(const float* g, int64_t n, float* partial, int nbl
   EG_CHECK((uintptr_t)g % 16 == 0, "eg_grad_sqnorm: alignment");
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, g, (long long)n, partial);
   EG_LAUNCH_CHECK("grad_sqnorm");
+  return 0;
+}
+
+extern "C" int eg_grad_sqnorm_clip(const float* g, int64_t n, float* partial, int nblk, float max_norm, eg_step_state* state,
+                                   uint32_t* counter, void* stream) {
+  EG_CHECK(g && partial && state && counter && n > 0 && nblk > 0 && nblk <= 4096, "eg_grad_sqnorm_clip: bad arguments");
+  EG_CHECK((uintptr_t)g % 16 == 0 && (uintptr_t)counter % 4 == 0, "eg_grad_sqnorm_clip: alignment");
+  hipLaunchKernelGGL(sqnorm_clip_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, g, (long long)n, partial, max_norm, state,
+                     counter);
+  EG_LAUNCH_CHECK("grad_sqnorm_clip");
   return 0;
 }
 

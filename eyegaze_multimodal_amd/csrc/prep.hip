@@ -230,26 +230,59 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const eg_pack_entry* __
   pack_block<T>(a, blockIdx.x - e.blk0, tile);
 }
 
-// eg_pack_table_ex: the modes above plus the two convolution weight layouts (1024 destination elements per block, four per
-// thread at stride 256 so that a wave's stores stay contiguous):
+// eg_pack_table_ex: the modes above plus the two convolution weight layouts (1024 destination elements per block in the
+// block count):
 //   mode 9  = pack_conv_weight_kernel:  rows = N, cols = Cin, p0 = k, p1 = Cp, p2 = Kp
 //   mode 10 = pack_convT_weight_kernel: rows = N, cols = Cin, p0 = k, p1 = stride, p2 = J
+// Both go through LDS (the reverse of unpack_conv_wgrad_kernel): a block takes whole UNITS of the entry, strided by the
+// entry's block count.  A unit's source is contiguous runs of w [N, Cin, k] and its destination is contiguous runs of dst;
+// the (c, tap) -> (tap, c) / phase transposition is done by the LDS addressing.
+//   mode 9 unit  = (n, CT channels): reads w[n][c0 .. c0+CT)[0 .. k), one run; writes k runs of CT at dst[n][tap*Cp + c0];
+//                  the unit with c0 == 0 also zeroes the row's tail [k*Cp, Kp).
+//   mode 10 unit = (32 rows n, CT channels): reads 32 runs of CT*k; writes stride*CT*J runs of 32 at dst[p][c][j*N + n0].
+// A kernel size too long for the staging buffer takes the element-wise gather of the stand-alone kernels instead.
+constexpr int PACK_STAGE = 4096;   // floats of LDS behind modes 9 / 10
+constexpr int PACK_NT = 32;        // rows n of a mode-10 unit
 template <typename T>
 __global__ __launch_bounds__(256) void pack_table_ex_kernel(const eg_pack_entry_ex* __restrict__ tab, int nent) {
-  __shared__ float tile[32][33];
+  __shared__ float stage[PACK_STAGE];
   __shared__ int ent_s;
+  static_assert(PACK_STAGE >= 32 * 33, "modes 0-8 use the buffer as a [32][33] tile");
   const eg_pack_entry_ex e = tab[pack_find_entry(tab, nent, &ent_s)];
   const int lb = blockIdx.x - e.blk0;
   if (e.mode < 9) {
     const PackArgs a = {e.src, e.dst, e.rows, e.cols, e.ldd, e.mode};
-    pack_block<T>(a, lb, tile);
+    pack_block<T>(a, lb, (float (*)[33])stage);
     return;
   }
   const float* w = (const float*)e.src;
   T* dst = (T*)e.dst;
   const int N = e.rows, Cin = e.cols, k = e.p0;
+  const int ks = k | 1;   // odd pitch: lanes that walk c at a fixed tap hit distinct banks
   if (e.mode == 9) {
     const int Cp = e.p1, Kp = e.p2;
+    const int CT = min(min(Cp, 64), PACK_STAGE / ks);
+    if (CT > 0) {
+      const int cchunks = (Cp + CT - 1) / CT;
+      const long long units = (long long)N * cchunks;
+      for (long long u = lb; u < units; u += e.nblk) {
+        const int n = (int)(u / cchunks), c0 = (int)(u % cchunks) * CT;
+        const int cn = min(CT, Cp - c0);              // destination channels of this unit
+        const int cs = max(0, min(cn, Cin - c0));     // of which the source has this many
+        const float* wr = w + ((size_t)n * Cin + c0) * k;
+        for (int i = threadIdx.x; i < cs * k; i += 256) stage[(i / k) * ks + i % k] = wr[i];
+        __syncthreads();
+        T* dr = dst + (size_t)n * Kp;
+        for (int i = threadIdx.x; i < cn * k; i += 256) {
+          const int tap = i / cn, cc = i % cn;
+          Elem<T>::st(dr + (size_t)tap * Cp + c0 + cc, cc < cs ? stage[cc * ks + tap] : 0.f);
+        }
+        if (c0 == 0)
+          for (int i = k * Cp + threadIdx.x; i < Kp; i += 256) Elem<T>::st(dr + i, 0.f);
+        __syncthreads();
+      }
+      return;
+    }
     const long long total = (long long)N * Kp;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -262,6 +295,32 @@ __global__ __launch_bounds__(256) void pack_table_ex_kernel(const eg_pack_entry_
     }
   } else {
     const int s = e.p1, J = e.p2;
+    constexpr int NP = PACK_NT + 1;   // stage[(cc*ks + tap)*NP + nn]: conflict-free on the way in and on the way out
+    const int CT = min(min(Cin, 4), PACK_STAGE / (ks * NP));
+    if (CT > 0) {
+      const int cchunks = (Cin + CT - 1) / CT, nchunks = (N + PACK_NT - 1) / PACK_NT;
+      const long long units = (long long)nchunks * cchunks;
+      for (long long u = lb; u < units; u += e.nblk) {
+        const int n0 = (int)(u / cchunks) * PACK_NT, c0 = (int)(u % cchunks) * CT;
+        const int cn = min(CT, Cin - c0), nn_n = min(PACK_NT, N - n0);
+        const int run = cn * k;                       // contiguous source floats per row n
+        for (int i = threadIdx.x; i < nn_n * run; i += 256) {
+          const int nn = i / run, r = i % run;
+          stage[((r / k) * ks + r % k) * NP + nn] = w[((size_t)(n0 + nn) * Cin + c0) * k + r];
+        }
+        __syncthreads();
+        const int per_c = J * nn_n, per_p = cn * per_c;
+        for (int i = threadIdx.x; i < s * per_p; i += 256) {
+          const int p = i / per_p, r = i % per_p;
+          const int cc = r / per_c, jn = r % per_c;
+          const int j = jn / nn_n, nn = jn % nn_n;
+          const int tap = s * (J - 1 - j) + p;
+          Elem<T>::st(dst + (((size_t)p * Cin + c0 + cc) * J + j) * N + n0 + nn, tap < k ? stage[(cc * ks + tap) * NP + nn] : 0.f);
+        }
+        __syncthreads();
+      }
+      return;
+    }
     const long long per_phase = (long long)Cin * J * N;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {

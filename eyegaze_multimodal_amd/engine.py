@@ -222,6 +222,11 @@ class Engine:
         # route for fp32 and for the shapes the fused kernels do not cover (see _fused_heads); tests set this attribute to
         # False to compare the two routes.
         self.fused_tail = dtype != EG_F32
+        # False: pack_params skips the layouts that the routes chosen above never read (see _pack_body); True packs every one
+        self.pack_unused = False
+        # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
+        # instead of eg_grad_sqnorm + eg_clip_coef.  Off by default: tests/test_gpu_accum.py counts the trainer's eg_grad_sqnorm calls
+        self.fused_norm_clip = False
         self._alloc()
         self.packed_version = -1
         self._recording = False
@@ -612,6 +617,11 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     GROUP_SPLITS = int(os.environ.get("EYEGAZE_GROUP_SPLITS", "5"))
     GROUP_MIN_ROWS = 4096   # below this the per-product launches (many splits) are the better shape
+    REDUCE_LN_FIRST = os.environ.get("EYEGAZE_REDUCE_LN_FIRST", "1") != "0"   # order of the grouped reduce table, see tables()
+
+    def _ln_splits(self, name: str) -> int:
+        """partial rows that the backward of LayerNorm `name` leaves (eg_ln_bwd_proj's tiles for a layer's ln1, else LN_BLOCKS)"""
+        return self.ln_proj_blocks if (self.ln_proj and name.endswith(".ln1")) else self.LN_BLOCKS
 
     def _wgrad_group_plan(self):
         if getattr(self, "_wg_plan", "unset") != "unset" and getattr(self, "_wg_key", None) == self.fp.grad.data_ptr():
@@ -669,18 +679,23 @@ class Engine:
         ln_names = [f"encoder.layers.{l}.{n}" for l in range(cfg.num_layers) for n in ("ln1", "ln2")]
         if not all(fp.offsets[n + ".bias"] == fp.offsets[n + ".weight"] + d for n in ln_names):
             return None
-        g["lnpart_all"] = self._t(len(ln_names) * self.ln_nblk_cap * 2 * d, dtype=torch.float32)
-        self._ln_slot = {n: i for i, n in enumerate(ln_names)}
+        # encoder.norm and cross_attn.norm get slots behind the layers': without a gradient reducer their gain / bias partials
+        # ride in the whole-encoder reduce launch too (backward decides; with a reducer their buckets are released at once)
+        tail_names = [n for n in ["encoder.norm"] + (["cross_attn.norm"] if cfg.use_cross_attention else [])
+                      if fp.offsets[n + ".bias"] == fp.offsets[n + ".weight"] + d]
+        g["lnpart_all"] = self._t((len(ln_names) + len(tail_names)) * self.ln_nblk_cap * 2 * d, dtype=torch.float32)
+        self._ln_slot = {n: i for i, n in enumerate(ln_names + tail_names)}
         ln_of = {}
         for i, n in enumerate(ln_names):
             ln_of.setdefault(int(n.split(".")[2]), []).append((i, n))
+        ln_tail = [(self._ln_slot[n], n) for n in tail_names]
         dev = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
         offs, off = [], 0
         for names, dyn, xn, N, K, ldy in probs:
             offs.append(off)
             off += smax * (N * K + N)
 
-        def tables(layers, with_cross=False, nsplit=None):
+        def tables(layers, with_cross=False, nsplit=None, with_tail=False):
             """TN problem table + reduce table (weights, biases and the deferred LayerNorm gain / bias partials) of `layers`
             (+ the cross-attention block's two products); block ranges are relative to the tables' own launches.  Which launch
             a product rides in does not change its result AT EQUAL nsplit (same row split, same ordered sum); the data-parallel
@@ -690,24 +705,29 @@ class Engine:
             sel = [4 * l + j for l in layers for j in range(4)]
             if with_cross:
                 sel += [4 * cfg.num_layers + j for j in range(ncross)]
-            lns = [e for l in layers for e in ln_of[l]]
+            lns = [e for l in layers for e in ln_of[l]] + (ln_tail if with_tail else [])
             tp = (L.TNProblem * len(sel))()
             rt = (L.ReduceEntry * (len(sel) + len(lns)))()
-            blk, rblk = 0, 0
-            for e, r, pi in zip(tp, rt, sel):
+            blk = 0
+            red = []        # (partial, out, n, splits) of the reduce entries, weight gradients first
+            for e, pi in zip(tp, sel):
                 names, dyn, xn, N, K, ldy = probs[pi]
                 slab = N * K + N
                 base = ptr(g["wg_partial"]) + 4 * offs[pi]
                 e.dY, e.X, e.partial = ptr(g[dyn]), ptr(self.a[xn]), base
                 e.ldy, e.ldx, e.N, e.K, e.part_rows, e.has_bias, e.blk0 = ldy, K, N, K, N // len(names), 1, blk
                 blk += ((N + tile - 1) // tile) * ((K + tile - 1) // tile) * nsplit
-                r.partial, r.out, r.n, r.stride, r.splits, r.blk0 = base, fp.g_ptr(names[0] + ".weight"), slab, slab, nsplit, rblk
-                rblk += _reduce_blocks(slab, nsplit)
-            for k, (i, n) in enumerate(lns):   # deferred LayerNorm gain / bias partials ride in the same reduce launch
-                r = rt[len(sel) + k]
-                r.partial, r.out = ptr(g["lnpart_all"]) + 4 * i * self.ln_nblk_cap * 2 * d, fp.g_ptr(n + ".weight")
-                r.n, r.stride, r.splits, r.blk0 = 2 * d, 2 * d, (self.ln_proj_blocks if (self.ln_proj and n.endswith(".ln1")) else self.LN_BLOCKS), rblk
-                rblk += _reduce_blocks(2 * d, r.splits)
+                red.append((base, fp.g_ptr(names[0] + ".weight"), slab, nsplit))
+            # deferred LayerNorm gain / bias partials ride in the same reduce launch.  Such an entry is 16 workgroups that walk
+            # hundreds of short rows each, pure latency: they go FIRST in the table, so that they run under the streaming
+            # weight-gradient entries instead of after them
+            lnred = [(ptr(g["lnpart_all"]) + 4 * i * self.ln_nblk_cap * 2 * d, fp.g_ptr(n + ".weight"), 2 * d, self._ln_splits(n))
+                     for i, n in lns]
+            red = lnred + red if self.REDUCE_LN_FIRST else red + lnred
+            rblk = 0
+            for r, (part, out, n, nsp) in zip(rt, red):
+                r.partial, r.out, r.n, r.stride, r.splits, r.blk0 = part, out, n, n, nsp, rblk
+                rblk += _reduce_blocks(n, nsp)
             return dict(tp=dev(tp), rt=dev(rt), n=len(sel), nr=len(sel) + len(lns), blocks=blk, rblocks=rblk, layers=list(layers),
                         splits=nsplit)
 
@@ -719,6 +739,7 @@ class Engine:
         pieces = ([tables(range(h, Lr), with_cross=True, nsplit=splits_p), tables(range(0, h), nsplit=splits_p)]
                   if Lr >= 2 else [whole])
         self._wg_plan = dict(whole, splits=splits, pieces=pieces, split_layer=h,
+                             whole_norms=tables(range(Lr), with_cross=True, with_tail=True) if ln_tail else None,
                              entry="eg_gemm_tn_grouped256" if big else "eg_gemm_tn_grouped")
         return self._wg_plan
 
@@ -818,7 +839,9 @@ class Engine:
 
     def pack_params(self):
         ex = bool(getattr(self, "fused_tail", False))       # (the image engine shares this method and keeps eg_pack_table)
-        key = (self.fp.flat.data_ptr(), ex)
+        # the routing flags decide which layouts _pack_body records, so a flag flipped on a live engine re-records the plan
+        key = (self.fp.flat.data_ptr(), ex, bool(getattr(self, "pack_unused", False)), getattr(self, "fuse_ffn", None),
+               getattr(self, "attn_block", None), getattr(self, "ln_proj", None))
         self._plan_ex = ex
         if getattr(self, "_plan_key", None) != key:
             self._plan, self._recording = [], True
@@ -862,13 +885,23 @@ class Engine:
         self.p_convT(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1T"]), d, d, self.k, self.s)
         self.p_cast(fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["pos"]), cfg.max_len * d)
 
+        # Layouts that the chosen route never reads are not recorded (their buffers stay allocated): the row-major q|k|v and
+        # out_proj of an encoder layer belong to the unfused attention route, out_proj^T to the separate backward-data product
+        # when eg_ln_bwd_proj is off, the four row-major feed-forward matrices to the unfused feed-forward route.  The
+        # cross-attention block "x" has no fused route and keeps all of its layouts.  pack_unused = True records everything.
+        full = bool(self.pack_unused)
+
         def attn_pack(pre, l):
+            enc = l != "x"
             for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                self.p_cast(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkv{l}"]) + i * d * d * self.es, d * d)
+                if full or not (enc and self.attn_block):
+                    self.p_cast(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkv{l}"]) + i * d * d * self.es, d * d)
                 self.p_transpose(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkvT{l}"]) + i * d * self.es, d, d, 3 * d)
                 self.p_copy(fp.p_ptr(f"{pre}{n}.bias"), ptr(w[f"bqkv{l}"]) + 4 * i * d, d)
-            self.p_cast(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"o{l}"]), d * d)
-            self.p_transpose(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"oT{l}"]), d, d, d)
+            if full or not (enc and self.attn_block):
+                self.p_cast(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"o{l}"]), d * d)
+            if full or not (enc and self.ln_proj):
+                self.p_transpose(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"oT{l}"]), d, d, d)
             if self.ln_proj and l != "x":
                 self.p_frag(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"oTf{l}"]), d, d, 6)
             if self.attn_block and l != "x":
@@ -879,10 +912,11 @@ class Engine:
         for l in range(cfg.num_layers):
             pre = f"encoder.layers.{l}."
             attn_pack(pre + "mha.", l)
-            self.p_cast(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1{l}"]), F * d)
-            self.p_transpose(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1T{l}"]), F, d, F)
-            self.p_cast(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2{l}"]), d * F)
-            self.p_transpose(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2T{l}"]), d, F, d)
+            if full or not self.fuse_ffn:
+                self.p_cast(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1{l}"]), F * d)
+                self.p_transpose(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1T{l}"]), F, d, F)
+                self.p_cast(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2{l}"]), d * F)
+                self.p_transpose(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2T{l}"]), d, F, d)
             if self.fuse_ffn:
                 self.p_frag(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1f{l}"]), F, d, 3)     # forward product 1
                 self.p_frag(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2f{l}"]), d, F, 5)     # forward product 2
@@ -1102,15 +1136,20 @@ class Engine:
 
         has_drop = p > 0
         gx = False
+        # no reducer waits for the encoder.norm / cross buckets: the gain / bias partials of the two norms outside the layers
+        # are summed by the grouped reduce launch at the end of backward instead of a 16-workgroup launch each
+        defer_norms = grouped and not pieced and on_segment is None and self._wg_plan["whole_norms"] is not None
+        nslot = lambda n: self._ln_slot.get(n) if defer_norms else None
         if cfg.use_cross_attention:
             xs = _layer_sites(Lr)
             gx = grouped and self._wg_cross                     # its weight gradients ride in the grouped launch
             drm = g["dYo_x"] if gx else (g["drm"] if has_drop else g["dr"])
             if has_drop:
-                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", g["dr"], drm, d1=(p, xs["drop1"]))
+                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", g["dr"], drm, d1=(p, xs["drop1"]),
+                            slot=nslot("cross_attn.norm"))
                 drx = g["dr"]
             else:
-                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", drm, None)
+                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", drm, None, slot=nslot("cross_attn.norm"))
                 drx = drm
             attn_block_bwd("cross_attn.cross_attn.", "x", a["zn"], drx, drm, B, xs["attn"], other,
                            g["dqkv_x"] if gx else g["dqkv"], gx)
@@ -1118,7 +1157,7 @@ class Engine:
             if not gx:
                 seg("cross")
         # final encoder norm (A:328)
-        self.ln_bwd(dz, a[f"x{Lr}"], a["stf"], "encoder.norm", other)
+        self.ln_bwd(dz, a[f"x{Lr}"], a["stf"], "encoder.norm", other, slot=nslot("encoder.norm"))
         dz, other = other, dz
         seg("encoder.norm")
         for l in reversed(range(Lr)):
@@ -1177,7 +1216,7 @@ class Engine:
                 for ll in reversed(self._wg_plan["pieces"][1]["layers"]):
                     seg(f"layer{ll}")
             else:
-                self._wgrad_group_launch()
+                self._wgrad_group_launch(self._wg_plan["whole_norms"] if defer_norms else None)
                 if gx:
                     seg("cross")
                 for l in reversed(range(Lr)):
@@ -1274,10 +1313,16 @@ class Engine:
         if norm_ready and not (accumulated and self._acc_norm_ready):
             raise L.EgError("optimizer_step(norm_ready=True): no norm partials of the whole accumulator from this engine")
         grad = self.fp.acc if accumulated else self.fp.grad
-        if not norm_ready:
-            call("eg_grad_sqnorm", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
         self._acc_norm_ready = False
-        call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr, self.stream)
+        if norm_ready or not self.fused_norm_clip:
+            if not norm_ready:
+                call("eg_grad_sqnorm", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
+            call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr, self.stream)
+        else:       # squared-norm partials and the coefficient in one launch (the last workgroup to finish sums the partials)
+            if "sq_ctr" not in self.g:
+                self.g["sq_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)
+            call("eg_grad_sqnorm_clip", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr,
+                 ptr(self.g["sq_ctr"]), self.stream)
         call("eg_adamw", ptr(self.fp.flat), ptr(grad), ptr(m), ptr(v), self.fp.total, betas[0], betas[1], eps,
              weight_decay, self.st_ptr, self.stream)
         if self.scaler_on:      # GradScaler.update(): back off after an overflow, grow after growth_interval clean steps

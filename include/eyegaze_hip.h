@@ -115,7 +115,8 @@ int eg_pack_table(const eg_pack_entry* table, int nentries, int total_blocks, in
  * every weight of a step:
  *   mode 9  = eg_pack_conv_weight:  rows = N, cols = Cin, p0 = k, p1 = Cp, p2 = Kp       (N * Kp destination elements)
  *   mode 10 = eg_pack_convT_weight: rows = N, cols = Cin, p0 = k, p1 = stride, p2 = J    (stride * Cin * J * N elements)
- * both at 1024 destination elements per block.  src_elems / dst_elems are the extents (fp32 source elements, destination
+ * both counted at 1024 destination elements per block (nblk; which elements a block serves is the kernel's business: it
+ * stages whole (row, channel-chunk) units through LDS).  src_elems / dst_elems are the extents (fp32 source elements, destination
  * elements) of the buffers behind src / dst from those addresses on, 0 = not stated (modes 9 / 10 must state both).
  * eg_pack_table_ex_check audits a HOST copy of the table when it is built -- block ranges, per-mode shape rules, alignment and
  * the stated extents -- and returns the launch's block count; eg_pack_table_ex launches the DEVICE copy. */
@@ -477,6 +478,11 @@ int eg_grad_sqnorm(const float* g, int64_t n, float* partial, int nblk, void* st
  *   1 <= nblk <= 1024 when sq_partial is given.  The grid is sized from the CU count, not from n. */
 int eg_grad_accumulate(float* acc, const float* g, int64_t n, int first, float* sq_partial, int nblk, void* stream);
 int eg_clip_coef(const float* partial, int nblk, float max_norm, eg_step_state* state, void* stream);
+/* eg_grad_sqnorm + eg_clip_coef as ONE launch: the same nblk partials (also left in `partial`) and the same bits in
+ * state->grad_norm / clip_coef / found_inf.  The workgroup that finishes last sums the partials; `counter` is one zeroed
+ * uint32 in device memory that the launch leaves at zero again (one launch at a time per counter). */
+int eg_grad_sqnorm_clip(const float* g, int64_t n, float* partial, int nblk, float max_norm, eg_step_state* state,
+                        uint32_t* counter, void* stream);
 int eg_adamw(float* p, const float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
              float weight_decay, const eg_step_state* state, void* stream);
 int eg_fill_f32(float* p, int64_t n, float value, void* stream);
