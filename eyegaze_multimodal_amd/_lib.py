@@ -14,6 +14,7 @@ LIB_PATH = _PKG / "libeyegaze_hip.so"
 EG_F32, EG_BF16, EG_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ABI_VERSION = 5
+GEMM_BATCH_MAX = 8      # EG_GEMM_BATCH_MAX
 
 
 class EgError(RuntimeError):
@@ -119,6 +120,10 @@ SIGNATURES = {
     "eg_pack_convT_weight": [_P, _P, _I, _I, _I, _I, _I, _P],
     "eg_gemm_nt": [C.POINTER(GemmDesc), _P],
     "eg_gemm_nt_route": [C.POINTER(GemmDesc)],
+    "eg_gemm_wide_rows": [_I, _I],
+    "eg_gemm_wide_config": [_I, _I],
+    "eg_gemm_nt_batch": [C.POINTER(GemmDesc), _I, _P],
+    "eg_gemm_nt_batch_route": [C.POINTER(GemmDesc), _I],
     "eg_ffn_chain": [C.POINTER(FfnDesc), _P],
     "eg_ln_bwd_proj": [C.POINTER(LnBwdProjDesc), _P],
     "eg_ln_bwd_proj_blocks": [_I],

@@ -853,10 +853,13 @@ static int launch_gemm_nt(const eg_gemm_desc* d, hipStream_t s) {
 }
 
 int eg_rs_gemm_try(const eg_gemm_desc* d, hipStream_t s);   // rsgemm.hip: register-stationary row-stream kernel (K == 256)
-int eg_wide_gemm_try(const eg_gemm_desc* d, hipStream_t s); // widegemm.hip: 160x256 tile, LDS-DMA ring (N == 256)
+int eg_wide_gemm_try(const eg_gemm_desc* d, hipStream_t s); // widegemm.hip: 160x256 or 128x256 tile, LDS-DMA ring (N == 256)
 
 bool eg_rs_gemm_ok(const eg_gemm_desc* d);
 bool eg_wide_gemm_ok(const eg_gemm_desc* d);
+int eg_wide_gemm_kind(const eg_gemm_desc* d);                                        // epilogue steps + activation of a product
+bool eg_wide_gemm_batch_ok(const eg_gemm_desc* descs, int n);
+int eg_wide_gemm_batch_try(const eg_gemm_desc* descs, int n, hipStream_t s);       // widegemm.hip: n products as one grid
 static int gemm_knob(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 1; }
 
 // which kernel eg_gemm_nt launches for this descriptor (measurement aid: bench.py attributes its per-launch timings with it)
@@ -868,7 +871,8 @@ extern "C" int eg_gemm_nt_route(const eg_gemm_desc* d) {
   return EG_ROUTE_TILED;
 }
 
-extern "C" int eg_gemm_nt(const eg_gemm_desc* d, void* stream) {
+// argument checks of eg_gemm_nt / eg_gemm_nt_batch: host only, before any launch
+static int gemm_nt_check(const eg_gemm_desc* d) {
   EG_CHECK(d && d->A && d->W && d->C, "eg_gemm_nt: null operand");
   EG_CHECK(d->M > 0 && d->N > 0 && d->K > 0, "eg_gemm_nt: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
   EG_CHECK(d->dtype == EG_F32 || d->dtype == EG_BF16 || d->dtype == EG_F16, "eg_gemm_nt: bad dtype %d", d->dtype);
@@ -887,9 +891,14 @@ extern "C" int eg_gemm_nt(const eg_gemm_desc* d, void* stream) {
   EG_CHECK(d->drop1_p >= 0.f && d->drop1_p < 1.f && d->drop2_p >= 0.f && d->drop2_p < 1.f, "eg_gemm_nt: dropout p");
   EG_CHECK((long long)d->M * d->N < (1ll << 32), "eg_gemm_nt: M*N exceeds the 32-bit dropout index");
   EG_CHECK(((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C) % 16 == 0, "eg_gemm_nt: operands must be 16-B aligned");
+  return 0;
+}
+
+extern "C" int eg_gemm_nt(const eg_gemm_desc* d, void* stream) {
+  if (const int rc = gemm_nt_check(d)) return rc;
   hipStream_t s = (hipStream_t)stream;
   static const int use_rs = gemm_knob("EYEGAZE_RS"), use_wide = gemm_knob("EYEGAZE_WIDE");
-  if (use_wide) {                                  // N == 256 (any K): one workgroup per 160 whole rows
+  if (use_wide) {                                  // N == 256 (any K): one workgroup per 160 or 128 whole rows
     const int rc = eg_wide_gemm_try(d, s);
     if (rc == 0) return 0;
     if (rc != -1) return eg_fail("wide gemm launch failed");
@@ -900,6 +909,38 @@ extern "C" int eg_gemm_nt(const eg_gemm_desc* d, void* stream) {
     if (rc != -1) return eg_fail("rs_gemm launch failed");
   }
   return d->dtype == EG_BF16 ? launch_gemm_nt<bf16_t>(d, s) : d->dtype == EG_F16 ? launch_gemm_nt<f16_t>(d, s) : launch_gemm_nt<float>(d, s);
+}
+
+static int gemm_nt_batch_check(const eg_gemm_desc* descs, int n) {
+  EG_CHECK(descs, "eg_gemm_nt_batch: null descriptors");
+  EG_CHECK(n >= 1 && n <= EG_GEMM_BATCH_MAX, "eg_gemm_nt_batch: n=%d is outside [1, %d]", n, EG_GEMM_BATCH_MAX);
+  for (int i = 0; i < n; ++i) {
+    if (const int rc = gemm_nt_check(descs + i)) return rc;
+    EG_CHECK(descs[i].dtype == descs[0].dtype, "eg_gemm_nt_batch: product %d has dtype %d, product 0 has %d", i, descs[i].dtype,
+             descs[0].dtype);
+    EG_CHECK(eg_wide_gemm_kind(descs + i) == eg_wide_gemm_kind(descs), "eg_gemm_nt_batch: product %d differs from product 0 in its epilogue", i);
+  }
+  return 0;
+}
+
+// 1: eg_gemm_nt_batch runs the products as ONE wide-tile grid; 0: as n eg_gemm_nt launches; -1: it refuses them
+extern "C" int eg_gemm_nt_batch_route(const eg_gemm_desc* descs, int n) {
+  if (gemm_nt_batch_check(descs, n)) return -1;
+  static const int use_wide = gemm_knob("EYEGAZE_WIDE");
+  return use_wide && eg_wide_gemm_batch_ok(descs, n) ? 1 : 0;
+}
+
+extern "C" int eg_gemm_nt_batch(const eg_gemm_desc* descs, int n, void* stream) {
+  if (const int rc = gemm_nt_batch_check(descs, n)) return rc;
+  static const int use_wide = gemm_knob("EYEGAZE_WIDE");
+  if (use_wide) {
+    const int rc = eg_wide_gemm_batch_try(descs, n, (hipStream_t)stream);
+    if (rc == 0) return 0;
+    if (rc != -1) return eg_fail("wide gemm batch launch failed");
+  }
+  for (int i = 0; i < n; ++i)
+    if (const int rc = eg_gemm_nt(descs + i, stream)) return rc;
+  return 0;
 }
 
 template <typename T>

@@ -11,16 +11,23 @@
 //   reads (conflict-free ds_read_b128).  Epilogue: accumulators -> wave-private fp32 LDS image (in the drained ring) -> whole
 //   128-B row segments with bias / activation / gate / dropout / second output / residual, exactly gemm_nt_kernel's order.
 // Arithmetic is the same k-ordered MFMA chain as gemm_nt_kernel (bit-identical results).
+//
+// The row count is a template parameter: 160 as above, or 128 (row halves of 64, 4 x 4 accumulator tiles per wave, a 16 KB A
+// stage: 48 KB per K step instead of 52).  wide_pick_rows chooses on the host, from M and the CU count, the tile with fewer
+// resident rounds and, on a tie, fewer staged bytes per CU: M = 32 768 is ONE round of 256 workgroups on the 128-row tile
+// (205 on 160 rows, with more bytes each), M = 33 280 stays on 160 rows (208 workgroups; 260 would be two rounds).
+// gemm_nt_wide_batch_kernel runs up to EG_GEMM_BATCH_MAX such products (own operands, row maps, M and K) as ONE grid: a
+// workgroup finds its product and row tile from the prefix table in the kernel arguments.
 #include "common.h"
 #include <stdlib.h>
 
 namespace {
 
-constexpr int WBM = 160, WBN = 256;
-constexpr int WST_A = WBM * 128, WST_W = WBN * 128, WSTAGE = WST_A + WST_W;   // 20 KB + 32 KB per stage
+constexpr int WBN = 256;
+constexpr int WST_W = WBN * 128;                                             // 32 KB of W per stage
 constexpr int WNST = 3;
-constexpr int WLDS = WNST * WSTAGE;                                         // 159,744 B
 constexpr int WTP = 68;                                                      // fp32 image pitch (floats): 64 + 4
+constexpr int wide_lds(int BM) { return WNST * (BM * 128 + WST_W); }         // 160 rows: 159,744 B; 128 rows: 147,456 B
 
 template <typename T>
 struct WideNT {
@@ -44,44 +51,50 @@ __device__ __forceinline__ float wide_act(float v) {
   return v;
 }
 
-template <typename T, int ACT>
-__global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
+// one BM x 256 output tile starting at row m0 of product p
+template <typename T, int ACT, int BM>
+__device__ __forceinline__ void wide_tile(const WideNT<T>& args, const int m0, char* smem) {
   typedef typename H16<T>::frag frag;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const WideNT<T> p = args;                                    // by value: the stores below cannot alias it
+  static_assert(BM == 160 || BM == 128, "row halves of 80 or 64");
+  constexpr int WST_A = BM * 128, WSTAGE = WST_A + WST_W;      // A stage: 20 KB or 16 KB
+  constexpr int NA = BM / 8;                                   // A DMA instructions per stage: 20 or 16
+  constexpr int NAW = (NA + 7) / 8;                            // ... of one wave, at most: 3 or 2
+  constexpr int HM = BM / 2, TI = BM / 32;                     // rows and 16-row accumulator tiles of a wave: 80 / 5 or 64 / 4
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const int l15 = lane & 15, g4 = lane >> 4;
-  const int m0 = blockIdx.x * WBM;
   const int nk = p.K >> 6;
 
   // ---- DMA addressing: an instruction moves 8 rows x 128 B; lane -> row lane/8, LDS chunk position lane%8 holding global
-  //      chunk pos ^ (row & 7).  A: 20 instructions per stage (waves 0-3 issue 3, waves 4-7 issue 2); W: 32 (4 per wave). ----
+  //      chunk pos ^ (row & 7).  A: 20 instructions per stage (waves 0-3 issue 3, waves 4-7 issue 2) or 16 (2 per wave);
+  //      W: 32 (4 per wave). ----
   const int drow = lane >> 3, dpos = lane & 7;
   const int dsw = (dpos ^ drow) << 4;                        // (8q + drow) & 7 == drow
-  const char* asrc[3];
+  const char* asrc[NAW];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < NAW; ++i) {
     const int r = 8 * (wave + 8 * i) + drow;
-    asrc[i] = (const char*)(p.A + row_off(p.a, min(m0 + min(r, WBM - 1), p.M - 1))) + dsw;
+    asrc[i] = (const char*)(p.A + row_off(p.a, min(m0 + min(r, BM - 1), p.M - 1))) + dsw;
   }
   const char* wsrc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) wsrc[i] = (const char*)(p.W + (size_t)(8 * (wave + 8 * i) + drow) * (size_t)p.ldw) + dsw;
-  const int na = wave < 4 ? 3 : 2;                           // A instructions of this wave per stage
+  const int na = (NA % 8 != 0 && wave >= NA % 8) ? NAW - 1 : NAW;   // A instructions of this wave per stage
   auto issue = [&](int kt, int slot) {
     char* sa = smem + slot * WSTAGE;
     const size_t ko = (size_t)kt * 128;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NAW; ++i)
       if (i < na) wdma16(asrc[i] + ko, sa + (wave + 8 * i) * 1024);
 #pragma unroll
     for (int i = 0; i < 4; ++i) wdma16(wsrc[i] + ko, sa + WST_A + (wave + 8 * i) * 1024);
   };
 
-  f32x4 acc[5][4];
+  f32x4 acc[TI][4];
 #pragma unroll
-  for (int i = 0; i < 5; ++i)
+  for (int i = 0; i < TI; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -91,25 +104,25 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's part of stage kt has landed once at most the next stage's DMAs are outstanding
     if (kt + 1 < nk) {
-      if (wave < 4) asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      if (NA % 8 != 0 && wave < NA % 8) asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // stage kt visible; stage kt-1 no longer read by anyone
     if (kt + 2 < nk) issue(kt + 2, slot == 0 ? 2 : slot - 1);        // (kt+2) % 3 == (slot + 2) % 3
     asm volatile("" ::: "memory");
-    const char* sa = smem + slot * WSTAGE + (80 * wm + l15) * 128;
+    const char* sa = smem + slot * WSTAGE + (HM * wm + l15) * 128;
     const char* sw = smem + slot * WSTAGE + WST_A + (64 * wn + l15) * 128;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int ch = ((kk * 4 + g4) ^ (l15 & 7)) << 4;
-      frag xf[5], wf[4];
+      frag xf[TI], wf[4];
 #pragma unroll
-      for (int i = 0; i < 5; ++i) xf[i] = *(const frag*)(sa + i * 16 * 128 + ch);
+      for (int i = 0; i < TI; ++i) xf[i] = *(const frag*)(sa + i * 16 * 128 + ch);
 #pragma unroll
       for (int j = 0; j < 4; ++j) wf[j] = *(const frag*)(sw + j * 16 * 128 + ch);
 #pragma unroll
-      for (int i = 0; i < 5; ++i)
+      for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = H16<T>::mfma(wf[j], xf[i], acc[i][j]);
     }
@@ -127,15 +140,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
 #pragma unroll
   for (int j = 0; j < 16; ++j) bv[j] = 0.f;
   if (p.bias) { load8(p.bias + n, bv); load8(p.bias + n + 8, bv + 8); }
-  // the epilogue operand (residual, else gate) of all of this lane's rows is requested up front: one exposed latency, not five
+  // the epilogue operand (residual, else gate) of all of this lane's rows is requested up front: one exposed latency, not TI
   const T* const eop = p.residual ? p.residual : p.gate;
   const RowMap& emap = p.residual ? p.r : p.c;
-  u32x4 eraw[5][2];
+  u32x4 eraw[TI][2];
 #pragma unroll
-  for (int i = 0; i < 5; ++i) {
+  for (int i = 0; i < TI; ++i) {
     eraw[i][0] = (u32x4){0u, 0u, 0u, 0u};
     eraw[i][1] = (u32x4){0u, 0u, 0u, 0u};
-    const int m = m0 + 80 * wm + 16 * i + er;
+    const int m = m0 + HM * wm + 16 * i + er;
     if (eop && m < p.M) {
       const T* pe = eop + row_off(emap, m) + n;
       eraw[i][0] = *(const u32x4*)pe;
@@ -143,11 +156,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
     }
   }
 #pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const int m = m0 + 80 * wm + 16 * i + er;
+  for (int i = 0; i < TI; ++i) {
+    const int m = m0 + HM * wm + 16 * i + er;
 #pragma unroll
     for (int j = 0; j < 4; ++j) *(f32x4*)(timg + l15 * WTP + 16 * j + 4 * g4) = acc[i][j];
-    if (m0 + 80 * wm + 16 * i >= p.M) break;                 // wave-uniform: tiles wholly beyond M
+    if (m0 + HM * wm + 16 * i >= p.M) break;                 // wave-uniform: tiles wholly beyond M
     float v[16];
     load8(timg + er * WTP + 16 * ec, v);
     load8(timg + er * WTP + 16 * ec + 8, v + 8);
@@ -194,8 +207,35 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
   }
 }
 
+template <typename T, int ACT, int BM>
+__global__ __launch_bounds__(512, 2) void gemm_nt_wide_kernel(WideNT<T> p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  wide_tile<T, ACT, BM>(p, blockIdx.x * BM, smem);
+}
+
+// Several products as one grid.  Workgroups [tile_end[i-1], tile_end[i]) are the row tiles of product i, in the host's order
+// (deepest K first, so the short products fill the last round); tile t of every product covers the same rows, and where the
+// per-product tile counts are multiples of the XCD count -- the convolution phases -- it lands on the same XCD in each.
 template <typename T>
-static int wide_launch(const eg_gemm_desc* d, hipStream_t s) {
+struct WideBatch {
+  WideNT<T> prob[EG_GEMM_BATCH_MAX];
+  int tile_end[EG_GEMM_BATCH_MAX];
+  int n;
+};
+
+template <typename T, int ACT, int BM>
+__global__ __launch_bounds__(512, 2) void gemm_nt_wide_batch_kernel(WideBatch<T> b) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int blk = blockIdx.x;
+  int pi = 0, t0 = 0;
+#pragma unroll
+  for (int i = 1; i < EG_GEMM_BATCH_MAX; ++i)
+    if (i < b.n && blk >= b.tile_end[i - 1]) { pi = i; t0 = b.tile_end[i - 1]; }
+  wide_tile<T, ACT, BM>(b.prob[pi], (blk - t0) * BM, smem);
+}
+
+template <typename T>
+static WideNT<T> wide_args(const eg_gemm_desc* d) {
   WideNT<T> p;
   p.A = (const T*)d->A; p.W = (const T*)d->W; p.C = (T*)d->C; p.bias = d->bias;
   p.residual = (const T*)d->residual; p.gate = (const T*)d->gate; p.out_pre = (T*)d->out_pre; p.st = d->state;
@@ -204,21 +244,74 @@ static int wide_launch(const eg_gemm_desc* d, hipStream_t s) {
   p.d1 = make_drop(d->drop1_p, d->drop1_site);
   p.d2 = make_drop(d->drop2_p, d->drop2_site);
   p.gate_scale = d->gate_scale == 0.f ? 1.0f : d->gate_scale;
-  const dim3 grid((d->M + WBM - 1) / WBM), blk(512);
-#define WIDE_LAUNCH(A_)                                                                                                \
-  do {                                                                                                                 \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)gemm_nt_wide_kernel<T, A_>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                WLDS);                                                                                 \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((gemm_nt_wide_kernel<T, A_>), grid, blk, WLDS, s, p);                                           \
+  return p;
+}
+
+// process-wide knobs: the forced tile (0 = by rule) and the row floor below which a product keeps the 128x128 tile
+int g_force_rows = [] { const char* e = getenv("EYEGAZE_WIDE_TILE"); const int v = e ? atoi(e) : 0; return v == 128 || v == 160 ? v : 0; }();
+int g_min_rows = 1024;                         // the head products (M = batch) keep the 128x128 tile
+
+int device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return cus;
+}
+
+// fewer resident rounds first (a workgroup holds a CU: 144 KB or 156 KB of LDS), then fewer staged rows (A + W) per CU
+int wide_pick_rows(long long tiles160, long long tiles128, int cus) {
+  if (cus < 1) cus = 1;
+  const long long r160 = (tiles160 + cus - 1) / cus, r128 = (tiles128 + cus - 1) / cus;
+  if (r160 != r128) return r160 < r128 ? 160 : 128;
+  return r160 * (160 + WBN) < r128 * (128 + WBN) ? 160 : 128;
+}
+
+#define WIDE_ATTR(kern, lds)                                                                              \
+  do {                                                                                                    \
+    static bool attr = false;                                                                             \
+    if (!attr) {                                                                                          \
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);      \
+      attr = true;                                                                                        \
+    }                                                                                                     \
   } while (0)
-  if (d->act == EG_ACT_RELU) WIDE_LAUNCH(EG_ACT_RELU);
-  else if (d->act == EG_ACT_GELU) WIDE_LAUNCH(EG_ACT_GELU);
-  else WIDE_LAUNCH(EG_ACT_NONE);
-#undef WIDE_LAUNCH
+
+template <typename T, int ACT, int BM>
+static void wide_launch_one(const eg_gemm_desc* d, hipStream_t s) {
+  WIDE_ATTR((gemm_nt_wide_kernel<T, ACT, BM>), wide_lds(BM));
+  hipLaunchKernelGGL((gemm_nt_wide_kernel<T, ACT, BM>), dim3((d->M + BM - 1) / BM), dim3(512), wide_lds(BM), s, wide_args<T>(d));
+}
+
+template <typename T, int BM>
+static int wide_launch(const eg_gemm_desc* d, hipStream_t s) {
+  if (d->act == EG_ACT_RELU) wide_launch_one<T, EG_ACT_RELU, BM>(d, s);
+  else if (d->act == EG_ACT_GELU) wide_launch_one<T, EG_ACT_GELU, BM>(d, s);
+  else wide_launch_one<T, EG_ACT_NONE, BM>(d, s);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+template <typename T, int ACT, int BM>
+static void wide_launch_batch_one(const eg_gemm_desc* const* d, int n, hipStream_t s) {
+  WideBatch<T> b;
+  int end = 0;
+  for (int i = 0; i < EG_GEMM_BATCH_MAX; ++i) {
+    b.prob[i] = wide_args<T>(d[i < n ? i : 0]);
+    if (i < n) end += (d[i]->M + BM - 1) / BM;
+    b.tile_end[i] = end;
+  }
+  b.n = n;
+  WIDE_ATTR((gemm_nt_wide_batch_kernel<T, ACT, BM>), wide_lds(BM));
+  hipLaunchKernelGGL((gemm_nt_wide_batch_kernel<T, ACT, BM>), dim3(end), dim3(512), wide_lds(BM), s, b);
+}
+
+template <typename T, int BM>
+static int wide_launch_batch(const eg_gemm_desc* const* d, int n, hipStream_t s) {
+  const int act = d[0]->act;
+  if (act == EG_ACT_RELU) wide_launch_batch_one<T, EG_ACT_RELU, BM>(d, n, s);
+  else if (act == EG_ACT_GELU) wide_launch_batch_one<T, EG_ACT_GELU, BM>(d, n, s);
+  else wide_launch_batch_one<T, EG_ACT_NONE, BM>(d, n, s);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -228,7 +321,7 @@ static int wide_launch(const eg_gemm_desc* d, hipStream_t s) {
 bool eg_wide_gemm_ok(const eg_gemm_desc* d) {
   if ((d->dtype != EG_BF16 && d->dtype != EG_F16) || d->N != WBN || d->K % 64 != 0 || d->K < 128) return false;
   if (d->a_seg_len || !d->C) return false;
-  if (d->M < 1024) return false;               // the head products (M = batch) keep the 128x128 tile
+  if (d->M < g_min_rows) return false;
   // the epilogue reads residual / gate rows and writes out_pre rows as 16-B vectors: misaligned bases keep the 128x128 tile
   if (((uintptr_t)d->residual | (uintptr_t)d->gate | (uintptr_t)d->out_pre | (uintptr_t)d->C | (uintptr_t)d->A | (uintptr_t)d->W) % 16)
     return false;
@@ -237,5 +330,50 @@ bool eg_wide_gemm_ok(const eg_gemm_desc* d) {
 
 int eg_wide_gemm_try(const eg_gemm_desc* d, hipStream_t s) {
   if (!eg_wide_gemm_ok(d)) return -1;
-  return d->dtype == EG_F16 ? wide_launch<f16_t>(d, s) : wide_launch<bf16_t>(d, s);
+  const int rows = g_force_rows ? g_force_rows : eg_gemm_wide_rows(d->M, device_cus());
+  if (rows == 128) return d->dtype == EG_F16 ? wide_launch<f16_t, 128>(d, s) : wide_launch<bf16_t, 128>(d, s);
+  return d->dtype == EG_F16 ? wide_launch<f16_t, 160>(d, s) : wide_launch<bf16_t, 160>(d, s);
+}
+
+// the epilogue steps a product takes (one bit each) and its activation; the products of a batch must agree on them
+int eg_wide_gemm_kind(const eg_gemm_desc* d) {
+  return (d->bias ? 1 : 0) | (d->residual ? 2 : 0) | (d->gate ? 4 : 0) | (d->out_pre ? 8 : 0) |
+         (d->drop1_p > 0.f ? 16 : 0) | (d->drop2_p > 0.f ? 32 : 0) | (d->act << 8);
+}
+
+// every product fits this kernel and they agree on dtype and epilogue: they can run as one grid
+bool eg_wide_gemm_batch_ok(const eg_gemm_desc* descs, int n) {
+  if (n < 1 || n > EG_GEMM_BATCH_MAX) return false;
+  for (int i = 0; i < n; ++i)
+    if (!eg_wide_gemm_ok(descs + i) || descs[i].dtype != descs[0].dtype || eg_wide_gemm_kind(descs + i) != eg_wide_gemm_kind(descs))
+      return false;
+  return true;
+}
+
+// 0: launched as one grid; -1: not eligible (the caller launches the products one by one); -2: launch error
+int eg_wide_gemm_batch_try(const eg_gemm_desc* descs, int n, hipStream_t s) {
+  if (!eg_wide_gemm_batch_ok(descs, n)) return -1;
+  const eg_gemm_desc* d[EG_GEMM_BATCH_MAX];
+  for (int i = 0; i < n; ++i) d[i] = descs + i;
+  for (int i = 1; i < n; ++i)                     // stable insertion sort, deepest K first
+    for (int j = i; j > 0 && d[j]->K > d[j - 1]->K; --j) { const eg_gemm_desc* t = d[j]; d[j] = d[j - 1]; d[j - 1] = t; }
+  long long t160 = 0, t128 = 0;
+  for (int i = 0; i < n; ++i) { t160 += (d[i]->M + 159) / 160; t128 += (d[i]->M + 127) / 128; }
+  const int rows = g_force_rows ? g_force_rows : wide_pick_rows(t160, t128, device_cus());
+  if ((rows == 128 ? t128 : t160) > 0x7fffffffll) return -1;     // the tiles must fit one grid
+  if (rows == 128) return d[0]->dtype == EG_F16 ? wide_launch_batch<f16_t, 128>(d, n, s) : wide_launch_batch<bf16_t, 128>(d, n, s);
+  return d[0]->dtype == EG_F16 ? wide_launch_batch<f16_t, 160>(d, n, s) : wide_launch_batch<bf16_t, 160>(d, n, s);
+}
+
+extern "C" int eg_gemm_wide_rows(int M, int cus) {
+  if (M < 1) return 0;
+  return wide_pick_rows(((long long)M + 159) / 160, ((long long)M + 127) / 128, cus);
+}
+
+extern "C" int eg_gemm_wide_config(int tile_rows, int min_rows) {
+  EG_CHECK(tile_rows == -1 || tile_rows == 0 || tile_rows == 128 || tile_rows == 160, "eg_gemm_wide_config: tile_rows=%d", tile_rows);
+  EG_CHECK(min_rows == -1 || min_rows >= 1, "eg_gemm_wide_config: min_rows=%d", min_rows);
+  if (tile_rows >= 0) g_force_rows = tile_rows;
+  if (min_rows >= 1) g_min_rows = min_rows;
+  return 0;
 }

@@ -135,6 +135,22 @@ class FlatParams:
         return name in self.offsets
 
 
+def conv_bwd_data_phases(k: int, s: int, pad: int, T1: int):
+    """The work a strided convolution's backward-data needs, per stride phase ph: [(ph, u0, n, j0)].  Phase ph gives the input
+    gradient's padded rows t = u*s + ph from J = ceil(k/s) tap blocks, block j holding tap s*(J-1-j) + ph.  Rows u0 .. u0+n-1
+    are the ones with pad <= t < pad + T1 (the rest are padding, which no reader touches); j0 = 1 when block 0's tap lies
+    beyond the kernel (a block of zeros in the transposed weights), else 0.  Phases without a real row are left out."""
+    J = (k + s - 1) // s
+    U = (T1 + 2 * pad + s - 1) // s
+    out = []
+    for ph in range(s):
+        u0 = max(0, -((ph - pad) // s))
+        u1 = min(U - 1, (pad + T1 - 1 - ph) // s)
+        if u1 >= u0:
+            out.append((ph, u0, u1 - u0 + 1, 1 if J > 1 and s * (J - 1) + ph > k - 1 else 0))
+    return out
+
+
 class Engine:
     """Workspace + kernel sequencing for a fixed (B, T) shape."""
     LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
@@ -227,6 +243,9 @@ class Engine:
         # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
         # instead of eg_grad_sqnorm + eg_clip_coef.  Off by default: tests/test_gpu_accum.py counts the trainer's eg_grad_sqnorm calls
         self.fused_norm_clip = False
+        # conv-1 backward-data as one batched launch over the real rows and the non-zero taps (conv1_bwd_data); False, or
+        # EYEGAZE_CONV1_BWD_BATCH=0, keeps one full launch per stride phase
+        self.conv1_bwd_batch = os.environ.get("EYEGAZE_CONV1_BWD_BATCH", "1") != "0"
         self._alloc()
         self.packed_version = -1
         self._recording = False
@@ -428,6 +447,53 @@ class Engine:
         call("eg_gemm_nt", C.byref(dsc), self.stream)
         if probe:
             probe[1].record(torch.cuda.current_stream(self.device))
+
+    def gemm_batch(self, items):
+        """eg_gemm_nt_batch: the products `items` -- dicts of gemm()'s arguments, one dtype and one epilogue kind -- as ONE
+        wide-tile launch where all of them fit it, else one launch each; the bits of len(items) gemm() calls either way."""
+        keys = ("a", "c", "r", "p", "ldw", "bias", "residual", "gate", "out_pre", "act", "drop1", "drop2", "gate_scale")
+        dflt = dict(a=None, c=None, r=None, p=None, ldw=None, bias=0, residual=0, gate=0, out_pre=0, act=0, drop1=(0.0, 0),
+                    drop2=(0.0, 0), gate_scale=1.0)
+        descs = (GemmDesc * len(items))()
+        for i, it in enumerate(items):
+            descs[i] = self._gemm_desc(it["A"], it["W"], it["C"], it["M"], it["N"], it["K"], *[it.get(k, dflt[k]) for k in keys])
+        probe = None
+        if self.probe_all is not None:      # bench.py: one timed launch carrying the work of all its products
+            probe = self._probe_pair()
+            nbytes = sum(self._gemm_bytes(it["M"], it["N"], it["K"], it.get("a"), (0, 0), it.get("residual", 0), it.get("gate", 0),
+                                          it.get("out_pre", 0), it["C"]) for it in items)
+            self.probe_all.append((probe[0], probe[1], sum(2.0 * it["M"] * it["N"] * it["K"] for it in items), nbytes,
+                                   (sum(it["M"] for it in items), items[0]["N"], max(it["K"] for it in items)),
+                                   L.lib().eg_gemm_nt_route(C.byref(descs[0]))))
+            probe[0].record(torch.cuda.current_stream(self.device))
+        call("eg_gemm_nt_batch", descs, len(items), self.stream)
+        if probe:
+            probe[1].record(torch.cuda.current_stream(self.device))
+
+    def conv1_bwd_data(self, sc01, batch=None):
+        """dh0 = conv-1's backward-data (gated by h0 > 0, scaled by sc01): stride phase ph gives rows t = u*s + ph of dh0pad
+        from J taps of dy1pad.
+        batch (default self.conv1_bwd_batch): the phases as ONE eg_gemm_nt_batch call that skips what the result does not
+        need -- the leading tap block of a phase whose tap s*(J-1) + ph lies beyond the kernel (zeros in conv1T) and the rows
+        that fall into dh0pad's pads, which nothing reads (conv-0's weight gradient starts at row `pad`; the buffer is zeroed
+        once, at allocation).  False: one full launch per phase.  The real rows of dh0 are the same bits either way."""
+        d, es, s, J, g, a, w = self.cfg.d_model, self.es, self.s, self.J, self.g, self.a, self.w
+        NB = self.NB
+        if not (self.conv1_bwd_batch if batch is None else batch):
+            for ph in range(s):
+                self.gemm(ptr(g["dy1pad"]), ptr(w["conv1T"]) + ph * d * J * d * es, ptr(g["dh0pad"]) + ph * d * es,
+                          NB * self.U, d, J * d, a=rowmap(d, self.RY * d, self.U), c=rowmap(s * d, self.R0 * d, self.U),
+                          gate=ptr(a["h0pad"]) + ph * d * es, gate_scale=sc01)
+            return
+        items = []
+        for ph, u0, n, j0 in conv_bwd_data_phases(self.k, s, self.pad, self.T1):
+            row = (u0 * s + ph) * d * es
+            items.append(dict(A=ptr(g["dy1pad"]) + (u0 + j0) * d * es, W=ptr(w["conv1T"]) + (ph * d * J * d + j0 * d) * es,
+                              C=ptr(g["dh0pad"]) + row, M=NB * n, N=d, K=(J - j0) * d, ldw=J * d,
+                              a=rowmap(d, self.RY * d, n), c=rowmap(s * d, self.R0 * d, n),
+                              gate=ptr(a["h0pad"]) + row, gate_scale=sc01))
+        for i in range(0, len(items), L.GEMM_BATCH_MAX):
+            self.gemm_batch(items[i:i + L.GEMM_BATCH_MAX])
 
     def qkv_proj(self, x, l):
         """q|k|v = x W^T + b (A:203-205), fused over the three projections (the row-stream GEMM at K = 256)"""
@@ -1242,10 +1308,7 @@ class Engine:
                    x=rowmap(self.s * d, self.R0 * d, self.T2), out_b=fp.g_ptr("temporal_conv.convs.1.bias"),
                    conv=(d, self.k, d))
         seg("conv1")            # 6.5 MB of the front end's 7 MB: reduces under the backward-data phases and conv-0's gradient
-        for ph in range(self.s):
-            self.gemm(ptr(g["dy1pad"]), ptr(w["conv1T"]) + ph * d * self.J * d * es, ptr(g["dh0pad"]) + ph * d * es,
-                      NB * self.U, d, self.J * d, a=rowmap(d, self.RY * d, self.U), c=rowmap(self.s * d, self.R0 * d, self.U),
-                      gate=ptr(a["h0pad"]) + ph * d * es, gate_scale=sc01)
+        self.conv1_bwd_data(sc01)
         h0map = rowmap(d, self.R0 * d, self.T1)
         self.wgrad(ptr(g["dh0pad"]) + self.pad * d * es, ptr(a["xt"]), fp.g_ptr("temporal_conv.convs.0.weight"),
                    NB * self.T1, d, self.K0, y=h0map, x=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1),

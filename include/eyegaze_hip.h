@@ -167,6 +167,21 @@ int eg_gemm_nt(const eg_gemm_desc* d, void* stream);
  * EG_ROUTE_ROWSTREAM rs_gemm_kernel (K == 256, register-stationary weights). */
 enum { EG_ROUTE_TILED = 0, EG_ROUTE_WIDE = 1, EG_ROUTE_ROWSTREAM = 2 };
 int eg_gemm_nt_route(const eg_gemm_desc* d);
+/* The wide kernel's row tile: 160 or 128 rows x 256 columns.  eg_gemm_wide_rows is the host rule for an M-row product on
+ * `cus` compute units (one workgroup per CU at a time): the tile with fewer resident rounds, on a tie the one that stages
+ * fewer bytes per CU.  EYEGAZE_WIDE_TILE=128|160 forces a tile for the process; eg_gemm_wide_config does the same at run time
+ * (tile_rows 0 = by rule) and sets the row count below which a product keeps the 128x128 tile (default 1024); -1 leaves a
+ * setting as it is.  Every tile gives the same bits. */
+int eg_gemm_wide_rows(int M, int cus);
+int eg_gemm_wide_config(int tile_rows, int min_rows);
+/* eg_gemm_nt_batch — n <= EG_GEMM_BATCH_MAX products of one dtype and one epilogue kind (the same activation and the same
+ * set of bias / gate / dropout / out_pre / residual steps), each with its own operands, row maps, M and K.  Where every
+ * product fits the wide kernel (N == 256, 16-bit, see eg_gemm_nt_route) they run as ONE grid, deepest K first; otherwise as n
+ * eg_gemm_nt launches.  The results are those of n eg_gemm_nt calls, bit for bit.  All checks are made before any launch.
+ * eg_gemm_nt_batch_route: 1 = one grid, 0 = n launches, -1 = refused (eg_last_error says why); no launch. */
+#define EG_GEMM_BATCH_MAX 8
+int eg_gemm_nt_batch(const eg_gemm_desc* descs, int n, void* stream);
+int eg_gemm_nt_batch_route(const eg_gemm_desc* descs, int n);
 
 /* ---------------------------------------------------------------------------------------------
  * eg_ffn_chain — the two products of the position-wise feed-forward block (A:264-272) in one launch, d_model == 256:
