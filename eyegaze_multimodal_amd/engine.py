@@ -13,13 +13,13 @@ Data layout in HBM (NB = 2B windows: stream 1 = samples [0,B), stream 2 = [B,2B)
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib as L
+from . import wgrad_plan
 from ._lib import EG_BF16, EG_F16, EG_F32, GemmDesc, GemmTNDesc, StepState, call, ptr, rowmap
 
 # dropout site ids (any fixed numbering works: the mask depends on (seed, site, element index))
@@ -35,10 +35,7 @@ def scramble_seed(seed: int) -> int:
     return z ^ (z >> 31)
 
 
-def _reduce_blocks(n: int, splits: int) -> int:
-    """workgroups eg_reduce_table spends on one entry (include/eyegaze_hip.h: EG_REDUCE_WIDE_SPLITS = 8)"""
-    cols = n // 4
-    return (cols + 255) // 256 if splits <= 8 else (cols + 7) // 8
+_reduce_blocks = wgrad_plan.reduce_blocks
 
 
 def _layer_sites(l: int):
@@ -151,25 +148,334 @@ def conv_bwd_data_phases(k: int, s: int, pad: int, T1: int):
     return out
 
 
-class Engine:
-    """Workspace + kernel sequencing for a fixed (B, T) shape."""
-    LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
-    SQ_BLOCKS = 1024              # squared-norm partials of the flat gradient buffer (g["sqpart"]) that eg_clip_coef sums
+class EngineBase:
+    """What every step engine is built on: device / dtype fields, the step state, timed launches, the GEMM and weight-gradient
+    wrappers, the table-driven parameter staging.  A subclass allocates a, w, g, defines _pack_body and ends with _init_state."""
+    tn_cap = 0      # floats of g["partial"], the split-K partials of wgrad (a subclass sizes it)
 
-    def __init__(self, model, B: int, T: int, device: torch.device, dtype: int, state_dev: Optional[torch.Tensor] = None):
-        """state_dev: the model's shared eg_step_state.  Every engine of one model (one per batch shape: the ragged tail batch
-        of an epoch gets its own workspace) must step ONE optimiser count, ONE loss scale and ONE overflow history; an engine
-        given no state creates (and initialises) its own."""
-        cfg = model.cfg
-        self._shared_state = state_dev
-        self.model, self.cfg, self.B, self.T, self.device, self.dtype = model, cfg, B, T, device, dtype
+    def __init__(self, model, B: int, device, dtype: int):
+        device = torch.device(device)
+        self.model, self.B, self.device, self.dtype = model, B, device, dtype
         self.tdtype = {EG_BF16: torch.bfloat16, EG_F16: torch.float16, EG_F32: torch.float32}[dtype]
         self.es = 4 if dtype == EG_F32 else 2
         self.bk = 32 if dtype == EG_F32 else 64
+        self.fp: FlatParams = model._flat
+        self.stream = 0
+        self.cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
+        self.a, self.w, self.g = {}, {}, {}     # activations, packed weights, backward temporaries (allocated on the first backward)
+        self.probes = {}        # tag -> (start_event, end_event) recorded around that launch
+        self.probe_all = None   # list of (start, end, flops, bytes, shape, route) of every timed launch when bench.py enables it
+        self.probe_pool = None  # bench.py's pre-created event pairs (see _probe_pair)
         # fp16 has 5 exponent bits: gradients are carried at loss_scale x their value (torch.cuda.amp.GradScaler semantics,
         # train_multimodal_fuzzy_fusion.py:435-472); the scale, the overflow flag and the step counter live in eg_step_state
-        self.scaler_on = dtype == EG_F16 and os.environ.get("EYEGAZE_LOSS_SCALING", "1") != "0"
+        self.scaler_on = False
         self.scaler_cfg = dict(init_scale=65536.0, growth=2.0, backoff=0.5, growth_interval=2000)
+        # the recorded pack table (pack_params)
+        self._recording, self._plan, self._plan_ex = False, [], False
+        self._plan_key, self._plan_dev, self._plan_n, self._plan_blocks = None, None, 0, 0
+        # the routes pack_params keys its table on.  Off here: an engine that has them resolves them (Engine._resolve_routes)
+        self.fused_tail = self.pack_unused = False
+        self.fuse_ffn = self.attn_block = self.ln_proj = False
+
+    def _init_state(self, state_dev: Optional[torch.Tensor]):
+        """state_dev: a shared eg_step_state, initialised once by whoever created it (DualEEGTransformer._state_for).  Every engine
+        of one model (one per batch shape: the ragged tail batch of an epoch gets its own workspace) must step ONE optimiser
+        count, ONE loss scale and ONE overflow history; an engine given no state creates (and initialises) its own."""
+        if state_dev is not None:
+            self.state_dev = state_dev
+        else:
+            self.state_dev = torch.zeros(L.STATE_WORDS, dtype=torch.int32, device=self.device)
+            self.set_state(seed=0, lr=0.0, step=1, grad_scale=1.0, reset_scaler=(1 if self.scaler_on else 2),
+                           init_scale=self.scaler_cfg["init_scale"])
+
+    def _t(self, *shape, dtype=None):
+        return torch.zeros(*shape, device=self.device, dtype=dtype or self.tdtype)
+
+    def _cur_stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+
+    # ------------------------------------------------------------------------------------------
+    # step state
+    # ------------------------------------------------------------------------------------------
+    def set_state(self, seed: int, lr: float, step: int, grad_scale: float = 1.0, beta1=0.9, beta2=0.999,
+                  reset_scaler: int = 0, init_scale: float = 65536.0, use_dev_t: bool = False):
+        """Publishes this step's host scalars.  They travel as kernel ARGUMENTS of a one-thread launch on the current
+        stream (eg_set_step_state), so the host may run any number of steps ahead: a queued step can never observe a later
+        step's seed / lr / bias corrections (a pinned staging buffer re-used per step could be overwritten before its copy ran).
+        reset_scaler: 0 keep the device's loss-scaling words, 1 enable dynamic loss scaling at init_scale, 2 disable."""
+        seed = scramble_seed(seed)     # consecutive step seeds must not share their low / high words (common.h: eg_hash)
+        # with loss scaling a step may be skipped on the device: the device's own count of taken steps feeds the bias corrections
+        use_dev_t = bool(use_dev_t) or self.scaler_on
+        call("eg_set_step_state", self.state_dev.data_ptr(), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, float(lr),
+             1.0 - beta1 ** step, 1.0 - beta2 ** step, float(grad_scale), int(reset_scaler), float(init_scale),
+             int(use_dev_t), self._cur_stream())
+
+    def reset_scaler(self, init_scale: float = 65536.0, growth: float = 2.0, backoff: float = 0.5, growth_interval: int = 2000):
+        """(re)starts dynamic loss scaling with GradScaler's parameters (fp16 engines only)"""
+        self.scaler_cfg = dict(init_scale=init_scale, growth=growth, backoff=backoff, growth_interval=growth_interval)
+        self.scaler_on = True
+        self.set_state(seed=0, lr=0.0, step=1, reset_scaler=1, init_scale=init_scale)
+
+    @property
+    def loss_scale_dev(self) -> torch.Tensor:
+        """the device-resident loss scale as a 1-element fp32 view of eg_step_state (word 8)"""
+        return self.state_dev.view(torch.float32)[8:9]
+
+    def read_state(self) -> StepState:
+        host = self.state_dev.cpu()
+        st = StepState()
+        C.memmove(C.addressof(st), host.data_ptr(), C.sizeof(st))
+        return st
+
+    @property
+    def st_ptr(self) -> int:
+        return self.state_dev.data_ptr()
+
+    # ------------------------------------------------------------------------------------------
+    # thin wrappers
+    # ------------------------------------------------------------------------------------------
+    def gemm(self, A, W, Cout, M, N, K, *, a=None, c=None, r=None, p=None, ldw=None, bias=0, residual=0, gate=0,
+             out_pre=0, act=0, drop1=(0.0, 0), drop2=(0.0, 0), gate_scale=1.0, tag=None, seg=(0, 0)):
+        dsc = self._gemm_desc(A, W, Cout, M, N, K, a, c, r, p, ldw, bias, residual, gate, out_pre, act, drop1, drop2,
+                              gate_scale, seg)
+        probe = self._timed(lambda: (2.0 * M * N * K, self._gemm_bytes(M, N, K, a, seg, residual, gate, out_pre, Cout),
+                                     (M, N, K), L.lib().eg_gemm_nt_route(C.byref(dsc))), tag)
+        call("eg_gemm_nt", C.byref(dsc), self.stream)
+        self._timed_end(probe)
+
+    def gemm_batch(self, items):
+        """eg_gemm_nt_batch: the products `items` -- dicts of gemm()'s arguments, one dtype and one epilogue kind -- as ONE
+        wide-tile launch where all of them fit it, else one launch each; the bits of len(items) gemm() calls either way."""
+        dflt = dict(a=None, c=None, r=None, p=None, ldw=None, bias=0, residual=0, gate=0, out_pre=0, act=0, drop1=(0.0, 0),
+                    drop2=(0.0, 0), gate_scale=1.0)
+        descs = (GemmDesc * len(items))()
+        for i, it in enumerate(items):
+            descs[i] = self._gemm_desc(it["A"], it["W"], it["C"], it["M"], it["N"], it["K"], *[it.get(k, v) for k, v in dflt.items()])
+
+        def work():                         # bench.py: one timed launch carrying the work of all its products
+            nbytes = sum(self._gemm_bytes(it["M"], it["N"], it["K"], it.get("a"), (0, 0), it.get("residual", 0), it.get("gate", 0),
+                                          it.get("out_pre", 0), it["C"]) for it in items)
+            return (sum(2.0 * it["M"] * it["N"] * it["K"] for it in items), nbytes,
+                    (sum(it["M"] for it in items), items[0]["N"], max(it["K"] for it in items)),
+                    L.lib().eg_gemm_nt_route(C.byref(descs[0])))
+        probe = self._timed(work)
+        call("eg_gemm_nt_batch", descs, len(items), self.stream)
+        self._timed_end(probe)
+
+    def _probe_pair(self):
+        """A (start, end) event pair for a timed launch: from bench.py's pre-created pool when there is one -- creating a
+        hipEvent costs the host far more than recording one, and fresh events inside the timed region made short runs host-bound."""
+        if self.probe_pool:
+            return self.probe_pool.pop()
+        return (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+
+    def _timed(self, work, tag=None):
+        """Before a launch that bench.py times (_timed_end follows it): with probe_all a list, HIP events go around EVERY such
+        launch and work() -- (flops, algorithmic HBM bytes, shape, route) -- is appended behind them; else `tag` may name a pair."""
+        probe = self.probes.get(tag) if tag else None
+        if self.probe_all is not None:
+            probe = self._probe_pair()
+            self.probe_all.append((probe[0], probe[1], *work()))
+        if probe:
+            probe[0].record(torch.cuda.current_stream(self.device))
+        return probe
+
+    def _timed_end(self, probe):
+        if probe:
+            probe[1].record(torch.cuda.current_stream(self.device))
+
+    def _gemm_bytes(self, M, N, K, a, seg, residual, gate, out_pre, Cout=1) -> float:
+        """Algorithmic HBM bytes of one gemm_nt launch: every distinct operand element read once, every output element
+        written once (overlapping conv rows count once; the weights count once)."""
+        es = self.es
+        if a is not None and a.rows_per_group > 0 and not seg[0]:
+            groups = M // a.rows_per_group
+            a_elems = groups * ((a.rows_per_group - 1) * min(a.row_stride, K) + K)
+        elif seg[0]:                       # segmented rows (spectrogram conv): K elements per row drawn from K/seg_len runs
+            a_elems = M * K if a is None else min(M * K, M * max(a.row_stride, 1) + K)
+        else:
+            a_elems = M * K
+        outs = (1 if Cout else 0) + (1 if out_pre else 0)
+        ins = (1 if residual else 0) + (1 if gate else 0)
+        return float(es * (a_elems + N * K + (outs + ins) * M * N) + 4 * N)
+
+    def _gemm_desc(self, A, W, Cout, M, N, K, a, c, r, p, ldw, bias, residual, gate, out_pre, act, drop1, drop2, gate_scale,
+                   seg=(0, 0)):
+        dsc = GemmDesc()
+        dsc.a_seg_len, dsc.a_seg_stride = seg
+        dsc.A, dsc.W, dsc.C = A, W, Cout or None
+        dsc.bias, dsc.residual, dsc.gate, dsc.out_pre = bias or None, residual or None, gate or None, out_pre or None
+        dsc.state = self.st_ptr
+        dsc.a = a or rowmap(K)
+        dsc.c = c or rowmap(N)
+        dsc.r = r or dsc.c
+        dsc.p = p or dsc.c
+        dsc.M, dsc.N, dsc.K, dsc.ldw = M, N, K, ldw or K
+        dsc.act, dsc.dtype = act, self.dtype
+        dsc.drop1_p, dsc.drop1_site = drop1
+        dsc.drop2_p, dsc.drop2_site = drop2
+        dsc.gate_scale = gate_scale
+        return dsc
+
+    def _packed(self, names, N, K) -> bool:
+        """`name.weight` / `name.bias` of the product [N, K] back to back in the flat buffers (wgrad_plan.packed)"""
+        return wgrad_plan.packed(self.fp.offsets, names, N, K)
+
+    def wgrad(self, dY, X, out_w, M, N, K, *, y=None, x=None, out_b=0, conv=None, split_out=None, x_tile_stride=0,
+              conv2d=None, linear=None):
+        """dW = dY^T X (+ db = colsum dY).
+        linear=[prefix, ...]: the product feeds N/len(linear) rows to each `prefix.weight` / `prefix.bias`; when those
+        parameters are laid out back to back in the flat buffer (they are: registration order) the bias sums are fused
+        into the GEMM launch and ONE reduce writes every weight and bias gradient.
+        conv / conv2d: tap-major partials are un-permuted into the parameter layout; out_b via a column-sum launch."""
+        tiles = ((N + 127) // 128) * ((K + 127) // 128)
+        fused = linear is not None and (N // len(linear)) % 4 == 0 and self._packed(linear, N, K)
+        slab = N * K + (N if fused else 0)
+        # one resident round: 256 CUs x 3 workgroups; rounding the split count UP would leave a nearly empty second round
+        splits = max(1, min((M + 127) // 128, max(1, 768 // tiles), self.tn_cap // slab))
+        # big products on 16-bit operands: 256 x 256 tiles, one 512-thread workgroup per CU (conv-1: 25 tiles x 10 row splits)
+        big = self.dtype != EG_F32 and N % 256 == 0 and K % 256 == 0 and not x_tile_stride and M * N * K >= (1 << 34)
+        if big:
+            t256 = (N // 256) * (K // 256)
+            splits = max(1, min((M + 63) // 64, max(1, self.cus // t256), self.tn_cap // slab))
+        dsc = GemmTNDesc()
+        dsc.tile = 256 if big else 128
+        dsc.dY, dsc.X, dsc.partial = dY, X, ptr(self.g["partial"])
+        dsc.y = y or rowmap(N)
+        dsc.x = x or rowmap(K)
+        dsc.M, dsc.N, dsc.K, dsc.splits, dsc.dtype = M, N, K, splits, self.dtype
+        dsc.x_tile_stride = x_tile_stride
+        if fused:
+            dsc.part_rows, dsc.has_bias = N // len(linear), 1
+        call("eg_gemm_tn", C.byref(dsc), self.stream)
+        pp = ptr(self.g["partial"])
+        if fused:
+            call("eg_reduce_partials", pp, self.fp.g_ptr(linear[0] + ".weight"), slab, splits, slab, 0, self.stream)
+            return
+        if linear is not None:  # non-contiguous parameters: per-parameter reduces + a column-sum launch
+            P = N // len(linear)
+            split_out = [(self.fp.g_ptr(n + ".weight"), i * P, P) for i, n in enumerate(linear)]
+            out_b = [(self.fp.g_ptr(n + ".bias"), i * P, P) for i, n in enumerate(linear)]
+        if conv2d is not None:
+            call("eg_unpack_conv2d_wgrad", pp, out_w, splits, conv2d[0], conv2d[1], self.stream)
+        elif conv is not None:
+            cin, kk, cp = conv
+            call("eg_unpack_conv_wgrad", pp, out_w, splits, N, cin, kk, cp, K, self.stream)
+        elif split_out is not None:
+            for gp, row0, rows in split_out:
+                call("eg_reduce_partials", pp + 4 * row0 * K, gp, rows * K, splits, N * K, 0, self.stream)
+        else:
+            call("eg_reduce_partials", pp, out_w, N * K, splits, N * K, 0, self.stream)
+        if out_b:
+            nblk = min(512, (M + 63) // 64)
+            call("eg_colsum", dY, dsc.y, M, N, ptr(self.g["cspart"]), nblk, self.dtype, self.stream)
+            if isinstance(out_b, (list, tuple)):
+                for gp, col0, cols in out_b:
+                    call("eg_reduce_partials", ptr(self.g["cspart"]) + 4 * col0, gp, cols, nblk, N, 0, self.stream)
+            else:
+                call("eg_reduce_partials", ptr(self.g["cspart"]), out_b, N, nblk, N, 0, self.stream)
+
+    # ------------------------------------------------------------------------------------------
+    # parameter staging
+    # ------------------------------------------------------------------------------------------
+    # table-driven staging: cast / transpose entries are recorded once and replayed as ONE launch per step
+    def p_cast(self, src, dst, n):
+        if self._recording:
+            self._plan.append((src, dst, 1, n, 0, 0))
+
+    def p_copy(self, src, dst, n):
+        if self._recording:
+            self._plan.append((src, dst, 1, n, 0, 2))
+
+    def p_transpose(self, src, dst, R, Cc, ldd):
+        if self._recording:
+            self._plan.append((src, dst, R, Cc, ldd, 1))
+
+    def p_frag(self, src, dst, R, Cc, mode, part=0):
+        """fragment order of the fp32 parameter src [R, Cc]: eg_ffn_chain's (eg_pack_table modes 3-6) or eg_attn_block_fwd's
+        (mode 7 with part = 0 / 1 / 2 for q / k / v_proj, mode 8 for out_proj)."""
+        if self._recording:
+            self._plan.append((src, dst, R, Cc, part, mode))
+
+    def p_conv(self, src, dst, N, Cin, k, Cp, Kp):
+        """eg_pack_conv_weight as an entry of the pack table (fused route) or as its own launch"""
+        if self._plan_ex:
+            if self._recording:
+                self._plan.append((src, dst, N, Cin, 0, 9, k, Cp, Kp))
+        else:
+            call("eg_pack_conv_weight", src, dst, N, Cin, k, Cp, Kp, self.dtype, self.stream)
+
+    def p_convT(self, src, dst, N, Cin, k, s):
+        """eg_pack_convT_weight, likewise"""
+        if self._plan_ex:
+            if self._recording:
+                self._plan.append((src, dst, N, Cin, 0, 10, k, s, (k + s - 1) // s))
+        else:
+            call("eg_pack_convT_weight", src, dst, N, Cin, k, s, self.dtype, self.stream)
+
+    def _extent_after(self, addr: int, elsize: int) -> int:
+        """elements of size `elsize` between `addr` and the end of the engine / parameter buffer that holds it (0: not found)"""
+        bufs = list(self.w.values()) + [self.fp.flat]
+        for t in bufs:
+            lo = t.data_ptr()
+            hi = lo + t.numel() * t.element_size()
+            if lo <= addr < hi:
+                return (hi - addr) // elsize
+        return 0
+
+    def pack_params(self):
+        ex = bool(self.fused_tail)          # eg_pack_table_ex carries the convolution layouts too; the image engine keeps eg_pack_table
+        # the routing flags decide which layouts _pack_body records, so a flag flipped on a live engine re-records the plan
+        key = (self.fp.flat.data_ptr(), ex, bool(self.pack_unused), self.fuse_ffn, self.attn_block, self.ln_proj)
+        self._plan_ex = ex
+        if self._plan_key != key:
+            self._plan, self._recording = [], True
+            self._pack_body()
+            self._recording = False
+            ents = ((L.PackEntryEx if ex else L.PackEntry) * len(self._plan))()
+            blk = 0
+            for e, ent in zip(ents, self._plan):
+                src, dst, R, Cc, ldd, mode = ent[:6]
+                if mode == 9:
+                    nb = (R * ent[8] + 1023) // 1024
+                elif mode == 10:
+                    nb = (ent[7] * Cc * ent[8] * R + 1023) // 1024
+                else:
+                    nb = (((R + 31) // 32) * ((Cc + 31) // 32) if mode == 1 else (R * Cc) // 2048 if mode >= 3 else
+                          (R * Cc + 1023) // 1024)
+                e.src, e.dst, e.rows, e.cols, e.ldd, e.mode, e.blk0, e.nblk = src, dst, R, Cc, ldd, mode, blk, nb
+                if ex:
+                    if mode >= 9:
+                        e.p0, e.p1, e.p2 = ent[6:9]
+                    e.src_elems = self._extent_after(src, 4)
+                    e.dst_elems = self._extent_after(dst, 4 if mode == 2 else self.es)
+                blk += nb
+            if ex:      # host-side audit of every entry (block ranges, shapes, alignment, extents) before the table is ever launched
+                total = C.c_int(0)
+                call("eg_pack_table_ex_check", C.cast(ents, C.c_void_p), len(self._plan), self.dtype, C.byref(total))
+                if total.value != blk:
+                    raise L.EgError(f"pack table: {total.value} blocks audited, {blk} planned")
+            raw = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8)
+            self._plan_dev = raw.to(self.device)
+            self._plan_n, self._plan_blocks, self._plan_key = len(self._plan), blk, key
+        else:
+            self._pack_body()
+        call("eg_pack_table_ex" if ex else "eg_pack_table", ptr(self._plan_dev), self._plan_n, self._plan_blocks, self.dtype,
+             self.stream)
+
+
+class Engine(EngineBase):
+    """Workspace + kernel sequencing for a fixed (B, T) shape."""
+    LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
+    SQ_BLOCKS = 1024              # squared-norm partials of the flat gradient buffer (g["sqpart"]) that eg_clip_coef sums
+    GROUP_MIN_ROWS = 4096         # token rows below which the per-product weight-gradient launches (many splits) are the better shape
+    tn_cap = 24 * 1024 * 1024     # floats (96 MB) of TN split-K partials: sized for the largest product (conv-1 weights / FFN)
+
+    def __init__(self, model, B: int, T: int, device: torch.device, dtype: int, state_dev: Optional[torch.Tensor] = None):
+        """state_dev: the model's shared eg_step_state (see _init_state)"""
+        super().__init__(model, B, device, dtype)
+        cfg = model.cfg
+        self.cfg, self.T = cfg, T
         d, H = cfg.d_model, cfg.num_heads
         if d % H != 0 or d // H != 32:
             raise L.EgError(f"HIP attention core needs d_model/num_heads == 32 (got {d}/{H})")
@@ -195,24 +501,33 @@ class Engine:
         self.n_spec = self.C if cfg.use_spectrogram else 0
         self.off = 1 + self.n_ibs + self.n_spec
         self.S = sequence_length(cfg, T)
+        self.M = self.NB * self.S
+        self._resolve_routes()
+        self._wg_key = self._wg_plan = None     # the grouped weight-gradient plan and the gradient buffer it was made for
+        self._wg_cross, self._ln_slot = False, {}
+        self._ranges_key = None
+        self._acc_norm_ready = False   # g["sqpart"] holds the norm partials of the whole accumulator (accumulate(norm=True))
+        self._alloc()
+        self._init_state(state_dev)
+
+    def _resolve_routes(self):
+        """Every route of the step, decided once from the compute dtype, the shapes and the surviving switches; nothing else in
+        this module reads the environment (but _wgrad_pieces).  Tests assign the plain attributes on a live engine."""
+        cfg, dtype, env = self.cfg, self.dtype, os.environ
+        half = dtype != EG_F32
+        self.scaler_on = dtype == EG_F16 and env.get("EYEGAZE_LOSS_SCALING", "1") != "0"
         # S > 160: the long-sequence attention core (eg_attention_long_*) at all four call sites; S <= 160 keeps the short one
         self.attn_long = self.S > ATTN_SHORT_MAX_S
-        self.M = self.NB * self.S
-        self._want_attn_block = os.environ.get("EYEGAZE_ATTN_BLOCK", "1") != "0"
-        self.fp: FlatParams = model._flat
-        self.stream = 0
-        self.probes = {}   # tag -> (start_event, end_event) recorded around that launch
-        self.cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
         # attention half of an encoder layer (q|k|v projection, attention core, out-proj + dropout + residual) as ONE launch with a
-        # workgroup per window (csrc/attnblock.hip): 16-bit compute dtypes, d_model == 256, 8 heads, S <= 80 (set after S is known)
-        self.attn_block = False
+        # workgroup per window (csrc/attnblock.hip): 16-bit compute dtypes, d_model == 256, 8 heads, S <= 80
+        self.attn_block = bool(env.get("EYEGAZE_ATTN_BLOCK", "1") != "0" and half
+                               and L.lib().eg_attn_block_ok(self.S, cfg.d_model, cfg.num_heads, dtype))
         # feed-forward pair as one launch (csrc/ffn.hip): 16-bit compute dtypes, d_model == 256, d_ff a multiple of 128
-        self.fuse_ffn = (dtype != EG_F32 and cfg.d_model == 256 and cfg.d_ff % 128 == 0
-                         and os.environ.get("EYEGAZE_FFN", "1") != "0")
+        self.fuse_ffn = half and cfg.d_model == 256 and cfg.d_ff % 128 == 0
         # LayerNorm backward: a block walks 8 rows per trip with TWO trips in flight (112 registers: four 256-thread blocks per CU).
         # All blocks must be resident at once -- a late block starts when an early one ends and doubles the launch -- so at most
         # 4 blocks per CU: 33 280 rows = 1024 blocks x 4.06 trips (round 2: 1040 x 4 with one trip in flight)
-        env_nb = os.environ.get("EYEGAZE_LN_BLOCKS")
+        env_nb = env.get("EYEGAZE_LN_BLOCKS")
         trips = max(1, self.M // 8192)
         self.LN_BLOCKS = int(env_nb) if env_nb else min(self.LN_PARTIAL_BLOCKS, 4 * self.cus,
                                                         max(1, (self.M + 8 * trips - 1) // (8 * trips)))
@@ -221,23 +536,20 @@ class Engine:
             raise L.EgError(f"EYEGAZE_LN_BLOCKS={env_nb} is outside [1, {self.LN_PARTIAL_BLOCKS}] (rows of the LayerNorm-backward "
                             "partial buffer)")
         self.ln_nblk_cap = max(self.LN_BLOCKS, (self.M + 63) // 64)
-        self.probe_all = None  # list of (start, end, flops) for every gemm_nt launch when bench.py enables it
-        self.attn_block = bool(self._want_attn_block and dtype != EG_F32
-                               and L.lib().eg_attn_block_ok(self.S, cfg.d_model, cfg.num_heads, dtype))
         # the two LayerNorms of an encoder layer as the tail of the launches that complete their input rows (eg_attn_block_fwd ->
         # norm1, eg_ffn_chain forward -> norm2) instead of two launches that re-read them; the statistics are summed in another order
         # than eg_layernorm_fwd's, so the step agrees with EYEGAZE_LN_FUSE=0 to rounding, not bit for bit
-        self.ln_fuse = os.environ.get("EYEGAZE_LN_FUSE", "1") != "0"
+        self.ln_fuse = env.get("EYEGAZE_LN_FUSE", "1") != "0"
         # norm1's backward and out_proj's backward-data product as one launch over 80-row tiles (eg_ln_bwd_proj): bit-identical to the
         # two launches (the gain / bias partials are grouped by tile instead of by LayerNorm block: equal to fp32 rounding)
-        self.ln_proj = (dtype != EG_F32 and cfg.d_model == 256 and os.environ.get("EYEGAZE_LN_PROJ", "1") != "0")
+        self.ln_proj = half and cfg.d_model == 256
         self.ln_proj_blocks = L.lib().eg_ln_bwd_proj_blocks(self.M) if self.ln_proj else 0
         # the step's small-launch tail on its fused kernels (16-bit compute dtypes): the convolution weight layouts inside the
         # one table-driven pack launch, the heads' forward as pooling + ONE chained launch, their backward as three, and the
         # position / cls / conv-1 gradient rows from ONE pass over dseq.  Same bits as the separate launches, which remain the
         # route for fp32 and for the shapes the fused kernels do not cover (see _fused_heads); tests set this attribute to
         # False to compare the two routes.
-        self.fused_tail = dtype != EG_F32
+        self.fused_tail = half
         # False: pack_params skips the layouts that the routes chosen above never read (see _pack_body); True packs every one
         self.pack_unused = False
         # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
@@ -245,16 +557,7 @@ class Engine:
         self.fused_norm_clip = False
         # conv-1 backward-data as one batched launch over the real rows and the non-zero taps (conv1_bwd_data); False, or
         # EYEGAZE_CONV1_BWD_BATCH=0, keeps one full launch per stride phase
-        self.conv1_bwd_batch = os.environ.get("EYEGAZE_CONV1_BWD_BATCH", "1") != "0"
-        self._alloc()
-        self.packed_version = -1
-        self._recording = False
-        self._plan = []
-        self._acc_norm_ready = False   # g["sqpart"] holds the norm partials of the whole accumulator (accumulate(norm=True))
-
-    # ------------------------------------------------------------------------------------------
-    def _t(self, *shape, dtype=None):
-        return torch.zeros(*shape, device=self.device, dtype=dtype or self.tdtype)
+        self.conv1_bwd_batch = env.get("EYEGAZE_CONV1_BWD_BATCH", "1") != "0"
 
     def _alloc(self):
         cfg, d, F, L_ = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_layers
@@ -337,15 +640,6 @@ class Engine:
             a["ibs_sloss"] = self._t(B, dtype=f32)
             a["ibs_loss"] = self._t(1, dtype=f32)
         self.a = a
-        # backward temporaries (allocated lazily on the first backward)
-        self.g: Dict[str, torch.Tensor] = {}
-        # device-resident step state (eg_step_state); the host publishes a step's scalars as kernel arguments
-        if self._shared_state is not None:      # initialised once, by whoever created it (DualEEGTransformer._state_for)
-            self.state_dev = self._shared_state
-        else:
-            self.state_dev = torch.zeros(L.STATE_WORDS, dtype=torch.int32, device=self.device)
-            self.set_state(seed=0, lr=0.0, step=1, grad_scale=1.0, reset_scaler=(1 if self.scaler_on else 2),
-                           init_scale=self.scaler_cfg["init_scale"])
 
     def _alloc_bwd(self):
         if self.g:
@@ -368,8 +662,6 @@ class Engine:
         g["dh0pad"] = self._t(NB, self.R0, d)
         g["possum"] = self._t(self.S, d, dtype=torch.float32)
         g["one"] = torch.ones(1, device=self.device, dtype=torch.float32)
-        # TN split-K partials: sized for the largest product (conv-1 weights / FFN)
-        self.tn_cap = 24 * 1024 * 1024  # floats (96 MB)
         g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
         g["lnpart"] = self._t(self.LN_PARTIAL_BLOCKS * 2 * max(d, 8), dtype=torch.float32)
         g["cspart"] = self._t(512 * max(3 * d, F), dtype=torch.float32)
@@ -377,98 +669,17 @@ class Engine:
             g["attn_delta"] = self._t(NB * self.cfg.num_heads * self.S, dtype=torch.float32)
         self.g = g
 
-    # ------------------------------------------------------------------------------------------
-    def set_state(self, seed: int, lr: float, step: int, grad_scale: float = 1.0, beta1=0.9, beta2=0.999,
-                  reset_scaler: int = 0, init_scale: float = 65536.0, use_dev_t: bool = False):
-        """Publishes this step's host scalars.  They travel as kernel ARGUMENTS of a one-thread launch on the current
-        stream (eg_set_step_state), so the host may run any number of steps ahead: a queued step can never observe a later
-        step's seed / lr / bias corrections (a pinned staging buffer re-used per step could be overwritten before its copy ran).
-        reset_scaler: 0 keep the device's loss-scaling words, 1 enable dynamic loss scaling at init_scale, 2 disable."""
-        seed = scramble_seed(seed)     # consecutive step seeds must not share their low / high words (common.h: eg_hash)
-        # with loss scaling a step may be skipped on the device: the device's own count of taken steps feeds the bias corrections
-        use_dev_t = bool(use_dev_t) or self.scaler_on
-        call("eg_set_step_state", self.state_dev.data_ptr(), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, float(lr),
-             1.0 - beta1 ** step, 1.0 - beta2 ** step, float(grad_scale), int(reset_scaler), float(init_scale),
-             int(use_dev_t), self._cur_stream())
-
-    def reset_scaler(self, init_scale: float = 65536.0, growth: float = 2.0, backoff: float = 0.5, growth_interval: int = 2000):
-        """(re)starts dynamic loss scaling with GradScaler's parameters (fp16 engines only)"""
-        self.scaler_cfg = dict(init_scale=init_scale, growth=growth, backoff=backoff, growth_interval=growth_interval)
-        self.scaler_on = True
-        self.set_state(seed=0, lr=0.0, step=1, reset_scaler=1, init_scale=init_scale)
-
     def check_overflow_and_update_scaler(self):
         """autograd path at fp16: flags a non-finite gradient norm (eg_step_state.found_inf) and adapts the internal loss scale,
         as the native optimiser step does between eg_clip_coef and eg_scaler_update -- without touching parameters."""
         self._alloc_bwd()
         self.stream = self._cur_stream()
-        nblk = 1024
-        if "sqpart" not in self.g:
-            self.g["sqpart"] = self._t(nblk, dtype=torch.float32)
+        nblk, sq = self.SQ_BLOCKS, ptr(self._sqpart())
         self._acc_norm_ready = False
-        call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
-        call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, 0.0, self.st_ptr, self.stream)
+        call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, sq, nblk, self.stream)
+        call("eg_clip_coef", sq, nblk, 0.0, self.st_ptr, self.stream)
         c = self.scaler_cfg
         call("eg_scaler_update", self.st_ptr, c["growth"], c["backoff"], c["growth_interval"], self.stream)
-
-    @property
-    def loss_scale_dev(self) -> torch.Tensor:
-        """the device-resident loss scale as a 1-element fp32 view of eg_step_state (word 8)"""
-        return self.state_dev.view(torch.float32)[8:9]
-
-    def read_state(self) -> StepState:
-        host = self.state_dev.cpu()
-        st = StepState()
-        C.memmove(C.addressof(st), host.data_ptr(), C.sizeof(st))
-        return st
-
-    @property
-    def st_ptr(self) -> int:
-        return self.state_dev.data_ptr()
-
-    def _cur_stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
-
-    # ------------------------------------------------------------------------------------------
-    # thin wrappers
-    # ------------------------------------------------------------------------------------------
-    def gemm(self, A, W, Cout, M, N, K, *, a=None, c=None, r=None, p=None, ldw=None, bias=0, residual=0, gate=0,
-             out_pre=0, act=0, drop1=(0.0, 0), drop2=(0.0, 0), gate_scale=1.0, tag=None, seg=(0, 0)):
-        probe = self.probes.get(tag) if tag else None
-        dsc = self._gemm_desc(A, W, Cout, M, N, K, a, c, r, p, ldw, bias, residual, gate, out_pre, act, drop1, drop2,
-                              gate_scale, seg)
-        if self.probe_all is not None:      # bench.py: HIP events around EVERY eg_gemm_nt launch of the timed region
-            probe = self._probe_pair()
-            self.probe_all.append((probe[0], probe[1], 2.0 * M * N * K,
-                                   self._gemm_bytes(M, N, K, a, seg, residual, gate, out_pre, Cout), (M, N, K),
-                                   L.lib().eg_gemm_nt_route(C.byref(dsc))))
-        if probe:
-            probe[0].record(torch.cuda.current_stream(self.device))
-        call("eg_gemm_nt", C.byref(dsc), self.stream)
-        if probe:
-            probe[1].record(torch.cuda.current_stream(self.device))
-
-    def gemm_batch(self, items):
-        """eg_gemm_nt_batch: the products `items` -- dicts of gemm()'s arguments, one dtype and one epilogue kind -- as ONE
-        wide-tile launch where all of them fit it, else one launch each; the bits of len(items) gemm() calls either way."""
-        keys = ("a", "c", "r", "p", "ldw", "bias", "residual", "gate", "out_pre", "act", "drop1", "drop2", "gate_scale")
-        dflt = dict(a=None, c=None, r=None, p=None, ldw=None, bias=0, residual=0, gate=0, out_pre=0, act=0, drop1=(0.0, 0),
-                    drop2=(0.0, 0), gate_scale=1.0)
-        descs = (GemmDesc * len(items))()
-        for i, it in enumerate(items):
-            descs[i] = self._gemm_desc(it["A"], it["W"], it["C"], it["M"], it["N"], it["K"], *[it.get(k, dflt[k]) for k in keys])
-        probe = None
-        if self.probe_all is not None:      # bench.py: one timed launch carrying the work of all its products
-            probe = self._probe_pair()
-            nbytes = sum(self._gemm_bytes(it["M"], it["N"], it["K"], it.get("a"), (0, 0), it.get("residual", 0), it.get("gate", 0),
-                                          it.get("out_pre", 0), it["C"]) for it in items)
-            self.probe_all.append((probe[0], probe[1], sum(2.0 * it["M"] * it["N"] * it["K"] for it in items), nbytes,
-                                   (sum(it["M"] for it in items), items[0]["N"], max(it["K"] for it in items)),
-                                   L.lib().eg_gemm_nt_route(C.byref(descs[0]))))
-            probe[0].record(torch.cuda.current_stream(self.device))
-        call("eg_gemm_nt_batch", descs, len(items), self.stream)
-        if probe:
-            probe[1].record(torch.cuda.current_stream(self.device))
 
     def conv1_bwd_data(self, sc01, batch=None):
         """dh0 = conv-1's backward-data (gated by h0 > 0, scaled by sc01): stride phase ph gives rows t = u*s + ph of dh0pad
@@ -495,18 +706,34 @@ class Engine:
         for i in range(0, len(items), L.GEMM_BATCH_MAX):
             self.gemm_batch(items[i:i + L.GEMM_BATCH_MAX])
 
-    def qkv_proj(self, x, l):
-        """q|k|v = x W^T + b (A:203-205), fused over the three projections (the row-stream GEMM at K = 256)"""
-        M, d = self.M, self.cfg.d_model
-        self.gemm(ptr(x), ptr(self.w[f"qkv{l}"]), ptr(self.a[f"qkv{l}"]), M, 3 * d, d, bias=ptr(self.w[f"bqkv{l}"]))
+    def _attn_stage(self, l):
+        """Attention stage l -- an encoder layer's index, or "x" for the cross-attention block, which is an unfused layer's
+        attention half under other names: (parameter prefix, q|k|v rows, log-sum-exps, context rows, pre-LN sum rows)"""
+        a = self.a
+        if l == "x":
+            return "cross_attn.cross_attn.", a["qkvx"], a["lsex"], a["ctxx"], a["rx"]
+        return f"encoder.layers.{l}.mha.", a[f"qkv{l}"], a[f"lse{l}"], a[f"ctx{l}"], a[f"r1_{l}"]
+
+    def attn_unfused_fwd(self, x, l, kv_shift, sites, p):
+        """Stage l's forward as three launches: q|k|v = x W^T + b (A:203-205) fused over the three projections (the row-stream
+        GEMM at K = 256), the attention core, out-proj + dropout + residual.  kv_shift = B pairs window b with b + B (D:966-974)."""
+        M, d, H = self.M, self.cfg.d_model, self.cfg.num_heads
+        pre, qkv, lse, ctx, r = self._attn_stage(l)
+        self.gemm(ptr(x), ptr(self.w[f"qkv{l}"]), ptr(qkv), M, 3 * d, d, bias=ptr(self.w[f"bqkv{l}"]))
+        call("eg_attention_long_fwd" if self.attn_long else "eg_attention_fwd", ptr(qkv), ptr(ctx), ptr(lse), self.NB, self.S, H,
+             kv_shift, self.dtype, p, sites["attn"], self.st_ptr, self.stream)
+        self._probs_hook(self.model.get_submodule(pre + "dropout"), qkv, lse, kv_shift)
+        self.gemm(ptr(ctx), ptr(self.w[f"o{l}"]), ptr(r), M, d, d, bias=self.fp.p_ptr(pre + "out_proj.bias"),
+                  drop1=(p, sites["drop1"]), residual=ptr(x))
 
     def attn_block_fwd(self, x, l, p, sites, ln=None):
         """eg_attn_block_fwd (csrc/attnblock.hip): A:202-213 + the residual of A:292-293 for encoder layer l in one launch"""
-        a, w, fp, d = self.a, self.w, self.fp, self.cfg.d_model
+        w, fp, d = self.w, self.fp, self.cfg.d_model
+        pre, qkv, lse, ctx, r1 = self._attn_stage(l)
         dsc = L.AttnBlockDesc()
         dsc.x, dsc.wqkv_frag, dsc.wo_frag = ptr(x), ptr(w[f"wqkvb{l}"]), ptr(w[f"wob{l}"])
-        dsc.bqkv, dsc.bo = ptr(w[f"bqkv{l}"]), fp.p_ptr(f"encoder.layers.{l}.mha.out_proj.bias")
-        dsc.qkv, dsc.ctx, dsc.lse, dsc.r1 = ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(a[f"lse{l}"]), ptr(a[f"r1_{l}"])
+        dsc.bqkv, dsc.bo = ptr(w[f"bqkv{l}"]), fp.p_ptr(pre + "out_proj.bias")
+        dsc.qkv, dsc.ctx, dsc.lse, dsc.r1 = ptr(qkv), ptr(ctx), ptr(lse), ptr(r1)
         dsc.state = self.st_ptr
         dsc.NB, dsc.S, dsc.d_model, dsc.num_heads, dsc.dtype = self.NB, self.S, d, self.cfg.num_heads, self.dtype
         dsc.attn_drop_p, dsc.attn_drop_site = p, sites["attn"]
@@ -514,27 +741,17 @@ class Engine:
         if ln is not None:                  # (gain name, output rows, statistics): norm1 in the same launch
             dsc.ln_gamma, dsc.ln_beta = fp.p_ptr(ln[0] + ".weight"), fp.p_ptr(ln[0] + ".bias")
             dsc.ln_out, dsc.ln_stats = ptr(ln[1]), ptr(ln[2])
-        probe = None
-        if self.probe_all is not None:      # bench.py: timed like the eg_gemm_nt launches, as its own kernel (route 8)
-            probe = self._probe_pair()
+
+        def work():                         # bench.py: timed like the eg_gemm_nt launches, as its own kernel (route 8)
             M, S, H = self.M, self.S, self.cfg.num_heads
             flops = 2.0 * M * d * 3 * d + 2.0 * M * d * d + 4.0 * self.NB * H * S * S * (d // H)
             nbytes = self.es * (M * d * 3 + M * 3 * d + 4 * d * d) + 4 * (self.NB * H * S + 4 * d)    # x, ctx, r1 | qkv | weights | lse, biases
             if ln is not None:
                 nbytes += self.es * M * d + 8 * M + 8 * d                                             # norm1 rows, statistics, gain / bias
-            self.probe_all.append((probe[0], probe[1], flops, float(nbytes), (M, 3 * d, d), 8))
-            probe[0].record(torch.cuda.current_stream(self.device))
+            return flops, float(nbytes), (M, 3 * d, d), 8
+        probe = self._timed(work)
         call("eg_attn_block_fwd", C.byref(dsc), self.stream)
-        if probe:
-            probe[1].record(torch.cuda.current_stream(self.device))
-
-    def _probe_pair(self):
-        """A (start, end) event pair for a timed launch: from bench.py's pre-created pool when there is one -- creating a
-        hipEvent costs the host far more than recording one, and fresh events inside the timed region made short runs host-bound."""
-        pool = getattr(self, "probe_pool", None)
-        if pool:
-            return pool.pop()
-        return (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self._timed_end(probe)
 
     def ffn(self, A, W1f, W2f, H, Cout, M, F, *, bias1=0, bias2=0, act1=0, residual=0, gate=0, bits_out=0, bits_in=0,
             drop_h=(0.0, 0), drop_c1=(0.0, 0), drop_c2=(0.0, 0), gate_scale=1.0, ln=None):
@@ -554,17 +771,15 @@ class Engine:
         if ln is not None:                  # (gain name, output rows, statistics): norm2 in the same launch
             dsc.ln_gamma, dsc.ln_beta = self.fp.p_ptr(ln[0] + ".weight"), self.fp.p_ptr(ln[0] + ".bias")
             dsc.ln_out, dsc.ln_stats = ptr(ln[1]), ptr(ln[2])
-        probe = None
-        if self.probe_all is not None:      # bench.py: timed like the eg_gemm_nt launches, as its own kernel (route 4)
-            probe = self._probe_pair()
+
+        def work():                         # bench.py: timed like the eg_gemm_nt launches, as its own kernel (route 4)
             es = self.es
             nbytes = es * (M * d * (2 + (1 if residual and residual != A else 0)) + M * F * (1 + (1 if gate else 0)) + 2 * F * d) \
                 + (M * F // 8 if (bits_out or bits_in) else 0) + 4 * (F + d) + ((es * M * d + 8 * M + 8 * d) if ln is not None else 0)
-            self.probe_all.append((probe[0], probe[1], 4.0 * M * F * d, float(nbytes), (M, F, d), 4))
-            probe[0].record(torch.cuda.current_stream(self.device))
+            return 4.0 * M * F * d, float(nbytes), (M, F, d), 4
+        probe = self._timed(work)
         call("eg_ffn_chain", C.byref(dsc), self.stream)
-        if probe:
-            probe[1].record(torch.cuda.current_stream(self.device))
+        self._timed_end(probe)
 
     def _probs_hook(self, drop_module, qkv, lse, kv_shift):
         """Analysis contract (5_Metrics/eeg_metrics.py:433-452): a forward hook on an attention-dropout module receives
@@ -584,236 +799,50 @@ class Engine:
         finally:
             drop_module.training = was
 
-    def _gemm_bytes(self, M, N, K, a, seg, residual, gate, out_pre, Cout=1) -> float:
-        """Algorithmic HBM bytes of one gemm_nt launch: every distinct operand element read once, every output element
-        written once (overlapping conv rows count once; the weights count once)."""
-        es = self.es
-        if a is not None and a.rows_per_group > 0 and not seg[0]:
-            groups = M // a.rows_per_group
-            a_elems = groups * ((a.rows_per_group - 1) * min(a.row_stride, K) + K)
-        elif seg[0]:                       # segmented rows (spectrogram conv): K elements per row drawn from K/seg_len runs
-            a_elems = M * K if a is None else min(M * K, M * max(a.row_stride, 1) + K)
-        else:
-            a_elems = M * K
-        outs = (1 if Cout else 0) + (1 if out_pre else 0)
-        ins = (1 if residual else 0) + (1 if gate else 0)
-        return float(es * (a_elems + N * K + (outs + ins) * M * N) + 4 * N)
-
-    def _gemm_desc(self, A, W, Cout, M, N, K, a, c, r, p, ldw, bias, residual, gate, out_pre, act, drop1, drop2, gate_scale,
-                   seg=(0, 0)):
-        dsc = GemmDesc()
-        dsc.a_seg_len, dsc.a_seg_stride = seg
-        dsc.A, dsc.W, dsc.C = A, W, Cout or None
-        dsc.bias, dsc.residual, dsc.gate, dsc.out_pre = bias or None, residual or None, gate or None, out_pre or None
-        dsc.state = self.st_ptr
-        dsc.a = a or rowmap(K)
-        dsc.c = c or rowmap(N)
-        dsc.r = r or dsc.c
-        dsc.p = p or dsc.c
-        dsc.M, dsc.N, dsc.K, dsc.ldw = M, N, K, ldw or K
-        dsc.act, dsc.dtype = act, self.dtype
-        dsc.drop1_p, dsc.drop1_site = drop1
-        dsc.drop2_p, dsc.drop2_site = drop2
-        dsc.gate_scale = gate_scale
-        return dsc
-
-    def wgrad(self, dY, X, out_w, M, N, K, *, y=None, x=None, out_b=0, conv=None, split_out=None, x_tile_stride=0,
-              conv2d=None, linear=None):
-        """dW = dY^T X (+ db = colsum dY).
-        linear=[prefix, ...]: the product feeds N/len(linear) rows to each `prefix.weight` / `prefix.bias`; when those
-        parameters are laid out back to back in the flat buffer (they are: registration order) the bias sums are fused
-        into the GEMM launch and ONE reduce writes every weight and bias gradient.
-        conv / conv2d: tap-major partials are un-permuted into the parameter layout; out_b via a column-sum launch."""
-        tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        fused = False
-        if linear is not None:
-            P = N // len(linear)
-            base = self.fp.offsets[linear[0] + ".weight"]
-            fused = P % 4 == 0 and all(self.fp.offsets[n + ".weight"] == base + i * (P * K + P) and
-                                       self.fp.offsets[n + ".bias"] == base + i * (P * K + P) + P * K
-                                       for i, n in enumerate(linear))
-        slab = N * K + (N if fused else 0)
-        # one resident round: 256 CUs x 3 workgroups; rounding the split count UP would leave a nearly empty second round
-        splits = max(1, min((M + 127) // 128, max(1, 768 // tiles), self.tn_cap // slab))
-        # big products on 16-bit operands: 256 x 256 tiles, one 512-thread workgroup per CU (conv-1: 25 tiles x 10 row splits)
-        big = (self.dtype != EG_F32 and N % 256 == 0 and K % 256 == 0 and not x_tile_stride and M * N * K >= (1 << 34)
-               and os.environ.get("EYEGAZE_TN256", "1") != "0")
-        if big:
-            t256 = (N // 256) * (K // 256)
-            splits = max(1, min((M + 63) // 64, max(1, self.cus // t256), self.tn_cap // slab))
-        dsc = GemmTNDesc()
-        dsc.tile = 256 if big else 128
-        dsc.dY, dsc.X, dsc.partial = dY, X, ptr(self.g["partial"])
-        dsc.y = y or rowmap(N)
-        dsc.x = x or rowmap(K)
-        dsc.M, dsc.N, dsc.K, dsc.splits, dsc.dtype = M, N, K, splits, self.dtype
-        dsc.x_tile_stride = x_tile_stride
-        if fused:
-            dsc.part_rows, dsc.has_bias = N // len(linear), 1
-        call("eg_gemm_tn", C.byref(dsc), self.stream)
-        pp = ptr(self.g["partial"])
-        if fused:
-            call("eg_reduce_partials", pp, self.fp.g_ptr(linear[0] + ".weight"), slab, splits, slab, 0, self.stream)
-            return
-        if linear is not None:  # non-contiguous parameters: per-parameter reduces + a column-sum launch
-            P = N // len(linear)
-            split_out = [(self.fp.g_ptr(n + ".weight"), i * P, P) for i, n in enumerate(linear)]
-            out_b = [(self.fp.g_ptr(n + ".bias"), i * P, P) for i, n in enumerate(linear)]
-        if conv2d is not None:
-            call("eg_unpack_conv2d_wgrad", pp, out_w, splits, conv2d[0], conv2d[1], self.stream)
-        elif conv is not None:
-            cin, kk, cp = conv
-            call("eg_unpack_conv_wgrad", pp, out_w, splits, N, cin, kk, cp, K, self.stream)
-        elif split_out is not None:
-            for gp, row0, rows in split_out:
-                call("eg_reduce_partials", pp + 4 * row0 * K, gp, rows * K, splits, N * K, 0, self.stream)
-        else:
-            call("eg_reduce_partials", pp, out_w, N * K, splits, N * K, 0, self.stream)
-        if out_b:
-            nblk = min(512, (M + 63) // 64)
-            call("eg_colsum", dY, dsc.y, M, N, ptr(self.g["cspart"]), nblk, self.dtype, self.stream)
-            if isinstance(out_b, (list, tuple)):
-                for gp, col0, cols in out_b:
-                    call("eg_reduce_partials", ptr(self.g["cspart"]) + 4 * col0, gp, cols, nblk, N, 0, self.stream)
-            else:
-                call("eg_reduce_partials", ptr(self.g["cspart"]), out_b, N, nblk, N, 0, self.stream)
-
     # ------------------------------------------------------------------------------------------
     # grouped weight gradients of the encoder: ONE launch for all 4*L products, ONE reduce launch
     # ------------------------------------------------------------------------------------------
-    GROUP_SPLITS = int(os.environ.get("EYEGAZE_GROUP_SPLITS", "5"))
-    GROUP_MIN_ROWS = 4096   # below this the per-product launches (many splits) are the better shape
-    REDUCE_LN_FIRST = os.environ.get("EYEGAZE_REDUCE_LN_FIRST", "1") != "0"   # order of the grouped reduce table, see tables()
-
     def _ln_splits(self, name: str) -> int:
         """partial rows that the backward of LayerNorm `name` leaves (eg_ln_bwd_proj's tiles for a layer's ln1, else LN_BLOCKS)"""
         return self.ln_proj_blocks if (self.ln_proj and name.endswith(".ln1")) else self.LN_BLOCKS
 
     def _wgrad_group_plan(self):
-        if getattr(self, "_wg_plan", "unset") != "unset" and getattr(self, "_wg_key", None) == self.fp.grad.data_ptr():
+        """The grouped launch's tables (wgrad_plan.plan) for the current gradient buffer, or None: too few rows, or parameters
+        not laid out for the fused reduces.  Allocates the per-layer dY operands and the partial buffers the tables point into."""
+        fp = self.fp
+        if self._wg_key == fp.grad.data_ptr():
             return self._wg_plan
-        cfg, d, F, M, fp = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.M, self.fp
-        self._wg_key = fp.grad.data_ptr()
-        self._wg_plan = None
-        if M < self.GROUP_MIN_ROWS:
+        self._wg_key, self._wg_plan = fp.grad.data_ptr(), None
+        cfg, d, F, M, g = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.M, self.g
+        lay = wgrad_plan.layout(cfg, self.dtype, self.cus, fp.offsets) if M >= self.GROUP_MIN_ROWS else None
+        if lay is None:
             return None
-        probs = []
-        for l in range(cfg.num_layers):
-            pre = f"encoder.layers.{l}."
-            probs += [([pre + "mha.out_proj"], f"dYo{l}", f"ctx{l}", d, d, d),
-                      ([pre + "mha.q_proj", pre + "mha.k_proj", pre + "mha.v_proj"], f"dqkv{l}", f"x{l}", 3 * d, d, 3 * d),
-                      ([pre + "ffn.linear2"], f"dYf{l}", f"hff{l}", d, F, d),
-                      ([pre + "ffn.linear1"], f"dh{l}", f"y1_{l}", F, d, F)]
-        def packed(names, N, K):                 # (weight, bias) pairs must sit back to back in the flat buffer
-            P = N // len(names)
-            base = fp.offsets[names[0] + ".weight"]
-            return all(fp.offsets[n + ".weight"] == base + i * (P * K + P) and fp.offsets[n + ".bias"] == base + i * (P * K + P) + P * K
-                       for i, n in enumerate(names))
-        if not all(packed(names, N, K) for names, _, _, N, K, _ in probs):
-            return None
-        # the two weight gradients of the cross-attention block ride in the same launch (their own dY buffers, as the layers have)
-        cx = "cross_attn.cross_attn."
-        cross = [([cx + "out_proj"], "dYo_x", "ctxx", d, d, d),
-                 ([cx + "q_proj", cx + "k_proj", cx + "v_proj"], "dqkv_x", "zn", 3 * d, d, 3 * d)]
-        self._wg_cross = (cfg.use_cross_attention and os.environ.get("EYEGAZE_WGRAD_CROSS", "1") != "0"
-                          and all(packed(names, N, K) for names, _, _, N, K, _ in cross))
-        ncross = 0
-        if self._wg_cross:
-            probs += cross
-            ncross = len(cross)
-        g = self.g
+        self._wg_cross, self._ln_slot = lay.wg_cross, lay.ln_slot
         for l in range(cfg.num_layers):
             g[f"dYo{l}"], g[f"dYf{l}"] = self._t(M, d), self._t(M, d)
             g[f"dqkv{l}"], g[f"dh{l}"] = self._t(M, 3 * d), self._t(M, F)
-        if self._wg_cross:
+        if lay.wg_cross:
             g["dYo_x"], g["dqkv_x"] = self._t(M, d), self._t(M, 3 * d)
-        # 16-bit dtypes: 256 x 256 tiles, one 512-thread workgroup per CU (72 tiles x 3 row splits = 216 blocks, one round);
-        # otherwise 128 x 128 tiles, three 256-thread workgroups per CU (288 tiles x 5 splits)
-        big = (self.dtype != EG_F32 and os.environ.get("EYEGAZE_TN256", "1") != "0"
-               and all(N % 256 == 0 and K % 256 == 0 for _, _, _, N, K, _ in probs))
-        splits = int(os.environ.get("EYEGAZE_GROUP_SPLITS256", "3")) if big else self.GROUP_SPLITS
-        tile = 256 if big else 128
-        total = sum(N * K + N for _, _, _, N, K, _ in probs)
-        # data-parallel runs cut the launch in two pieces; with 256 x 256 tiles a piece has ~40 tiles, so it takes twice the
-        # row splits to fill the chip (240 / 216 blocks) -- with the whole launch's 3 splits each piece ran on 45 % of the CUs
-        # and the pair cost 0.42 ms more than the single launch
-        Lr_ = cfg.num_layers
-        piece_tiles = ((Lr_ - Lr_ // 2) * 12 + (4 if self._wg_cross else 0)) if big else 0
-        splits_p = max(splits, self.cus // piece_tiles) if big and piece_tiles else splits
-        smax = max(splits, splits_p)
-        g["wg_partial"] = self._t(smax * total, dtype=torch.float32)
-        ln_names = [f"encoder.layers.{l}.{n}" for l in range(cfg.num_layers) for n in ("ln1", "ln2")]
-        if not all(fp.offsets[n + ".bias"] == fp.offsets[n + ".weight"] + d for n in ln_names):
-            return None
-        # encoder.norm and cross_attn.norm get slots behind the layers': without a gradient reducer their gain / bias partials
-        # ride in the whole-encoder reduce launch too (backward decides; with a reducer their buckets are released at once)
-        tail_names = [n for n in ["encoder.norm"] + (["cross_attn.norm"] if cfg.use_cross_attention else [])
-                      if fp.offsets[n + ".bias"] == fp.offsets[n + ".weight"] + d]
-        g["lnpart_all"] = self._t((len(ln_names) + len(tail_names)) * self.ln_nblk_cap * 2 * d, dtype=torch.float32)
-        self._ln_slot = {n: i for i, n in enumerate(ln_names + tail_names)}
-        ln_of = {}
-        for i, n in enumerate(ln_names):
-            ln_of.setdefault(int(n.split(".")[2]), []).append((i, n))
-        ln_tail = [(self._ln_slot[n], n) for n in tail_names]
-        dev = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        offs, off = [], 0
-        for names, dyn, xn, N, K, ldy in probs:
-            offs.append(off)
-            off += smax * (N * K + N)
-
-        def tables(layers, with_cross=False, nsplit=None, with_tail=False):
-            """TN problem table + reduce table (weights, biases and the deferred LayerNorm gain / bias partials) of `layers`
-            (+ the cross-attention block's two products); block ranges are relative to the tables' own launches.  Which launch
-            a product rides in does not change its result AT EQUAL nsplit (same row split, same ordered sum); the data-parallel
-            pieces run with more row splits than the single launch (splits_p vs splits), so their gradients differ from the
-            single launch's by fp32 summation order (~2e-6 relative), each arrangement deterministic in itself."""
-            nsplit = nsplit or splits
-            sel = [4 * l + j for l in layers for j in range(4)]
-            if with_cross:
-                sel += [4 * cfg.num_layers + j for j in range(ncross)]
-            lns = [e for l in layers for e in ln_of[l]] + (ln_tail if with_tail else [])
-            tp = (L.TNProblem * len(sel))()
-            rt = (L.ReduceEntry * (len(sel) + len(lns)))()
-            blk = 0
-            red = []        # (partial, out, n, splits) of the reduce entries, weight gradients first
-            for e, pi in zip(tp, sel):
-                names, dyn, xn, N, K, ldy = probs[pi]
-                slab = N * K + N
-                base = ptr(g["wg_partial"]) + 4 * offs[pi]
-                e.dY, e.X, e.partial = ptr(g[dyn]), ptr(self.a[xn]), base
-                e.ldy, e.ldx, e.N, e.K, e.part_rows, e.has_bias, e.blk0 = ldy, K, N, K, N // len(names), 1, blk
-                blk += ((N + tile - 1) // tile) * ((K + tile - 1) // tile) * nsplit
-                red.append((base, fp.g_ptr(names[0] + ".weight"), slab, nsplit))
-            # deferred LayerNorm gain / bias partials ride in the same reduce launch.  Such an entry is 16 workgroups that walk
-            # hundreds of short rows each, pure latency: they go FIRST in the table, so that they run under the streaming
-            # weight-gradient entries instead of after them
-            lnred = [(ptr(g["lnpart_all"]) + 4 * i * self.ln_nblk_cap * 2 * d, fp.g_ptr(n + ".weight"), 2 * d, self._ln_splits(n))
-                     for i, n in lns]
-            red = lnred + red if self.REDUCE_LN_FIRST else red + lnred
-            rblk = 0
-            for r, (part, out, n, nsp) in zip(rt, red):
-                r.partial, r.out, r.n, r.stride, r.splits, r.blk0 = part, out, n, n, nsp, rblk
-                rblk += _reduce_blocks(n, nsp)
-            return dict(tp=dev(tp), rt=dev(rt), n=len(sel), nr=len(sel) + len(lns), blocks=blk, rblocks=rblk, layers=list(layers),
-                        splits=nsplit)
-
-        Lr = cfg.num_layers
-        whole = tables(range(Lr), with_cross=True)
-        # data parallel: two pieces, so the gradient buckets of layers L-1 .. L/2 start their all-reduce while layers L/2-1 .. 0
-        # are still in backward (one piece would hold every encoder bucket back until backward has finished)
-        h = Lr // 2
-        pieces = ([tables(range(h, Lr), with_cross=True, nsplit=splits_p), tables(range(0, h), nsplit=splits_p)]
-                  if Lr >= 2 else [whole])
-        self._wg_plan = dict(whole, splits=splits, pieces=pieces, split_layer=h,
-                             whole_norms=tables(range(Lr), with_cross=True, with_tail=True) if ln_tail else None,
-                             entry="eg_gemm_tn_grouped256" if big else "eg_gemm_tn_grouped")
+        g["wg_partial"] = self._t(lay.smax * lay.total, dtype=torch.float32)
+        g["lnpart_all"] = self._t(len(lay.ln_slot) * self.ln_nblk_cap * 2 * d, dtype=torch.float32)
+        addr = {}
+        for _, dyn, xn, _, _, _ in lay.probs:
+            addr[dyn], addr[xn] = ptr(g[dyn]), ptr(self.a[xn])
+        self._wg_plan = wgrad_plan.plan(lay, cfg, addr, ptr(g["wg_partial"]), ptr(g["lnpart_all"]), ptr(fp.grad), fp.offsets,
+                                        self.ln_nblk_cap, self._ln_splits, self.device)
         return self._wg_plan
 
-    def _wgrad_group_launch(self, piece=None):
-        """piece: None = every encoder layer in one launch; else one of `_wg_plan['pieces']` (data-parallel runs)."""
+    def _wgrad_group_launch(self, piece, seg, cross=False):
+        """piece: None = every encoder layer in one launch; else one of `_wg_plan['pieces']` (data-parallel runs) or its
+        'whole_norms'.  seg then hears which gradient buckets are complete: "cross" when the cross-attention block's products
+        rode in this launch, and the piece's layers, last first."""
         pl = self._wg_plan if piece is None else piece
         call(self._wg_plan["entry"], ptr(pl["tp"]), pl["n"], pl["blocks"], self.M, pl["splits"], self.dtype, self.stream)
         call("eg_reduce_table", ptr(pl["rt"]), pl["nr"], pl["rblocks"], self.stream)
+        if cross:
+            seg("cross")
+        for l in reversed(pl["layers"]):
+            seg(f"layer{l}")
 
     def ln_fwd(self, x, gname, y, stats):
         call("eg_layernorm_fwd", ptr(x), self.fp.p_ptr(gname + ".weight"), self.fp.p_ptr(gname + ".bias"), ptr(y),
@@ -822,127 +851,49 @@ class Engine:
     def ln_bwd_proj(self, dy, x, stats, gname, wfrag, dx, dx_drop, dC, d1=(0.0, 0), slot=None):
         """eg_ln_bwd_proj: LayerNorm backward + the backward-data product dC = dx_drop W^T in one launch (csrc/lnproj.hip)"""
         d = self.cfg.d_model
-        nblk = self.ln_proj_blocks
-        lp = ptr(self.g["lnpart"]) if slot is None else ptr(self.g["lnpart_all"]) + 4 * slot * self.ln_nblk_cap * 2 * d
-        cap = self.LN_PARTIAL_BLOCKS if slot is None else self.ln_nblk_cap
+        lp, cap = self._ln_partials(slot)
         dsc = L.LnBwdProjDesc()
         dsc.dy, dsc.x, dsc.stats, dsc.gamma, dsc.W_frag = ptr(dy), ptr(x), ptr(stats), self.fp.p_ptr(gname + ".weight"), ptr(wfrag)
         dsc.dx, dsc.dx_drop, dsc.dC, dsc.partial, dsc.state = ptr(dx), ptr(dx_drop), ptr(dC), lp, self.st_ptr
         dsc.M, dsc.d_model, dsc.dtype, dsc.partial_capacity_blocks = self.M, d, self.dtype, cap
         dsc.drop1_p, dsc.drop1_site = d1
         call("eg_ln_bwd_proj", C.byref(dsc), self.stream)
-        if slot is not None:
-            return
-        if self.fp.offsets[gname + ".bias"] == self.fp.offsets[gname + ".weight"] + d:
-            call("eg_reduce_partials", lp, self.fp.g_ptr(gname + ".weight"), 2 * d, nblk, 2 * d, 0, self.stream)
-        else:
-            call("eg_reduce_partials", lp, self.fp.g_ptr(gname + ".weight"), d, nblk, 2 * d, 0, self.stream)
-            call("eg_reduce_partials", lp + 4 * d, self.fp.g_ptr(gname + ".bias"), d, nblk, 2 * d, 0, self.stream)
+        if slot is None:
+            self._reduce_ln_partials(lp, gname, self.ln_proj_blocks)
 
     def ln_bwd(self, dy, x, stats, gname, dx, dx_drop=None, d1=(0.0, 0), d2=(0.0, 0), slot=None):
         """slot: index into the deferred gain/bias partial buffer (reduced by the grouped reduce at the end of backward)"""
         d = self.cfg.d_model
-        nblk = self.LN_BLOCKS
-        lp = ptr(self.g["lnpart"]) if slot is None else ptr(self.g["lnpart_all"]) + 4 * slot * self.ln_nblk_cap * 2 * d
-        cap = self.LN_PARTIAL_BLOCKS if slot is None else self.ln_nblk_cap      # rows of [2, d] behind `lp`
+        lp, cap = self._ln_partials(slot)
         call("eg_layernorm_bwd", ptr(dy), ptr(x), ptr(stats), self.fp.p_ptr(gname + ".weight"), ptr(dx), ptr(dx_drop),
-             lp, nblk, cap, self.M, d, self.dtype, d1[0], d1[1], d2[0], d2[1], self.st_ptr, self.stream)
-        if slot is not None:
-            return
-        if self.fp.offsets[gname + ".bias"] == self.fp.offsets[gname + ".weight"] + d:   # (gain | bias) back to back
-            call("eg_reduce_partials", lp, self.fp.g_ptr(gname + ".weight"), 2 * d, nblk, 2 * d, 0, self.stream)
+             lp, self.LN_BLOCKS, cap, self.M, d, self.dtype, d1[0], d1[1], d2[0], d2[1], self.st_ptr, self.stream)
+        if slot is None:
+            self._reduce_ln_partials(lp, gname, self.LN_BLOCKS)
+
+    def _ln_partials(self, slot):
+        """(address, rows of [2, d]) of a LayerNorm backward's gain / bias partials: the scratch buffer, or a slot of the deferred one"""
+        if slot is None:
+            return ptr(self.g["lnpart"]), self.LN_PARTIAL_BLOCKS
+        return ptr(self.g["lnpart_all"]) + 4 * slot * self.ln_nblk_cap * 2 * self.cfg.d_model, self.ln_nblk_cap
+
+    def _reduce_ln_partials(self, lp, gname, nblk):
+        """sums the nblk rows of [gain | bias] partials at lp into the gradients of LayerNorm `gname`"""
+        d, fp = self.cfg.d_model, self.fp
+        if fp.offsets[gname + ".bias"] == fp.offsets[gname + ".weight"] + d:   # (gain | bias) back to back
+            call("eg_reduce_partials", lp, fp.g_ptr(gname + ".weight"), 2 * d, nblk, 2 * d, 0, self.stream)
         else:
-            call("eg_reduce_partials", lp, self.fp.g_ptr(gname + ".weight"), d, nblk, 2 * d, 0, self.stream)
-            call("eg_reduce_partials", lp + 4 * d, self.fp.g_ptr(gname + ".bias"), d, nblk, 2 * d, 0, self.stream)
+            call("eg_reduce_partials", lp, fp.g_ptr(gname + ".weight"), d, nblk, 2 * d, 0, self.stream)
+            call("eg_reduce_partials", lp + 4 * d, fp.g_ptr(gname + ".bias"), d, nblk, 2 * d, 0, self.stream)
 
-    # ------------------------------------------------------------------------------------------
-    # parameter staging
-    # ------------------------------------------------------------------------------------------
-    # table-driven staging: cast / transpose entries are recorded once and replayed as ONE launch per step
-    def p_cast(self, src, dst, n):
-        if self._recording:
-            self._plan.append((src, dst, 1, n, 0, 0))
-
-    def p_copy(self, src, dst, n):
-        if self._recording:
-            self._plan.append((src, dst, 1, n, 0, 2))
-
-    def p_transpose(self, src, dst, R, Cc, ldd):
-        if self._recording:
-            self._plan.append((src, dst, R, Cc, ldd, 1))
-
-    def p_frag(self, src, dst, R, Cc, mode, part=0):
-        """fragment order of the fp32 parameter src [R, Cc]: eg_ffn_chain's (eg_pack_table modes 3-6) or eg_attn_block_fwd's
-        (mode 7 with part = 0 / 1 / 2 for q / k / v_proj, mode 8 for out_proj)."""
-        if self._recording:
-            self._plan.append((src, dst, R, Cc, part, mode))
-
-    def p_conv(self, src, dst, N, Cin, k, Cp, Kp):
-        """eg_pack_conv_weight as an entry of the pack table (fused route) or as its own launch"""
-        if self._plan_ex:
-            if self._recording:
-                self._plan.append((src, dst, N, Cin, 0, 9, k, Cp, Kp))
-        else:
-            call("eg_pack_conv_weight", src, dst, N, Cin, k, Cp, Kp, self.dtype, self.stream)
-
-    def p_convT(self, src, dst, N, Cin, k, s):
-        """eg_pack_convT_weight, likewise"""
-        if self._plan_ex:
-            if self._recording:
-                self._plan.append((src, dst, N, Cin, 0, 10, k, s, (k + s - 1) // s))
-        else:
-            call("eg_pack_convT_weight", src, dst, N, Cin, k, s, self.dtype, self.stream)
-
-    def _extent_after(self, addr: int, elsize: int) -> int:
-        """elements of size `elsize` between `addr` and the end of the engine / parameter buffer that holds it (0: not found)"""
-        bufs = list(self.w.values()) + [self.fp.flat]
-        for t in bufs:
-            lo = t.data_ptr()
-            hi = lo + t.numel() * t.element_size()
-            if lo <= addr < hi:
-                return (hi - addr) // elsize
-        return 0
-
-    def pack_params(self):
-        ex = bool(getattr(self, "fused_tail", False))       # (the image engine shares this method and keeps eg_pack_table)
-        # the routing flags decide which layouts _pack_body records, so a flag flipped on a live engine re-records the plan
-        key = (self.fp.flat.data_ptr(), ex, bool(getattr(self, "pack_unused", False)), getattr(self, "fuse_ffn", None),
-               getattr(self, "attn_block", None), getattr(self, "ln_proj", None))
-        self._plan_ex = ex
-        if getattr(self, "_plan_key", None) != key:
-            self._plan, self._recording = [], True
-            self._pack_body()
-            self._recording = False
-            ents = ((L.PackEntryEx if ex else L.PackEntry) * len(self._plan))()
-            blk = 0
-            for e, ent in zip(ents, self._plan):
-                src, dst, R, Cc, ldd, mode = ent[:6]
-                if mode == 9:
-                    nb = (R * ent[8] + 1023) // 1024
-                elif mode == 10:
-                    nb = (ent[7] * Cc * ent[8] * R + 1023) // 1024
-                else:
-                    nb = (((R + 31) // 32) * ((Cc + 31) // 32) if mode == 1 else (R * Cc) // 2048 if mode >= 3 else
-                          (R * Cc + 1023) // 1024)
-                e.src, e.dst, e.rows, e.cols, e.ldd, e.mode, e.blk0, e.nblk = src, dst, R, Cc, ldd, mode, blk, nb
-                if ex:
-                    if mode >= 9:
-                        e.p0, e.p1, e.p2 = ent[6:9]
-                    e.src_elems = self._extent_after(src, 4)
-                    e.dst_elems = self._extent_after(dst, 4 if mode == 2 else self.es)
-                blk += nb
-            if ex:      # host-side audit of every entry (block ranges, shapes, alignment, extents) before the table is ever launched
-                total = C.c_int(0)
-                call("eg_pack_table_ex_check", C.cast(ents, C.c_void_p), len(self._plan), self.dtype, C.byref(total))
-                if total.value != blk:
-                    raise L.EgError(f"pack table: {total.value} blocks audited, {blk} planned")
-            raw = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8)
-            self._plan_dev = raw.to(self.device)
-            self._plan_n, self._plan_blocks, self._plan_key = len(self._plan), blk, key
-        else:
-            self._pack_body()
-        call("eg_pack_table_ex" if ex else "eg_pack_table", ptr(self._plan_dev), self._plan_n, self._plan_blocks, self.dtype,
-             self.stream)
+    def ln_bwd_residual(self, dy, x, stats, gname, dmasked, d1, d2=(0.0, 0), slot=None):
+        """Backward of the LayerNorm behind a residual sum whose branch ends in dropout: `dmasked` receives the gradient that
+        enters the branch (masked by d1 / d2); returns the buffer that holds the gradient of the residual path -- g["dr"] with
+        dropout active, else `dmasked` itself (no mask: one gradient serves both)."""
+        if self.train_flags[0] > 0:
+            self.ln_bwd(dy, x, stats, gname, self.g["dr"], dmasked, d1=d1, d2=d2, slot=slot)
+            return self.g["dr"]
+        self.ln_bwd(dy, x, stats, gname, dmasked, None, slot=slot)
+        return dmasked
 
     def _pack_body(self):
         cfg, d, F, fp, w, dt, st = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.fp, self.w, self.dtype, self.stream
@@ -1003,8 +954,7 @@ class Engine:
     # forward
     # ------------------------------------------------------------------------------------------
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], train: bool):
-        cfg, d, F, H = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_heads
-        attn_fwd = "eg_attention_long_fwd" if self.attn_long else "eg_attention_fwd"
+        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
         B, NB, M, S, a, w, fp, es = self.B, self.NB, self.M, self.S, self.a, self.w, self.fp, self.es
         self.stream = self._cur_stream()
         st = self.stream
@@ -1038,12 +988,7 @@ class Engine:
                 self.attn_block_fwd(x, l, p, sites, ln=((pre + "ln1", a[f"y1_{l}"], a[f"st1_{l}"]) if self.ln_fuse else None))
                 self._probs_hook(self.model.encoder.layers[l].mha.dropout, a[f"qkv{l}"], a[f"lse{l}"], 0)
             else:
-                self.qkv_proj(x, l)
-                call(attn_fwd, ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(a[f"lse{l}"]), NB, S, H, 0, self.dtype, p,
-                     sites["attn"], self.st_ptr, st)
-                self._probs_hook(self.model.encoder.layers[l].mha.dropout, a[f"qkv{l}"], a[f"lse{l}"], 0)
-                self.gemm(ptr(a[f"ctx{l}"]), ptr(w[f"o{l}"]), ptr(a[f"r1_{l}"]), M, d, d, bias=fp.p_ptr(pre + "mha.out_proj.bias"),
-                          drop1=(p, sites["drop1"]), residual=ptr(x))
+                self.attn_unfused_fwd(x, l, 0, sites, p)
             if not (self.attn_block and self.ln_fuse):
                 self.ln_fwd(a[f"r1_{l}"], pre + "ln1", a[f"y1_{l}"], a[f"st1_{l}"])
             if self.fuse_ffn:       # linear1 -> ReLU -> dropout -> linear2 -> dropout x2 -> + residual in one launch (A:272, A:294)
@@ -1064,15 +1009,8 @@ class Engine:
         z = a["zn"]
         if cfg.use_cross_attention:
             # D:966-974: both directions in one launch each (kv_shift = B pairs window b with b+B)
-            xs = _layer_sites(Lr)
-            self.qkv_proj(z, "x")
-            call(attn_fwd, ptr(a["qkvx"]), ptr(a["ctxx"]), ptr(a["lsex"]), NB, S, H, B, self.dtype, p, xs["attn"],
-                 self.st_ptr, st)
-            self._probs_hook(self.model.cross_attn.cross_attn.dropout, a["qkvx"], a["lsex"], B)
-            self.gemm(ptr(a["ctxx"]), ptr(w["ox"]), ptr(a["rx"]), M, d, d, bias=fp.p_ptr("cross_attn.cross_attn.out_proj.bias"),
-                      drop1=(p, xs["drop1"]), residual=ptr(z))
-            call("eg_layernorm_fwd", ptr(a["rx"]), fp.p_ptr("cross_attn.norm.weight"), fp.p_ptr("cross_attn.norm.bias"),
-                 ptr(a["zc"]), ptr(a["stx"]), M, d, self.dtype, st)
+            self.attn_unfused_fwd(z, "x", B, _layer_sites(Lr), p)
+            self.ln_fwd(a["rx"], "cross_attn.norm", a["zc"], a["stx"])
             z = a["zc"]
         self.z_final = z
         # heads (D:1193-1213)
@@ -1099,15 +1037,22 @@ class Engine:
                  lab, ptr(a["ibs_logits"]), ptr(a["ibs_sloss"]), ptr(a["ibs_loss"]), B, d // 2, cfg.num_classes, self.dtype, st)
         self.labels = labels
 
+    @staticmethod
+    def _wgrad_pieces(listening: bool) -> bool:
+        """Whether backward cuts the grouped weight-gradient launch in two pieces (see wgrad_plan.plan): with a gradient reducer
+        listening (data parallel) it does; EYEGAZE_WGRAD_PIECES=1 forces the cut without a reducer (bit-identity tests), =0
+        forbids it.  The one switch read per backward and not at construction: tests flip it on a live engine."""
+        pcs = os.environ.get("EYEGAZE_WGRAD_PIECES", "")
+        return pcs != "0" and (listening or pcs == "1")
+
     def _fused_heads(self, backward: bool = False) -> bool:
         """the fused head kernels cover 16-bit compute dtypes at d_model == 256 with at most 16 classes; their in-launch weight
         gradients (backward) sum at most 256 samples, and need classifier.0 / symmetric_fusion.proj each laid out as weight then
         bias in the flat gradient buffer (as eg_gemm_tn's fused-bias reduce does)"""
         ok = bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model == 256 and self.cfg.num_classes <= 16
         if ok and backward:
-            o, d = self.fp.offsets, self.cfg.d_model
-            ok = self.B <= 256 and all(o[n + ".bias"] == o[n + ".weight"] + 3 * d * d
-                                       for n in ("classifier.0", "symmetric_fusion.proj"))
+            d = self.cfg.d_model
+            ok = self.B <= 256 and all(self._packed([n], d, 3 * d) for n in ("classifier.0", "symmetric_fusion.proj"))
         return ok
 
     # ------------------------------------------------------------------------------------------
@@ -1136,18 +1081,15 @@ class Engine:
             gibs_logits, gibs_token = sc_(gibs_logits), sc_(gibs_token)
         # ---- heads ----
         fused_heads = self._fused_heads(backward=True)
+        # fused -- launch 1: CE backward rows + classifier.3's gradients; launch 2: both backward-data products chained per 16
+        # samples + classifier.0's gradients; (launch 3, below: pool backward + symmetric_fusion.proj's gradients)
+        call("eg_classifier_ce_bwd_fused" if fused_heads else "eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"),
+             ptr(a["logits"]), lab, ptr(gloss), ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
+             fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
         if fused_heads:
-            # launch 1: CE backward rows + classifier.3's gradients; launch 2: both backward-data products chained per 16
-            # samples + classifier.0's gradients; (launch 3, below: pool backward + symmetric_fusion.proj's gradients)
-            call("eg_classifier_ce_bwd_fused", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), ptr(a["logits"]), lab, ptr(gloss),
-                 ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
-                 fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
             call("eg_heads_bwd_chain", ptr(g["dhcl"]), ptr(w["c0T"]), ptr(w["sfT"]), ptr(a["zf"]), ptr(g["dzf"]), ptr(g["dcomb"]),
                  fp.g_ptr("classifier.0.weight"), fp.g_ptr("classifier.0.bias"), B, d, self.dtype, st)
         else:
-            call("eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), ptr(a["logits"]), lab, ptr(gloss),
-                 ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
-                 fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
             self.gemm(ptr(g["dhcl"]), ptr(w["c0T"]), ptr(g["dzf"]), B, 3 * d, d)
             self.wgrad(ptr(g["dhcl"]), ptr(a["zf"]), 0, B, d, 3 * d, linear=["classifier.0"])
             self.gemm(ptr(g["dzf"]), ptr(w["sfT"]), ptr(g["dcomb"]), B, 3 * d, d, a=rowmap(3 * d))
@@ -1178,29 +1120,25 @@ class Engine:
         other = g["dzB"]
 
         grouped = self._wgrad_group_plan() is not None
-        # with a gradient reducer listening (data parallel) the grouped launch is cut in two pieces (see _wgrad_group_plan);
-        # EYEGAZE_WGRAD_PIECES=1 forces the cut without a reducer (bit-identity tests), =0 forbids it
-        pcs = os.environ.get("EYEGAZE_WGRAD_PIECES", "")
-        pieced = grouped and len(self._wg_plan["pieces"]) == 2 and pcs != "0" and (on_segment is not None or pcs == "1")
+        pieced = grouped and len(self._wg_plan["pieces"]) == 2 and self._wgrad_pieces(on_segment is not None)
 
-        def attn_block_bwd(pre, l, x_in, dr, drm, kv_shift, site_attn, dx_out, dqkv, defer, dctx_done=False):
+        def attn_block_bwd(l, x_in, dr, drm, kv_shift, site_attn, dx_out, dqkv, defer, dctx_done=False):
             """dr: grad of the pre-LN sum (residual path), drm: same, masked by the branch dropout."""
+            pre, qkv, lse, ctx, _ = self._attn_stage(l)
             names = [pre + n for n in ("q_proj", "k_proj", "v_proj")]
             if not defer:
-                self.wgrad(ptr(drm), ptr(a[f"ctx{l}"]), 0, M, d, d, linear=[pre + "out_proj"])
+                self.wgrad(ptr(drm), ptr(ctx), 0, M, d, d, linear=[pre + "out_proj"])
             if not dctx_done:       # (eg_ln_bwd_proj has written dctx together with dr / drm)
                 self.gemm(ptr(drm), ptr(w[f"oT{l}"]), ptr(g["dctx"]), M, d, d)
-            if self.attn_long:
-                call("eg_attention_long_bwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(g["dctx"]), ptr(a[f"lse{l}"]), ptr(dqkv),
-                     NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, ptr(g["attn_delta"]), g["attn_delta"].numel(), st)
-            else:
-                call("eg_attention_bwd", ptr(a[f"qkv{l}"]), ptr(a[f"ctx{l}"]), ptr(g["dctx"]), ptr(a[f"lse{l}"]), ptr(dqkv),
-                     NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, st)
+            delta = (ptr(g["attn_delta"]), g["attn_delta"].numel()) if self.attn_long else ()    # (the long core's scratch)
+            call("eg_attention_long_bwd" if self.attn_long else "eg_attention_bwd", ptr(qkv), ptr(ctx), ptr(g["dctx"]), ptr(lse),
+                 ptr(dqkv), NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, *delta, st)
             if not defer:
                 self.wgrad(ptr(dqkv), ptr(x_in), 0, M, 3 * d, d, linear=names)
             self.gemm(ptr(dqkv), ptr(w[f"qkvT{l}"]), ptr(dx_out), M, d, 3 * d, residual=ptr(dr))
 
         has_drop = p > 0
+        dY1 = g["drm"] if has_drop else g["dr"]     # ungrouped route: ONE buffer for the masked gradient that enters a branch
         gx = False
         # no reducer waits for the encoder.norm / cross buckets: the gain / bias partials of the two norms outside the layers
         # are summed by the grouped reduce launch at the end of backward instead of a 16-workgroup launch each
@@ -1209,16 +1147,9 @@ class Engine:
         if cfg.use_cross_attention:
             xs = _layer_sites(Lr)
             gx = grouped and self._wg_cross                     # its weight gradients ride in the grouped launch
-            drm = g["dYo_x"] if gx else (g["drm"] if has_drop else g["dr"])
-            if has_drop:
-                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", g["dr"], drm, d1=(p, xs["drop1"]),
-                            slot=nslot("cross_attn.norm"))
-                drx = g["dr"]
-            else:
-                self.ln_bwd(dz, a["rx"], a["stx"], "cross_attn.norm", drm, None, slot=nslot("cross_attn.norm"))
-                drx = drm
-            attn_block_bwd("cross_attn.cross_attn.", "x", a["zn"], drx, drm, B, xs["attn"], other,
-                           g["dqkv_x"] if gx else g["dqkv"], gx)
+            drm = g["dYo_x"] if gx else dY1
+            drx = self.ln_bwd_residual(dz, a["rx"], a["stx"], "cross_attn.norm", drm, (p, xs["drop1"]), slot=nslot("cross_attn.norm"))
+            attn_block_bwd("x", a["zn"], drx, drm, B, xs["attn"], other, g["dqkv_x"] if gx else g["dqkv"], gx)
             dz, other = other, dz
             if not gx:
                 seg("cross")
@@ -1229,18 +1160,14 @@ class Engine:
         for l in reversed(range(Lr)):
             pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
             # with the grouped weight-gradient launch every layer keeps its own dY operands until the end of backward
-            dYf = g[f"dYf{l}"] if grouped else (g["drm"] if has_drop else g["dr"])
-            dYo = g[f"dYo{l}"] if grouped else (g["drm"] if has_drop else g["dr"])
+            dYf = g[f"dYf{l}"] if grouped else dY1
+            dYo = g[f"dYo{l}"] if grouped else dY1
             dh = g[f"dh{l}"] if grouped else g["dh"]
             dqkv = g[f"dqkv{l}"] if grouped else g["dqkv"]
             s2 = self._ln_slot[pre + "ln2"] if grouped else None
             s1 = self._ln_slot[pre + "ln1"] if grouped else None
-            if has_drop:
-                self.ln_bwd(dz, a[f"r2_{l}"], a[f"st2_{l}"], pre + "ln2", g["dr"], dYf, d1=(p, sites["ffn_b"]),
-                            d2=(p, sites["drop2"]), slot=s2)
-            else:
-                self.ln_bwd(dz, a[f"r2_{l}"], a[f"st2_{l}"], pre + "ln2", dYf, None, slot=s2)
-            dr = g["dr"] if has_drop else dYf
+            dr = self.ln_bwd_residual(dz, a[f"r2_{l}"], a[f"st2_{l}"], pre + "ln2", dYf, (p, sites["ffn_b"]), (p, sites["drop2"]),
+                                      slot=s2)
             if not grouped:
                 self.wgrad(ptr(dYf), ptr(a[f"hff{l}"]), 0, M, d, F, linear=[pre + "ffn.linear2"])
             if self.fuse_ffn:
@@ -1259,34 +1186,19 @@ class Engine:
                                  d1=(p, sites["drop1"]) if has_drop else (0.0, 0), slot=s1)
                 dr = g["dr"]
             else:
-                if has_drop:
-                    self.ln_bwd(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", g["dr"], dYo, d1=(p, sites["drop1"]), slot=s1)
-                else:
-                    self.ln_bwd(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", dYo, None, slot=s1)
-                dr = g["dr"] if has_drop else dYo
-            attn_block_bwd(pre + "mha.", l, a[f"x{l}"], dr, dYo, 0, sites["attn"], other, dqkv, grouped, dctx_done=self.ln_proj)
+                dr = self.ln_bwd_residual(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", dYo, (p, sites["drop1"]), slot=s1)
+            attn_block_bwd(l, a[f"x{l}"], dr, dYo, 0, sites["attn"], other, dqkv, grouped, dctx_done=self.ln_proj)
             dz, other = other, dz
             if not grouped:
                 seg(f"layer{l}")
             elif pieced and l == self._wg_plan["split_layer"]:
                 # upper half of the encoder: its weight gradients are complete -> reduce them now, hand the buckets to the
                 # all-reduce while the lower layers' backward-data chain keeps the compute stream busy
-                self._wgrad_group_launch(self._wg_plan["pieces"][0])
-                if gx:
-                    seg("cross")
-                for ll in reversed(self._wg_plan["pieces"][0]["layers"]):
-                    seg(f"layer{ll}")
-        if grouped:
-            if pieced:
-                self._wgrad_group_launch(self._wg_plan["pieces"][1])
-                for ll in reversed(self._wg_plan["pieces"][1]["layers"]):
-                    seg(f"layer{ll}")
-            else:
-                self._wgrad_group_launch(self._wg_plan["whole_norms"] if defer_norms else None)
-                if gx:
-                    seg("cross")
-                for l in reversed(range(Lr)):
-                    seg(f"layer{l}")
+                self._wgrad_group_launch(self._wg_plan["pieces"][0], seg, gx)
+        if grouped and pieced:
+            self._wgrad_group_launch(self._wg_plan["pieces"][1], seg)
+        elif grouped:
+            self._wgrad_group_launch(self._wg_plan["whole_norms"] if defer_norms else None, seg, gx)
         dseq = dz
         # positional table / cls token (A:120-126, D:1157)
         # conv1 backward: dY = dseq[:, off:, :] * relu/dropout gate
@@ -1318,10 +1230,16 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # gradient accumulation: one optimiser step from several micro-batches (no reference counterpart: T is one batch per step)
     # ------------------------------------------------------------------------------------------
+    def _sqpart(self) -> torch.Tensor:
+        """squared-norm partials of the flat gradient buffer (SQ_BLOCKS floats), made on first use"""
+        if "sqpart" not in self.g:
+            self.g["sqpart"] = self._t(self.SQ_BLOCKS, dtype=torch.float32)
+        return self.g["sqpart"]
+
     def bucket_ranges(self) -> Dict[str, Tuple[int, int]]:
         """ddp.bucket_ranges of this model: segment name (as backward's on_segment emits it) -> [begin, end) in floats."""
         key = self.fp.grad.data_ptr()
-        if getattr(self, "_ranges_key", None) != key:
+        if self._ranges_key != key:
             from .ddp import bucket_ranges
             fp = self.fp
             self._ranges = bucket_ranges(fp.names, fp.offsets, fp.total, self.cfg.num_layers, self.cfg.use_cross_attention)
@@ -1346,11 +1264,7 @@ class Engine:
             b, e = rg[segment]
             if norm:
                 raise L.EgError("accumulate: the fused norm partials cover the whole buffer, not one bucket")
-        sq = 0
-        if norm:
-            if "sqpart" not in self.g:
-                self.g["sqpart"] = self._t(self.SQ_BLOCKS, dtype=torch.float32)
-            sq = ptr(self.g["sqpart"])
+        sq = ptr(self._sqpart()) if norm else 0
         self._acc_norm_ready = False
         if e > b:
             call("eg_grad_accumulate", ptr(acc) + 4 * b, ptr(self.fp.grad) + 4 * b, e - b, int(bool(first)), sq,
@@ -1368,9 +1282,7 @@ class Engine:
         eg_grad_sqnorm's pass over the buffer is not repeated."""
         self._alloc_bwd()
         self.stream = self._cur_stream()
-        nblk = self.SQ_BLOCKS
-        if "sqpart" not in self.g:
-            self.g["sqpart"] = self._t(nblk, dtype=torch.float32)
+        nblk, sq = self.SQ_BLOCKS, ptr(self._sqpart())
         if accumulated and self.fp.acc is None:
             raise L.EgError("optimizer_step(accumulated=True) without a preceding Engine.accumulate")
         if norm_ready and not (accumulated and self._acc_norm_ready):
@@ -1379,12 +1291,12 @@ class Engine:
         self._acc_norm_ready = False
         if norm_ready or not self.fused_norm_clip:
             if not norm_ready:
-                call("eg_grad_sqnorm", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, self.stream)
-            call("eg_clip_coef", ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr, self.stream)
+                call("eg_grad_sqnorm", ptr(grad), self.fp.total, sq, nblk, self.stream)
+            call("eg_clip_coef", sq, nblk, max_norm, self.st_ptr, self.stream)
         else:       # squared-norm partials and the coefficient in one launch (the last workgroup to finish sums the partials)
             if "sq_ctr" not in self.g:
                 self.g["sq_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)
-            call("eg_grad_sqnorm_clip", ptr(grad), self.fp.total, ptr(self.g["sqpart"]), nblk, max_norm, self.st_ptr,
+            call("eg_grad_sqnorm_clip", ptr(grad), self.fp.total, sq, nblk, max_norm, self.st_ptr,
                  ptr(self.g["sq_ctr"]), self.stream)
         call("eg_adamw", ptr(self.fp.flat), ptr(grad), ptr(m), ptr(v), self.fp.total, betas[0], betas[1], eps,
              weight_decay, self.st_ptr, self.stream)

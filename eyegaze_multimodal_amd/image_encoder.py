@@ -19,8 +19,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import tokens
-from ._lib import EG_BF16, EG_F16, EG_F32, call, ptr, rowmap
-from .engine import Engine, FlatParams
+from ._lib import call, ptr, rowmap
+from .engine import EngineBase, FlatParams
 
 
 class _CNN(nn.Module):
@@ -56,40 +56,29 @@ class GazeCNNEncoder(nn.Module):
         return self._engines[key]
 
 
-class ImageEngine(Engine):
-    """Workspace + kernel sequencing of GazeCNNEncoder for a fixed (B, F, W); reuses Engine's GEMM / weight-gradient /
-    staging / optimiser plumbing, and may share the eg_step_state of another engine (`state_dev`) so that ONE global clip
+class ImageEngine(EngineBase):
+    """Workspace + kernel sequencing of GazeCNNEncoder for a fixed (B, F, W) on EngineBase's GEMM / weight-gradient /
+    staging plumbing; it may share the eg_step_state of another engine (`state_dev`) so that ONE global clip
     coefficient, ONE loss scale and ONE overflow flag govern the whole multimodal model (GradScaler + clip_grad_norm_ over
     model.parameters(), train_multimodal_fuzzy_fusion.py:462-472)."""
+    tn_cap = 8 * 1024 * 1024      # floats of g["partial"]
 
     def __init__(self, model: GazeCNNEncoder, B: int, F: int, W: int, device, dtype: int, state_dev=None):
         if F % 8 or (W // 2) % 4 or W < 8:
             raise L.EgError(f"image {F}x{W} unsupported: F % 8 == 0 and floor(W/2) % 4 == 0 required")
-        self.model, self.B, self.device, self.dtype = model, B, device, dtype
+        super().__init__(model, B, device, dtype)
         self.cfg = SimpleNamespace(d_model=model.d_model, num_classes=model.num_classes)
-        self.tdtype = {EG_BF16: torch.bfloat16, EG_F16: torch.float16, EG_F32: torch.float32}[dtype]
-        self.es = 4 if dtype == EG_F32 else 2
-        self.bk = 32 if dtype == EG_F32 else 64
-        self.fp = model._flat
-        self.stream, self.probes, self.probe_all = 0, {}, None
-        self.cus = torch.cuda.get_device_properties(device).multi_processor_count if torch.device(device).type == "cuda" else 256
-        self._shared_state = state_dev
-        self._recording, self._plan = False, []
-        self.scaler_on = False
-        self.scaler_cfg = dict(init_scale=65536.0, growth=2.0, backoff=0.5, growth_interval=2000)
-        self.a, self.w, self.g = {}, {}, {}
+        # no convolution layouts to carry and no fused tail: the short eg_pack_table.  Loss scaling is the sharing trainer's
+        # business (MultimodalTrainer._engines copies the EEG engine's scaler_on)
+        self.fused_tail, self.scaler_on = False, False
         d, nc = model.d_model, model.num_classes
         tokens.spec_cnn_alloc(self, 2 * B, F, W)
         self.a["feat"] = self._t(2 * B, d)                     # image order (b, player): a row pair IS the head's input row
         self.a["logits"] = self._t(B, nc, dtype=torch.float32)
         self.a["sloss"] = self._t(B, dtype=torch.float32)
         self.a["loss"] = self._t(1, dtype=torch.float32)
-        if state_dev is None:
-            self.state_dev = torch.zeros(L.STATE_WORDS, dtype=torch.int32, device=device)
-            self.set_state(seed=0, lr=0.0, step=1, reset_scaler=2)
-        else:
-            self.state_dev = state_dev
         self.train_p01 = 0.0
+        self._init_state(state_dev)
 
     def _alloc_bwd(self):
         if self.g:
@@ -99,7 +88,6 @@ class ImageEngine(Engine):
         tokens.spec_cnn_alloc_bwd(self)
         g["dfeat"] = self._t(2 * B, d)
         g["dlogits"] = self._t(B, self.cfg.num_classes, dtype=torch.float32)
-        self.tn_cap = 8 * 1024 * 1024
         g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
         g["cspart"] = self._t(512 * 1024, dtype=torch.float32)
 

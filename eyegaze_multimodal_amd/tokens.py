@@ -3,7 +3,6 @@ synchrony (IBS) tokens, matrix form (D:473-911) or scalar form (D:178-470).  Cal
 module hooks; every op is a C-ABI kernel (signal.hip, spec.hip, gemm.hip).  D = dual_eeg_transformer.py."""
 from __future__ import annotations
 
-import os
 import ctypes as C
 
 import numpy as np
@@ -11,10 +10,8 @@ import torch
 
 from . import _lib as L
 from ._lib import EG_F32, call, ptr, rowmap
-from .engine import SITE_IBSGEN, SITE_IBSTOK, SITE_SPEC, Engine, _align
+from .engine import SITE_IBSGEN, SITE_IBSTOK, SITE_SPEC, Engine
 
-CONV2_FWD_FLAT = os.environ.get("EYEGAZE_CONV2_FLAT", "1") != "0"           # 0: conv-2 forward / backward-data as segmented-row eg_gemm_nt
-CONV2_WGRAD_FLAT = os.environ.get("EYEGAZE_CONV2_WGRAD_FLAT", "1") != "0"   # 0: the conv-2 weight gradient as an im2col eg_gemm_tn
 ROBUST_BANDS = [(0.5, 45.0), (0.5, 4.0), (4.0, 8.0), (8.0, 13.0), (13.0, 30.0), (30.0, 45.0)]  # D:500-507
 SCALAR_BANDS = [(4.0, 8.0), (8.0, 13.0), (13.0, 30.0), (30.0, 45.0)]                           # D:201-206
 
@@ -96,7 +93,6 @@ def _alloc_bwd(model, eng: Engine):
     cfg, d, B = eng.cfg, eng.cfg.d_model, eng.B
     g = eng.g
     if cfg.use_spectrogram:
-        sp = eng.sp
         spec_cnn_alloc_bwd(eng)
     if cfg.use_ibs:
         if cfg.use_robust_ibs:
@@ -209,7 +205,7 @@ def forward(model, eng: Engine, eeg1, eeg2, train: bool):
         call("eg_rows_copy", ptr(a["x0"]), S, d, n_ibs, 1, 0, B, B, dt, st)
     if cfg.use_spectrogram:
         sp, pre = eng.sp, "spectrogram_generator."
-        F, nfr, Hp, Wp, nimg = sp["F"], sp["nfr"], sp["Hp"], sp["Wp"], sp["nimg"]
+        F, nfr = sp["F"], sp["nfr"]
         win = model.spectrogram_generator.window
         for i, x in enumerate((eeg1, eeg2)):
             call("eg_stft_logmag", ptr(x), ptr(win), ptr(a["spimg"]) + i * B * Cn * F * nfr * 4, B * Cn, T, cfg.spec_n_fft,
@@ -217,6 +213,12 @@ def forward(model, eng: Engine, eeg1, eeg2, train: bool):
         off = (1 + n_ibs) * d * es
         spec_cnn_forward(eng, pre, p01, model.spectrogram_generator.spec_conv[3], ptr(a["x0"]) + off, rowmap(d, S * d, Cn),
                          rowmap(d, 0, Cn), ptr(w["pos"]) + off)
+
+
+def _conv2_flat(eng) -> bool:
+    """conv-2 on the flat-correlation kernels of csrc/spec.hip: 16-bit operands, and two image rows + 2 pixels fit their LDS halo.
+    Else (fp32, wider images) the segmented-row eg_gemm_nt / im2col eg_gemm_tn, which re-read every pixel twelve times through L2."""
+    return eng.dtype != EG_F32 and 2 * (eng.sp["Wp"] + 4) + 2 <= 64
 
 
 def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
@@ -230,7 +232,7 @@ def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
     call("eg_spec_conv1_fwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
          ptr(a["sp_p1"]), nimg, F, nfr, dt, st)
     row = (Wp + 4) * 32
-    if dt != L.EG_F32 and CONV2_FWD_FLAT and 2 * (Wp + 4) + 2 <= 64:
+    if _conv2_flat(eng):
         # 16-bit operands: nine row offsets of one LDS image of p1 (csrc/spec.hip) instead of a segmented-row product that re-reads
         # every pixel twelve times through L2
         Q = nimg * (Hp + 2) * (Wp + 4)
@@ -305,7 +307,7 @@ def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01):
     eng.gemm(ptr(g["sp_dhp0"]), ptr(w["spp0T"]), ptr(g["sp_dpooled"]), nimg, 1024, 2 * d)
     call("eg_spec_avgpool_bwd", ptr(a["sp_out2"]), ptr(g["sp_dpooled"]), ptr(g["sp_d2"]), nimg, Hp, Wp, dt, st)
     row32, row64 = (Wp + 4) * 32, (Wp + 4) * 64
-    if dt != L.EG_F32 and CONV2_WGRAD_FLAT and 2 * (Wp + 4) + 2 <= 64:   # (the kernel's LDS halo holds two image rows + 2 pixels)
+    if _conv2_flat(eng):
         # 16-bit operands: the flat correlation (csrc/spec.hip) reads every activation / gradient byte once; the im2col product below
         # fetched p1 twelve times and d2 three times through L2 (0.93 ms of the C = 32 step)
         Q = nimg * (Hp + 2) * (Wp + 4)
@@ -319,7 +321,7 @@ def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01):
         eng.wgrad(ptr(g["sp_d2"]) + (row64 + 64) * es, ptr(a["sp_p1"]), fp.g_ptr(pre + "spec_conv.3.weight"), rows, 64, 384,
                   y=rowmap(64, row64, Wp), x=rowmap(32, row32, Wp), x_tile_stride=row32, conv2d=(64, 32),
                   out_b=fp.g_ptr(pre + "spec_conv.3.bias"))
-    if dt != L.EG_F32 and CONV2_FWD_FLAT and 2 * (Wp + 4) + 2 <= 64:
+    if _conv2_flat(eng):
         Q = nimg * (Hp + 2) * (Wp + 4)
         call("eg_conv2d_flat", ptr(g["sp_d2"]), ptr(w["spc2T"]), 0, ptr(g["sp_dp1"]), Q, Q + 4 * (Wp + 4), Wp + 4, Wp, 64, 32, L.ACT_NONE,
              2 * eng.cus, dt, st)
@@ -365,10 +367,8 @@ def backward(model, eng: Engine, dseq):
         eng.wgrad(ptr(g["ig_dh"]), ptr(a["ig_featp"]), fp.g_ptr(pre + "0.weight"), B, 2 * d, 64, out_b=fp.g_ptr(pre + "0.bias"),
                   conv=(28, 1, 28))
     if cfg.use_spectrogram:
-        sp, pre = eng.sp, "spectrogram_generator."
-        F, nfr, Hp, Wp, nimg, rows = sp["F"], sp["nfr"], sp["Hp"], sp["Wp"], sp["nimg"], sp["rows"]
         off = (1 + n_ibs) * d * es
-        spec_cnn_backward(eng, pre, ptr(dseq) + off, rowmap(d, S * d, Cn), sc01)
+        spec_cnn_backward(eng, "spectrogram_generator.", ptr(dseq) + off, rowmap(d, S * d, Cn), sc01)
 
 
 def fire_spec_backward_hooks(model, eng: Engine):

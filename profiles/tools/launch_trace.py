@@ -1,0 +1,186 @@
+"""Launch trace of the step engines on the CPU: every C-ABI launch a forward / backward / optimiser step would issue, recorded
+instead of issued, with addresses rewritten as [tensor name, byte offset] so that two processes (two checkouts) agree.
+
+    python profiles/tools/launch_trace.py --repo PATH --out FILE.json
+
+Two trees issue the same launches with the same arguments exactly when their files are identical (`cmp`).  The library must be
+built in PATH (the host-side audit of the pack table, eg_attn_block_ok and the other shape queries really run)."""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import pkgutil
+import sys
+
+TABLES = ("plan_dev", "wg.")       # tensors that hold a launch's table: their bytes are part of the launch
+
+
+class Recorder:
+    def __init__(self, real):
+        self.real, self.rows, self.engines, self.extra = real, [], [], []
+
+    def known(self):
+        """(lo, hi, name, tensor) of every workspace / parameter / table tensor alive now (backward allocates lazily)"""
+        out = {}
+        for tag, e in self.engines:
+            for kind in ("a", "w", "g"):
+                out.update({f"{tag}{kind}.{k}": v for k, v in getattr(e, kind).items()})
+            out.update({tag + "flat": e.fp.flat, tag + "grad": e.fp.grad, tag + "acc": e.fp.acc, tag + "state": e.state_dev,
+                        tag + "plan_dev": getattr(e, "_plan_dev", None)})
+            plan = getattr(e, "_wg_plan", None)
+            if isinstance(plan, dict):
+                parts = [("whole", plan), ("norms", plan["whole_norms"])] + [(f"piece{i}", p) for i, p in enumerate(plan["pieces"])]
+                out.update({f"{tag}wg.{n}.{k}": p[k] for n, p in parts if p for k in ("tp", "rt")})
+        for fn in self.extra:
+            out.update(fn())
+        return [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), n, t) for n, t in out.items()
+                if hasattr(t, "data_ptr") and t.numel()]
+
+    def addr(self, v, known, raw=False):
+        for lo, hi, n, t in known:
+            if lo <= v < hi:
+                return [n, v - lo], (t if v == lo and any(s in n for s in TABLES) else None)
+        return (v if raw or v < (1 << 32) else "?"), None       # a temporary's address: no two runs agree on it
+
+    def words(self, b, known):
+        """a structure's bytes as 8-byte words, those that point into a known tensor rewritten"""
+        out = [self.addr(int.from_bytes(b[i:i + 8], "little"), known, raw=True)[0] for i in range(0, len(b) - len(b) % 8, 8)]
+        return out + ([b[len(b) - len(b) % 8:].hex()] if len(b) % 8 else [])
+
+    def __call__(self, name, *args):
+        known, row = self.known(), [name]
+        for a in args:
+            if isinstance(a, bool) or a is None or isinstance(a, str):
+                row.append(a)
+            elif isinstance(a, int):
+                v, table = self.addr(a, known)
+                row.append(v)
+                if table is not None:
+                    row.append({"table": self.words(bytes(table.numpy()), known)})
+            elif isinstance(a, float):
+                row.append(repr(a))
+            elif isinstance(a, C.c_void_p):
+                row.append("?")
+            elif hasattr(a, "_obj") or isinstance(a, (C.Structure, C.Array, C._SimpleCData)):
+                row.append({"bytes": self.words(bytes(getattr(a, "_obj", a)), known)})
+            else:
+                raise TypeError(f"{name}: argument {a!r}")
+        self.rows.append(row)
+        if name == "eg_pack_table_ex_check":
+            self.real(name, *args)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--repo", required=True)
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.repo))
+    import torch
+    import eyegaze_multimodal_amd as pkg
+    from eyegaze_multimodal_amd import _lib as L
+    for m in pkgutil.iter_modules(pkg.__path__):
+        if not m.name.startswith(("lib", "build")):     # (the shared library itself is listed as a module)
+            importlib.import_module(f"{pkg.__name__}.{m.name}")
+    from eyegaze_multimodal_amd import DualEEGTransformer
+    from eyegaze_multimodal_amd.engine import Engine
+    from eyegaze_multimodal_amd.fuzzy_gating_fusion import FuzzyGatingFusion
+    from eyegaze_multimodal_amd.image_encoder import GazeCNNEncoder, ImageEngine
+    from eyegaze_multimodal_amd.train_multimodal_fuzzy_fusion import MultimodalFusionModel, MultimodalTrainer
+    rec = Recorder(L.call)
+    for name, mod in list(sys.modules.items()):
+        if name.startswith(pkg.__name__) and getattr(mod, "call", None) is rec.real:
+            mod.call = rec
+    cpu, cases = torch.device("cpu"), {}
+    DT = dict(bf16=L.EG_BF16, fp16=L.EG_F16, f32=L.EG_F32)
+    SMALL = dict(use_spectrogram=False, use_ibs=False)
+    LONG = dict(SMALL, max_len=512)
+
+    def case(name, fn, env=None):
+        old = {k: os.environ.get(k) for k in env or {}}
+        os.environ.update(env or {})
+        rec.rows, rec.engines, rec.extra = [], [], []
+        try:
+            fn()
+        finally:
+            for k, v in old.items():
+                os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
+        cases[name] = rec.rows
+
+    def eeg(dt, B=32, T=1024, train=True, attrs=None, mode="step", bwd=None, **kw):
+        def run():
+            model = DualEEGTransformer(**{**dict(in_channels=8, max_len=256), **kw})
+            model._flat.ensure(cpu)
+            eng = Engine(model, B, T, cpu, DT[dt])
+            for k, v in (attrs or {}).items():
+                assert hasattr(eng, k), k
+                setattr(eng, k, v)
+            x, y = torch.zeros(B, 8, T), torch.zeros(B, dtype=torch.long)
+            m, v = torch.zeros(eng.fp.total), torch.zeros(eng.fp.total)
+            rec.engines = [("", eng)]
+            rec.extra = [lambda: dict(x=x, labels=y, m=m, v=v)]
+            one = torch.ones(1)
+            for i in range(2 if mode == "accum" else 1):
+                eng.forward(x, x, y, train=train)
+                eng.backward(gloss=one, gloss_ibs=(one if model.cfg.use_ibs else None), **(bwd or {}))
+                if mode == "accum":
+                    eng.accumulate(i == 0, norm=(i == 1))
+            if mode == "overflow":
+                eng.check_overflow_and_update_scaler()
+            else:
+                eng.optimizer_step(m, v, **(dict(accumulated=True, norm_ready=True) if mode == "accum" else {}))
+        return run
+
+    def image(dt):
+        def run():
+            model = GazeCNNEncoder(compute_dtype=dt)
+            model._flat.ensure(cpu)
+            eng = ImageEngine(model, 4, 64, 64, cpu, DT[dt])
+            img, gl = torch.zeros(4, 64, 64), torch.ones(4, 3)
+            rec.engines, rec.extra = [("", eng)], [lambda: dict(img=img, glogits=gl)]
+            eng.forward(img, img, True)
+            eng.backward(gl)
+        return run
+
+    def trainer():
+        model = MultimodalFusionModel(GazeCNNEncoder(num_classes=3, d_model=64, compute_dtype="bf16"),
+                                      DualEEGTransformer(in_channels=8, max_len=256, compute_dtype="bf16", **SMALL),
+                                      FuzzyGatingFusion(num_classes=3, mode="full"))
+        tr = MultimodalTrainer(model, cpu)
+        x, img, y = torch.zeros(4, 8, 1024), torch.zeros(4, 64, 16), torch.zeros(4, dtype=torch.long)
+        rec.engines = [("eeg.", model.eeg_encoder.engine(4, 1024, cpu))]
+        rec.engines.append(("img.", model.gaze_encoder.engine(4, 64, 16, cpu, state_dev=rec.engines[0][1].state_dev)))
+        rec.extra = [lambda: dict(x=x, img=img, labels=y, fus_flat=tr.fus.flat, fus_grad=tr.fus.grad, sqpart=tr.sqpart),
+                     lambda: {f"lw.{k}": t for w in tr._lw.values() for k, t in w.items()},
+                     lambda: {f"{s}.{i}": t for s, mv in tr.state.items() for i, t in enumerate(mv)}]
+        tr.train_step(img, img, x, x, y)
+
+    for dt in ("bf16", "fp16", "f32"):
+        case(f"a_{dt}", eeg(dt))
+    for dt in ("bf16", "f32"):
+        case(f"b_B4_{dt}", eeg(dt, B=4))
+        case(f"i_image_{dt}", image(dt))
+    case("c_small", eeg("bf16", **SMALL))
+    case("c_small_nocross", eeg("bf16", use_cross_attention=False, **SMALL))
+    case("d_long", eeg("bf16", B=2, T=4096, **LONG))
+    case("e_eval", eeg("bf16", train=False))
+    listen = dict(on_segment=lambda n: None)
+    case("f_listener", eeg("bf16", bwd=listen))
+    case("f_listener_pieces0", eeg("bf16", bwd=listen), env={"EYEGAZE_WGRAD_PIECES": "0"})
+    case("f_pieces1", eeg("bf16"), env={"EYEGAZE_WGRAD_PIECES": "1"})
+    for k in ("EYEGAZE_ATTN_BLOCK", "EYEGAZE_LN_FUSE", "EYEGAZE_CONV1_BWD_BATCH"):
+        case(f"g_{k}=0", eeg("bf16", **SMALL), env={k: "0"})
+    for k, v in dict(fuse_ffn=False, ln_proj=False, fused_tail=False, pack_unused=True, fused_norm_clip=True).items():
+        case(f"g_{k}={v}", eeg("bf16", attrs={k: v}, **SMALL))
+    case("h_accum", eeg("bf16", mode="accum"))
+    case("h_fp16_overflow", eeg("fp16", mode="overflow"))
+    case("j_multimodal_trainer", trainer)
+    with open(args.out, "w") as f:
+        json.dump(cases, f, indent=0)
+    print(json.dumps({"cases": len(cases), "rows": sum(len(r) for r in cases.values()),
+                      "per_case": {k: len(v) for k, v in cases.items()}}))
+
+
+if __name__ == "__main__":
+    main()
