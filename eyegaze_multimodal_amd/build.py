@@ -19,7 +19,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-res
 def _stale(obj: Path, src: Path) -> bool:
     if not obj.exists():
         return True
-    deps = [src, CSRC / "common.h", PKG.parent / "include" / "eyegaze_hip.h"]
+    deps = [src, *CSRC.glob("*.h"), PKG.parent / "include" / "eyegaze_hip.h"]
     return any(d.stat().st_mtime > obj.stat().st_mtime for d in deps)
 
 

@@ -6,7 +6,8 @@
 // As three launches (row-stream q|k|v GEMM, attention core, wide out-proj GEMM; the LayerNorm that follows is a fourth unless ln_out
 // asks for it here) the layer moved
 // x twice, q|k|v twice and ctx twice through HBM: 204 MB per layer at the benchmark size (33 280 rows).  Here a workgroup owns
-// one WINDOW (S <= 80 token rows x 256 = 40 KB in LDS for the whole launch): x is read once and is also the residual, q|k|v and
+// one WINDOW (S <= 80 token rows x 256 = 40 KB in LDS for the whole launch: the resident tile of rowtile.h, which also holds the
+// fragment order of the weights and the final epilogue's image and row steps): x is read once and is also the residual, q|k|v and
 // ctx leave the chip once as results and are consumed on chip from LDS images: 102 MB.
 //
 // Design (gfx950): one 256-thread workgroup (4 waves, one per SIMD) per window, TWO workgroups per CU (72 KB of LDS each) whose
@@ -29,20 +30,19 @@
 // of a head at S = 65), not by bandwidth; static s_setprio for the matrix phases measured no change (57.9 vs 58.2 us by HIP events).
 // Same MFMA chains, rounding points and dropout indices as the launches it replaces: q|k|v, lse, ctx and r1 are BIT-IDENTICAL
 // to eg_gemm_nt -> eg_attention_fwd -> eg_gemm_nt (tests/test_gpu_attnblock.py).
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) short ab_s16x8;
 
-constexpr int AR = 80;                         // rows of the window tile (5 MFMA row tiles): S <= 80
-constexpr int AD = 256;                        // d_model
+constexpr int AR = RT_ROWS;                    // rows of the window tile (5 MFMA row tiles): S <= 80
+constexpr int AD = RT_COLS;                    // d_model
 constexpr int AH = 8;                          // heads of 32
-constexpr int A_XT = AR * AD * 2;              // 40,960 B: the window's x rows
+constexpr int A_XT = RT_TILEB;                 // 40,960 B: the window's x rows
 constexpr int A_QK = AR * 64;                  // 5,120 B: one [80][32] image
 constexpr int A_IMGH = 2 * A_QK + 96 * 64;     // 16,384 B per head of a chunk: q | k | v (v: 96 rows, rows 80..95 stay zero)
 constexpr int A_LDS = A_XT + 2 * A_IMGH;       // 73,728 B
-constexpr int A_TP = 68;                       // fp32 image pitch of the final epilogue (floats)
 constexpr float kAScale = 0.17677669529663687f;   // 1/sqrt(32)
 
 template <typename T>
@@ -55,10 +55,6 @@ struct ABArgs {
   DropCfg da, d1;
 };
 
-__device__ __forceinline__ void ab_dma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 // [rows][32] 16-bit image, 64-B rows; the two 32-B halves of a row are swapped when (row >> 2) & 1 (csrc/attention.hip)
 __device__ __forceinline__ int ab_img_off(int row, int c4) {
   return row * 64 + ((((c4 >> 1) ^ ((row >> 2) & 1))) << 5) + ((c4 & 1) << 4);
@@ -83,12 +79,9 @@ __device__ __forceinline__ typename H16<T>::frag ab_frag_tr(const char* img, int
 }
 template <typename T>
 __device__ __forceinline__ typename H16<T>::frag ab_pack_frag(const f32x4& a, const f32x4& b) {
-  u32x4 v;
-  v[0] = H16<T>::pack2(a[0], a[1]);
-  v[1] = H16<T>::pack2(a[2], a[3]);
-  v[2] = H16<T>::pack2(b[0], b[1]);
-  v[3] = H16<T>::pack2(b[2], b[3]);
-  return __builtin_bit_cast(typename H16<T>::frag, v);
+  const float fa[4] = {a[0], a[1], a[2], a[3]}, fb[4] = {b[0], b[1], b[2], b[3]};
+  const u32x2 lo = pack4<T>(fa), hi = pack4<T>(fb);
+  return __builtin_bit_cast(typename H16<T>::frag, (u32x4){lo[0], lo[1], hi[0], hi[1]});
 }
 
 // NKTX > 0: the tile count is a compile-time constant (no wave-uniform branches inside the unrolled tile loops: the scheduler
@@ -109,35 +102,28 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
   const size_t row0 = (size_t)b * (size_t)S;     // its first token row
   const int nkt = NKTX ? NKTX : (S + 15) >> 4;   // key / query tiles in use (<= 5)
 
-  // ---- x tile: instruction q moves rows 2q, 2q+1 (lane -> row half lane/32, LDS chunk position lane%32 holding global chunk
-  //      pos ^ 2 (row & 7)); rows beyond S repeat row S-1 (finite values that never reach a stored result) ----
-  {
-    const int half = lane >> 5, pos = lane & 31;
+  // ---- x tile: rows beyond S repeat row S-1 (finite values that never reach a stored result) ----
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const int q = wn + 4 * i;
-      const int r = 2 * q + half;
-      const int row = min(r, S - 1);
-      ab_dma16((const char*)(p.X + (row0 + row) * AD) + ((pos ^ ((r & 7) << 1)) << 4), xt + q * 1024);
-    }
+  for (int i = 0; i < RT_DMA_PER_WAVE; ++i) {
+    const int row = min(rt_dma_row(wn, lane, i), S - 1);
+    rt_dma_issue((const char*)(p.X + (row0 + row) * AD), xt, wn, lane, i);
   }
   // rows 80..95 of both v images are read by the last key pair's transposed fragments and never written: zero them once
   if (tid < 128) *(u32x4*)(imgs + (tid >> 6) * A_IMGH + 2 * A_QK + 80 * 64 + (tid & 63) * 16) = (u32x4){0u, 0u, 0u, 0u};
 
-  // ---- weight fragment streams (L2 -> registers), fragment order: Wqkv [chunk c][wave][k-step s: 8][tile j: 3][lane],
-  //      Wo [chunk c][wave][k-step s: 2][tile j: 4][lane] ----
-  const T* const wqp = p.Wqkv + (size_t)wn * (8 * 3 * 512) + lane * 8;
-  const T* const wop = p.Wo + (size_t)wn * (2 * 4 * 512) + lane * 8;
+  // ---- weight fragment streams (L2 -> registers), fragment order: Wqkv 8 k-steps x 3 tiles, Wo 2 k-steps x 4 tiles ----
+  const T* const wqp = p.Wqkv + rt_frag_elem<8, 3>(0, wn, 0, 0, lane);
+  const T* const wop = p.Wo + rt_frag_elem<2, 4>(0, wn, 0, 0, lane);
   frag w1r[3][3], wor[2][4];
   auto req_w1 = [&](int c, int s, int slot) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) w1r[slot][j] = *(const frag*)(wqp + (size_t)c * (4 * 8 * 3 * 512) + (s * 3 + j) * 512);
+    for (int j = 0; j < 3; ++j) w1r[slot][j] = *(const frag*)(wqp + rt_frag_elem<8, 3>(c, 0, s, j));
   };
   auto req_wo = [&](int c) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) wor[s][j] = *(const frag*)(wop + (size_t)c * (4 * 2 * 4 * 512) + (s * 4 + j) * 512);
+      for (int j = 0; j < 4; ++j) wor[s][j] = *(const frag*)(wop + rt_frag_elem<2, 4>(c, 0, s, j));
   };
 #pragma unroll
   for (int s = 0; s < 3; ++s) req_w1(0, s, s);
@@ -164,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
     // the loop (loop-invariant address registers pushed the kernel past its 256-register budget and into scratch)
     int lv = lane;
     asm volatile("" : "+v"(lv));
-    const int l15 = lv & 15, g4 = lv >> 4, sw7 = (l15 & 7) << 1;   // chunk ^ 2 (row & 7): conflict-free under ds_read_b128's lane groups on 512-B rows (ffn.hip)
+    const int l15 = lv & 15, g4 = lv >> 4, sw7 = rt_swz(l15);
     // ================= P1: q|k|v columns of heads 2c, 2c+1 =================
     // column tile t = 3 wn + j of the chunk: head t / 6, part (t % 6) / 2 (q, k, v), 16-column half t % 2
     f32x4 acc1[5][3];
@@ -175,8 +161,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       frag xf[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) xf[i] = *(const frag*)(xt + (l15 + 16 * i) * 512 + (((4 * s + g4) ^ sw7) << 4));
+      rt_frags<T>(xt, l15, g4, sw7, s, xf);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -205,10 +190,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = acc1[i][j][q] + b1[j][q];
-        u32x2 pk;
-        pk[0] = H16<T>::pack2(v[0], v[1]);
-        pk[1] = H16<T>::pack2(v[2], v[3]);
-        *(u32x2*)(imgs + ioff[j] + ab_img_off(r, c4) + ((g4 & 1) << 3)) = pk;
+        *(u32x2*)(imgs + ioff[j] + ab_img_off(r, c4) + ((g4 & 1) << 3)) = pack4<T>(v);
       }
     }
     __syncthreads();        // (B) the chunk's q, k, v images are complete
@@ -349,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
   __syncthreads();          // every wave has left the images: they become the fp32 image of the final epilogue
 
   // ---- final epilogue (eg_gemm_nt's order): + bias, dropout, + residual (the x rows, from LDS), store ----
-  float* timg = (float*)(imgs + wn * (16 * A_TP * 4));
+  float* timg = (float*)(imgs + wn * RT_IMGB);
   const int er = lane >> 2, ec = lane & 3;
   const int n = 64 * wn + 16 * ec;
   float bv[16];
@@ -365,41 +347,20 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int r = 16 * i + er;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *(f32x4*)(timg + l15 * A_TP + 16 * j + 4 * g4) = acc2[i][j];
+    rt_image_put(timg, acc2[i], lane);
     if (16 * i >= S) break;                        // workgroup-uniform: tiles wholly beyond the window
     float v[16];
-    load8(timg + er * A_TP + 16 * ec, v);
-    load8(timg + er * A_TP + 16 * ec + 8, v + 8);
+    rt_image_get(timg, lane, v);
     if (r < S) {
       const size_t m = row0 + r;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] += bv[j];
-      if (p.d1.thresh) {
-        const uint32_t idx = (uint32_t)m * (uint32_t)AD + (uint32_t)n;
-        float (&v0)[8] = *(float (*)[8])v;
-        float (&v1)[8] = *(float (*)[8])(v + 8);
-        eg_dropout_run<8>(v0, p.d1, seed_lo, seed_hi, idx);
-        eg_dropout_run<8>(v1, p.d1, seed_lo, seed_hi, idx + 8);
-      }
-      const u32x4 e0 = *(const u32x4*)(xt + r * 512 + ((((n >> 3)) ^ ((r & 7) << 1)) << 4));
-      const u32x4 e1 = *(const u32x4*)(xt + r * 512 + ((((n >> 3) + 1) ^ ((r & 7) << 1)) << 4));
-      float rv[16];
-      load8((const T*)&e0, rv);
-      load8((const T*)&e1, rv + 8);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] += rv[j];
-      T* pc = p.R1 + m * AD + n;
-      store8(pc, v);
-      store8(pc + 8, v + 8);
-      if (LNF) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) vv[i][j] = round_store<T>(v[j]);
-      }
+      u32x4 e0, e1;
+      rt_tile_row16(xt, r, n, e0, e1);
+      rt_row_epilogue<T, LNF>(v, bv, p.d1, DropCfg{0u, 1.f, 0u}, seed_lo, seed_hi, (uint32_t)m * (uint32_t)AD + (uint32_t)n, true, e0, e1,
+                              p.R1 + m * AD + n, vv[LNF ? i : 0]);
     }
   }
   if constexpr (LNF)
-    eg_epilogue_layernorm256<T>(vv, (float*)(imgs + 4 * (16 * A_TP * 4)), wn, lane, S, row0, p.ln_gamma, p.ln_beta, p.LN_OUT, p.ln_stats);
+    eg_epilogue_layernorm256<T>(vv, (float*)(imgs + 4 * RT_IMGB), wn, lane, S, row0, p.ln_gamma, p.ln_beta, p.LN_OUT, p.ln_stats);
 }
 
 template <typename T>
@@ -412,15 +373,7 @@ static int ab_launch(const eg_attn_block_desc* d, hipStream_t s) {
   p.d1 = make_drop(d->out_drop_p, d->out_drop_site);
   p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.LN_OUT = (T*)d->ln_out; p.ln_stats = d->ln_stats;
   const bool lnf = d->ln_out != nullptr;
-#define AB_LAUNCH(N_, T_, L_)                                                                                                  \
-  do {                                                                                                                         \
-    static bool attr = false;                                                                                                  \
-    if (!attr) {                                                                                                               \
-      (void)hipFuncSetAttribute((const void*)attn_block_fwd_kernel<T, N_, T_, L_>, hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS); \
-      attr = true;                                                                                                             \
-    }                                                                                                                          \
-    hipLaunchKernelGGL((attn_block_fwd_kernel<T, N_, T_, L_>), dim3(d->NB), dim3(256), A_LDS, s, p);                           \
-  } while (0)
+#define AB_LAUNCH(N_, T_, L_) eg_launch_lds<attn_block_fwd_kernel<T, N_, T_, L_>, A_LDS>(dim3(d->NB), dim3(256), s, p)
   if (d->S == 65) { if (lnf) AB_LAUNCH(5, true, true); else AB_LAUNCH(5, true, false); }     // class token + 64 positions
   else { if (lnf) AB_LAUNCH(0, false, true); else AB_LAUNCH(0, false, false); }
 #undef AB_LAUNCH

@@ -81,6 +81,19 @@ template <> struct H16<f16_t> {
 // rounding through the storage type (identity for fp32): what a stored element reads back as
 template <typename T> __device__ __forceinline__ float round_store(float v) { return H16<T>::round(v); }
 template <> __device__ __forceinline__ float round_store<float>(float v) { return v; }
+// 4 floats -> 4 elements of the 16-bit storage type (two packed converts)
+template <typename T> __device__ __forceinline__ u32x2 pack4(const float v[4]) {
+  u32x2 o;
+  o[0] = H16<T>::pack2(v[0], v[1]);
+  o[1] = H16<T>::pack2(v[2], v[3]);
+  return o;
+}
+// the activation is a template parameter: with a run-time `act` every element carries the branch tree of erff() inline
+template <int ACT> __device__ __forceinline__ float eg_act(float v) {
+  if (ACT == EG_ACT_RELU) return fmaxf(v, 0.f);
+  if (ACT == EG_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+  return v;
+}
 
 template <typename T> struct Elem;
 template <> struct Elem<float> {
@@ -352,6 +365,29 @@ __device__ __forceinline__ void eg_ln_bwd_row8(const float (&xv)[8], const float
 __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
   const int q = nblocks >> 3, r = nblocks & 7, x = bid & 7, i = bid >> 3;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
+}
+
+// table-driven launches: the last entry with blk0 <= bid (thread 0 searches, everyone reads the answer after the barrier)
+template <typename E>
+__device__ __forceinline__ int eg_find_entry(const E* __restrict__ tab, int nent, int bid, int* slot) {
+  if (threadIdx.x == 0) {
+    int lo = 0, hi = nent - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (tab[mid].blk0 <= bid) lo = mid; else hi = mid - 1;
+    }
+    *slot = lo;
+  }
+  __syncthreads();
+  return *slot;
+}
+
+// host: launch KERN with LDS bytes of dynamic LDS; the first launch of an instantiation raises its dynamic-LDS limit
+template <auto KERN, int LDS, typename... Args>
+static inline void eg_launch_lds(dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  (void)attr;
+  hipLaunchKernelGGL(KERN, grid, block, LDS, s, args...);
 }
 
 // grouped row addressing: row r of a logical [M, *] matrix lives at

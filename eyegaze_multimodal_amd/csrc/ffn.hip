@@ -10,13 +10,14 @@
 // of LDS each): the two row halves of a CU share nothing, so they run as independent workgroups whose phases drift apart -- one's
 // MFMA bursts sit beside the other's epilogue / barrier / store phases (as one 512-thread workgroup every wave hit the same
 // barrier and the matrix pipe idled through each epilogue):
-//   * the A tile [80 x 256] stays in LDS for the whole launch (40 KB, LDS-DMA, 16-B chunks XOR-swizzled by 2 (row & 7)); it is the
+//   * the A tile [80 x 256] stays in LDS for the whole launch (40 KB: the resident tile of rowtile.h, which also holds the DMA map,
+//     the swizzle, the fragment order of the weights and the image epilogue used below); it is the
 //     B operand of every product-1 MFMA and, in the forward pass, the residual of the final epilogue (no second HBM read);
 //   * the hidden dimension is walked in chunks of 128 columns: product 1 gives a wave 80 x 32 of the chunk (5 x 2 accumulator
 //     tiles over K = 256), its epilogue writes the 16-bit chunk into one of TWO 20 KB LDS buffers (one barrier per chunk), from
 //     where (a) all threads stream it to HBM as whole 256-B row segments and (b) product 2 reads it back as the B operand of
 //     the wave's 80 x 64 part of C (5 x 4 accumulator tiles that live in registers across all chunks);
-//   * WEIGHTS NEVER TOUCH LDS: a wave's W1 / W2 fragments (pre-packed in fragment order: one contiguous 1-KB read each,
+//   * WEIGHTS NEVER TOUCH LDS: a wave's W1 / W2 fragments (pre-packed in fragment order, rt_frag_elem: one contiguous 1-KB read each,
 //     L2-resident, 1 MB per layer) go straight into registers through rolling rings four / two k-steps ahead, so the LDS pipe only carries
 //     the activation fragments: 0.5 KB per MFMA in product 1, 0.25 KB in product 2 -- below the 0.5 KB / MFMA at which LDS and
 //     matrix pipes balance, which the 128 x 128 and 160 x 256 tiles (weights through LDS) sit on;
@@ -28,17 +29,16 @@
 //     rows themselves remain accepted as the gate (eg_ffn_desc.gate) for callers without a forward launch of this kernel.
 // Arithmetic: the same k-ordered chains of v_mfma_f32_16x16x32 as eg_gemm_nt's kernels and the same epilogue order and dropout
 // indices, so H and C are bit-identical to the two-launch path.
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
-constexpr int FR = 80;                        // rows per workgroup
-constexpr int FD = 256;                       // d_model: K of product 1, N of product 2
+constexpr int FR = RT_ROWS;                   // rows per workgroup
+constexpr int FD = RT_COLS;                   // d_model: K of product 1, N of product 2
 constexpr int FC = 128;                       // hidden columns per chunk
-constexpr int F_XT = FR * FD * 2;             // 40,960 B
+constexpr int F_XT = RT_TILEB;                // 40,960 B
 constexpr int F_HT = FR * FC * 2;             // 20,480 B
 constexpr int F_LDS = F_XT + 2 * F_HT;        // 81,920 B = half the LDS of a CU
-constexpr int F_TP = 68;                      // fp32 image pitch of the final epilogue (floats)
 
 template <typename T>
 struct FfnArgs {
@@ -51,18 +51,6 @@ struct FfnArgs {
   DropCfg dh, dc1, dc2;
   float gate_scale;
 };
-
-__device__ __forceinline__ void fdma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-template <typename T> __device__ __forceinline__ u32x2 f_pack4(const float v[4]) {
-  u32x2 o;
-  o[0] = H16<T>::pack2(v[0], v[1]);
-  o[1] = H16<T>::pack2(v[2], v[3]);
-  return o;
-}
 
 // EPI selects epilogue 1's bias / ReLU at compile time: 3 = bias + ReLU (the forward pass), 0 = neither (the backward pass),
 // 4 = as the descriptor says at run time (a per-value select on the flag -- 80 extra vector instructions per chunk).
@@ -79,24 +67,18 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
   const int m0 = blockIdx.x * FR;
   const int nch = p.F / FC;
 
-  // ---- A tile: instruction q moves rows 2q, 2q+1 (lane -> row half lane/32, LDS chunk position lane%32 holding global chunk
-  //      pos ^ 2 (row & 7)); wave w issues q = w, w+4, .. (10 each) ----
-  {
-    const int half = lane >> 5, pos = lane & 31;
+  // ---- A tile (rows beyond M repeat row M - 1) ----
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const int q = wn + 4 * i;
-      const int r = 2 * q + half;
-      const int row = min(m0 + r, p.M - 1);
-      fdma16((const char*)(p.A + (size_t)row * (size_t)p.lda) + ((pos ^ ((r & 7) << 1)) << 4), xt + q * 1024);
-    }
+  for (int i = 0; i < RT_DMA_PER_WAVE; ++i) {
+    const int row = min(m0 + rt_dma_row(wn, lane, i), p.M - 1);
+    rt_dma_issue((const char*)(p.A + (size_t)row * (size_t)p.lda), xt, wn, lane, i);
   }
 
   // ---- weight fragment streams (global -> registers): the weights arrive in FRAGMENT ORDER (eg_pack_table modes 3-6), so a
   //      fragment load is one contiguous 1-KB read per wave.  (Row-major weights cost 64 L1 tag look-ups per load -- 16 rows x
   //      64 B per quarter wave -- and made the launch tag-rate-bound: 98 us against 72 us for the two launches it replaces.) ----
-  const char* const w1u = (const char*)(p.W1 + (size_t)wn * (8 * 2 * 512));      // + c * (4*8*2*512) + (s * 2 + j) * 512   [elements]
-  const char* const w2u = (const char*)(p.W2 + (size_t)wn * (4 * 4 * 512));      // + c * (4*4*4*512) + (s * 4 + j) * 512
+  const char* const w1u = (const char*)(p.W1 + rt_frag_elem<8, 2>(0, wn, 0, 0));    // this wave's part of chunk 0
+  const char* const w2u = (const char*)(p.W2 + rt_frag_elem<4, 4>(0, wn, 0, 0));
   const uint32_t wl = (uint32_t)lane * 16u;                                      // wave-uniform base + 32-bit lane offset: saddr loads
   // Rolling rings, four (W1) / two (W2) k-steps ahead of their MFMAs and running on across chunk boundaries.  (Requesting a
   // whole chunk's fragments one phase ahead -- 16 + 16 live fragments -- was built: 67-88 spilled registers; the 256-register
@@ -104,11 +86,11 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
   frag w1r[4][2], w2r[2][4];
   auto req_w1 = [&](int c, int s, int slot) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) w1r[slot][j] = *(const frag*)(w1u + ((size_t)c * (4 * 8 * 2 * 512) + (s * 2 + j) * 512) * 2 + wl);
+    for (int j = 0; j < 2; ++j) w1r[slot][j] = *(const frag*)(w1u + rt_frag_elem<8, 2>(c, 0, s, j) * 2 + wl);
   };
   auto req_w2 = [&](int c, int s, int slot) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) w2r[slot][j] = *(const frag*)(w2u + ((size_t)c * (4 * 4 * 4 * 512) + (s * 4 + j) * 512) * 2 + wl);
+    for (int j = 0; j < 4; ++j) w2r[slot][j] = *(const frag*)(w2u + rt_frag_elem<4, 4>(c, 0, s, j) * 2 + wl);
   };
 #pragma unroll
   for (int s = 0; s < 4; ++s) req_w1(0, s, s);
@@ -151,8 +133,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
     if (nch > 1) gnext1 = bits_p[256];
   }
   const int rbase = l15;                                     // row of tile i within the workgroup: rbase + 16 i
-  const int sw7 = (l15 & 7) << 1;      // chunk ^ 2 (row & 7): free of bank conflicts under ds_read_b128's lane groups on 256-B and 512-B rows
-                                        // (chunk ^ (row & 7) is two ways conflicted there: SQ_LDS_BANK_CONFLICT 44 % of the LDS cycles)
+  const int sw7 = rt_swz(l15);
   // epilogue-1 lane constants: byte offset of this lane's 8-B slot (row l15, hidden column 32 wn + 16 j + 4 g4 of the chunk) in the
   // swizzled chunk image -- tile row i adds the immediate 4096 i -- and the dropout PAIR index of (row m0 + l15, column 32 wn + 4 g4)
   int ha[2];
@@ -208,8 +189,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       frag xf[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) xf[i] = *(const frag*)(xt + (rbase + 16 * i) * 512 + (((4 * s + g4) ^ sw7) << 4));
+      rt_frags<T>(xt, rbase, g4, sw7, s, xf);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -258,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
           v[2] = (h1 & 0xFFFFu) >= p.dh.thresh ? v[2] * p.dh.scale : 0.0f;
           v[3] = (h1 >> 16) >= p.dh.thresh ? v[3] * p.dh.scale : 0.0f;
         }
-        const u32x2 pk = f_pack4<T>(v);
+        const u32x2 pk = pack4<T>(v);
         *(u32x2*)(hc + ha[j] + 4096 * i) = pk;
         if (BOUT) {                                            // "stored value > 0", taken from the stored 16-bit patterns:
 #pragma unroll
@@ -280,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
 #pragma unroll
     for (int ps = 0; ps < 5; ++ps) {
       const int r = 16 * ps + tq, ch = tid & 15;
-      const u32x4 o = *(const u32x4*)(hc + r * 256 + ((ch ^ ((r & 7) << 1)) << 4));
+      const u32x4 o = *(const u32x4*)(hc + r * 256 + rt_piece(r, ch));
       if (m0 + r < p.M) *(u32x4*)(p.H + (size_t)(m0 + r) * (size_t)p.ldh + FC * c + 8 * ch) = o;
     }
 
@@ -288,8 +268,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       frag hf[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) hf[i] = *(const frag*)(hc + (rbase + 16 * i) * 256 + (((4 * s + g4) ^ sw7) << 4));
+      rt_frags<T, FC * 2>(hc, rbase, g4, sw7, s, hf);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -300,8 +279,8 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
   }
   __syncthreads();          // every wave has left the chunk buffers: they become the fp32 image of the final epilogue
 
-  // ---- epilogue 2: per 16-row tile through a wave-private fp32 image [16][68]; a lane then owns 16 consecutive columns of a row ----
-  float* timg = (float*)(hb + wn * (16 * F_TP * 4));
+  // ---- epilogue 2: per 16-row tile through the wave-private fp32 image; a lane then owns 16 consecutive columns of a row ----
+  float* timg = (float*)(hb + wn * RT_IMGB);
   const int er = lane >> 2, ec = lane & 3;
   const int n = 64 * wn + 16 * ec;
   float bv[16];
@@ -315,8 +294,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
     eraw[i][1] = (u32x4){0u, 0u, 0u, 0u};
     const int r = 16 * i + er;
     if (p.res_in_lds) {
-      eraw[i][0] = *(const u32x4*)(xt + r * 512 + ((((n >> 3)) ^ ((r & 7) << 1)) << 4));
-      eraw[i][1] = *(const u32x4*)(xt + r * 512 + ((((n >> 3) + 1) ^ ((r & 7) << 1)) << 4));
+      rt_tile_row16(xt, r, n, eraw[i][0], eraw[i][1]);
     } else if (p.residual && m0 + r < p.M) {
       const T* pe = p.residual + (size_t)(m0 + r) * (size_t)p.ldr + n;
       eraw[i][0] = *(const u32x4*)pe;
@@ -333,42 +311,16 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int m = m0 + 16 * i + er;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *(f32x4*)(timg + l15 * F_TP + 16 * j + 4 * g4) = acc2[i][j];
+    rt_image_put(timg, acc2[i], lane);
     if (m0 + 16 * i >= p.M) break;                 // workgroup-uniform: tiles wholly beyond M
     float v[16];
-    load8(timg + er * F_TP + 16 * ec, v);
-    load8(timg + er * F_TP + 16 * ec + 8, v + 8);
-    if (m < p.M) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] += bv[j];
-      if (p.dc1.thresh | p.dc2.thresh) {
-        const uint32_t idx = (uint32_t)m * (uint32_t)FD + (uint32_t)n;
-        float (&v0)[8] = *(float (*)[8])v;
-        float (&v1)[8] = *(float (*)[8])(v + 8);
-        eg_dropout_run<8>(v0, p.dc1, seed_lo, seed_hi, idx);
-        eg_dropout_run<8>(v0, p.dc2, seed_lo, seed_hi, idx);
-        eg_dropout_run<8>(v1, p.dc1, seed_lo, seed_hi, idx + 8);
-        eg_dropout_run<8>(v1, p.dc2, seed_lo, seed_hi, idx + 8);
-      }
-      if (p.residual) {
-        float rv[16];
-        load8((const T*)&eraw[i][0], rv);
-        load8((const T*)&eraw[i][1], rv + 8);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] += rv[j];
-      }
-      T* pc = p.C + (size_t)m * (size_t)p.ldc + n;
-      store8(pc, v);
-      store8(pc + 8, v + 8);
-      if (LNF) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) vv[i][j] = round_store<T>(v[j]);
-      }
-    }
+    rt_image_get(timg, lane, v);
+    if (m < p.M)
+      rt_row_epilogue<T, LNF>(v, bv, p.dc1, p.dc2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)FD + (uint32_t)n, p.residual != nullptr,
+                              eraw[i][0], eraw[i][1], p.C + (size_t)m * (size_t)p.ldc + n, vv[LNF ? i : 0]);
   }
   if constexpr (LNF)
-    eg_epilogue_layernorm256<T>(vv, (float*)(hb + 4 * (16 * F_TP * 4)), wn, lane, min(FR, p.M - m0), (size_t)m0, p.ln_gamma, p.ln_beta,
+    eg_epilogue_layernorm256<T>(vv, (float*)(hb + 4 * RT_IMGB), wn, lane, min(FR, p.M - m0), (size_t)m0, p.ln_gamma, p.ln_beta,
                                 p.LN_OUT, p.ln_stats);
 }
 
@@ -388,15 +340,7 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   p.gate_scale = d->gate_scale == 0.f ? 1.0f : d->gate_scale;
   p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.LN_OUT = (T*)d->ln_out; p.ln_stats = d->ln_stats;
   const dim3 grid((d->M + FR - 1) / FR);
-#define FFN_LAUNCH(G_, B_, E_, L_)                                                                                     \
-  do {                                                                                                                 \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)ffn_chain_kernel<T, G_, B_, E_, L_>, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS); \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((ffn_chain_kernel<T, G_, B_, E_, L_>), grid, dim3(256), F_LDS, s, p);                           \
-  } while (0)
+#define FFN_LAUNCH(G_, B_, E_, L_) eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_>, F_LDS>(grid, dim3(256), s, p)
   const int gsel = d->gate_bits_in ? 2 : d->gate ? 1 : 0;
   const bool bout = d->gate_bits_out != nullptr;
   const bool lnf = d->ln_out != nullptr;                                                                      // (forward form only, checked below)

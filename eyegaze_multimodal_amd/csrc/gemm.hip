@@ -4,7 +4,7 @@
 // 128x128 output tile, 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16 tiles.
 //   bf16: v_mfma_f32_16x16x32_bf16, K-tile 64      f32: v_mfma_f32_16x16x4_f32 (exact fmaf chain), K-tile 32
 // LDS rows are 128 B wide with a 16-B-chunk XOR swizzle so ds_read_b128 fragment reads are conflict-free.
-#include "common.h"
+#include "rowtile.h"      // eg_dma16 (tn_body256); gemm_nt_kernel and the fp32 paths use nothing of it
 #include <stdlib.h>
 
 namespace {
@@ -24,12 +24,6 @@ struct GemmNT {
   int seg_tiles;              // K-tiles per A-row segment (0 = one contiguous row)
   long long seg_stride_bytes; // distance between segments of an A row
 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  if (act == EG_ACT_RELU) return fmaxf(v, 0.f);
-  if (act == EG_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-  return v;
-}
 
 template <typename T>
 __device__ __forceinline__ void mma_ktile(const char* bufA, const char* bufW, int wm, int wn, int lane, f32x4 (&acc)[4][4]) {
@@ -70,14 +64,6 @@ __device__ __forceinline__ void mma_ktile<float>(const char* bufA, const char* b
       for (int mi = 0; mi < 4; ++mi)
         acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0);
   }
-}
-
-// the activation is a template parameter: with a run-time `act` every element carries the branch tree of erff() inline
-template <int ACT>
-__device__ __forceinline__ float apply_act_t(float v) {
-  if (ACT == EG_ACT_RELU) return fmaxf(v, 0.f);
-  if (ACT == EG_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-  return v;
 }
 
 // NARROW: products with N <= 64 (the spectrogram / image convolutions' 64 output channels).  On the 128 x 128 tile the two waves of
@@ -202,7 +188,7 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_kernel(GemmNT<T> p) {
         float v[8];
         load8(ct + row * CT_PITCH + ch * 8, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = apply_act_t<ACT>(v[j] + bv[j]);
+        for (int j = 0; j < 8; ++j) v[j] = eg_act<ACT>(v[j] + bv[j]);
         const long long coff = row_off(p.c, m) + n;
         if (p.gate) {
           float gv[8];
@@ -434,7 +420,26 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_kernel(GemmTN<T> p) {
 }
 
 // grouped form: many weight-gradient products (all with plain row-major operands and the same reduction length M)
-// in ONE launch; block -> problem by binary search over the problems' first block.
+// in ONE launch; block -> problem by binary search over the problems' first block (eg_find_entry).
+// The kernel arguments of one problem of the table, for the 128 x 128 tile (tile counts rounded up) or the 256 x 256 tile (N and K
+// are multiples of 256: exact division).
+template <typename T, int TILE>
+__device__ __forceinline__ GemmTN<T> tn_args_from_problem(const eg_tn_problem& q, int M, int splits, int rows_per_split) {
+  static_assert(TILE == 128 || TILE == 256, "tile edge");
+  GemmTN<T> p;
+  p.dY = (const T*)q.dY; p.X = (const T*)q.X; p.partial = (float*)q.partial;
+  p.y.row_stride = q.ldy; p.y.group_stride = 0; p.y.rows_per_group = 0;
+  p.x.row_stride = q.ldx; p.x.group_stride = 0; p.x.rows_per_group = 0;
+  p.M = M; p.N = q.N; p.K = q.K; p.splits = splits; p.rows_per_split = rows_per_split;
+  p.tiles_k = TILE == 128 ? (q.K + 127) / 128 : q.K / 256;
+  p.tiles_nk = p.tiles_k * (TILE == 128 ? (q.N + 127) / 128 : q.N / 256);
+  p.x_tile_stride = TILE;
+  p.part_rows = q.part_rows > 0 ? q.part_rows : q.N;
+  p.has_bias = q.has_bias;
+  p.part_size = (long long)p.part_rows * q.K + (q.has_bias ? p.part_rows : 0);
+  p.slab = (long long)(q.N / p.part_rows) * p.part_size;
+  return p;
+}
 template <typename T>
 __global__ __launch_bounds__(256, 3) void gemm_tn_grouped_kernel(const eg_tn_problem* __restrict__ probs, int nprob,
                                                                  int M, int splits, int rows_per_split) {
@@ -442,28 +447,8 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_grouped_kernel(const eg_tn_pro
   __shared__ int pi_s;
   // XCD-aware order: the tiles of one (problem, row range) read the same dY / X rows, so they must share an L2
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = nprob - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (probs[mid].blk0 <= bid) lo = mid; else hi = mid - 1;
-    }
-    pi_s = lo;
-  }
-  __syncthreads();
-  const eg_tn_problem q = probs[pi_s];
-  GemmTN<T> p;
-  p.dY = (const T*)q.dY; p.X = (const T*)q.X; p.partial = (float*)q.partial;
-  p.y.row_stride = q.ldy; p.y.group_stride = 0; p.y.rows_per_group = 0;
-  p.x.row_stride = q.ldx; p.x.group_stride = 0; p.x.rows_per_group = 0;
-  p.M = M; p.N = q.N; p.K = q.K; p.splits = splits; p.rows_per_split = rows_per_split;
-  p.tiles_k = (q.K + 127) / 128;
-  p.tiles_nk = p.tiles_k * ((q.N + 127) / 128);
-  p.x_tile_stride = 128;
-  p.part_rows = q.part_rows > 0 ? q.part_rows : q.N;
-  p.has_bias = q.has_bias;
-  p.part_size = (long long)p.part_rows * q.K + (q.has_bias ? p.part_rows : 0);
-  p.slab = (long long)(q.N / p.part_rows) * p.part_size;
+  const eg_tn_problem q = probs[eg_find_entry(probs, nprob, bid, &pi_s)];
+  const GemmTN<T> p = tn_args_from_problem<T, 128>(q, M, splits, rows_per_split);
   const int local = bid - q.blk0;
   tn_body<T>(p, local / p.tiles_nk, local % p.tiles_nk, smem);
 }
@@ -478,11 +463,6 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_grouped_kernel(const eg_tn_pro
 // ------------------------------------------------------------------------------------------------
 // 512 zero bytes: the LDS-DMA source of the rows beyond a split's end (a DMA cannot write a constant)
 __device__ __attribute__((aligned(512))) char eg_zero_row[512];
-
-__device__ __forceinline__ void tn_dma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // 256 x 256 weight-gradient tile over one row split.  The loop is fed by LDS-DMA through a FOUR-stage ring of 32-row stages
 // (2 x 16 KB each, 128 KB): three stages = 96 KB per CU are always in flight behind the one being multiplied.  (Before: 64-row
@@ -523,8 +503,8 @@ __device__ __forceinline__ void tn_body256(const GemmTN<T>& p, const int split, 
       const int mc = ok ? m : mend - 1;
       const char* sy = (const char*)(p.dY + row_off(p.y, mc) + n0) + ch;
       const char* sx = (const char*)(p.X + row_off(p.x, mc) + k0) + ch;
-      tn_dma16(ok ? sy : zsrc, st + q * 1024);
-      tn_dma16(ok ? sx : zsrc, st + TILEB + q * 1024);
+      eg_dma16(ok ? sy : zsrc, st + q * 1024);
+      eg_dma16(ok ? sx : zsrc, st + TILEB + q * 1024);
     }
   };
   const int nt = (mend - mbeg + RS - 1) / RS;
@@ -636,28 +616,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_grouped256_kernel(const eg_tn_
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int pi_s;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = nprob - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (probs[mid].blk0 <= bid) lo = mid; else hi = mid - 1;
-    }
-    pi_s = lo;
-  }
-  __syncthreads();
-  const eg_tn_problem q = probs[pi_s];
-  GemmTN<T> p;
-  p.dY = (const T*)q.dY; p.X = (const T*)q.X; p.partial = (float*)q.partial;
-  p.y.row_stride = q.ldy; p.y.group_stride = 0; p.y.rows_per_group = 0;
-  p.x.row_stride = q.ldx; p.x.group_stride = 0; p.x.rows_per_group = 0;
-  p.M = M; p.N = q.N; p.K = q.K; p.splits = splits; p.rows_per_split = rows_per_split;
-  p.tiles_k = q.K / 256;
-  p.tiles_nk = p.tiles_k * (q.N / 256);
-  p.x_tile_stride = 256;
-  p.part_rows = q.part_rows > 0 ? q.part_rows : q.N;
-  p.has_bias = q.has_bias;
-  p.part_size = (long long)p.part_rows * q.K + (q.has_bias ? p.part_rows : 0);
-  p.slab = (long long)(q.N / p.part_rows) * p.part_size;
+  const eg_tn_problem q = probs[eg_find_entry(probs, nprob, bid, &pi_s)];
+  const GemmTN<T> p = tn_args_from_problem<T, 256>(q, M, splits, rows_per_split);
   const int local = bid - q.blk0;
   tn_body256<T>(p, local / p.tiles_nk, local % p.tiles_nk, smem);
 }
@@ -666,16 +626,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_grouped256_kernel(const eg_tn_
 __global__ __launch_bounds__(256) void reduce_table_kernel(const eg_reduce_entry* __restrict__ tab, int nent) {
   __shared__ f32x4 red[32][8];
   __shared__ int ei_s;
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = nent - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (tab[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    ei_s = lo;
-  }
-  __syncthreads();
-  const eg_reduce_entry e = tab[ei_s];
+  const eg_reduce_entry e = tab[eg_find_entry(tab, nent, (int)blockIdx.x, &ei_s)];
   const float* partial = (const float*)e.partial;
   float* out = (float*)e.out;
   if (e.splits <= EG_REDUCE_WIDE_SPLITS) {
@@ -963,12 +914,7 @@ static int launch_gemm_tn(const eg_gemm_tn_desc* d, hipStream_t s) {
       p.tiles_k = d->K / 256;
       p.tiles_nk = p.tiles_k * (d->N / 256);
       constexpr int lds256 = 4 * 2 * 32 * 512;          // tn_body256's four-stage ring
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn256_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds256);
-        attr = true;
-      }
-      hipLaunchKernelGGL(gemm_tn256_kernel<T>, dim3(p.tiles_nk * d->splits), dim3(512), lds256, s, p);
+      eg_launch_lds<gemm_tn256_kernel<T>, lds256>(dim3(p.tiles_nk * d->splits), dim3(512), s, p);
       EG_LAUNCH_CHECK("gemm_tn256");
       return 0;
     }
@@ -1095,16 +1041,10 @@ extern "C" int eg_gemm_tn_grouped256(const eg_tn_problem* probs, int nprob, int 
   rps = (rps + 63) / 64 * 64;
   hipStream_t s = (hipStream_t)stream;
   constexpr int lds = 4 * 2 * 32 * 512;                  // tn_body256's four-stage ring
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_grouped256_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_grouped256_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
   if (dtype == EG_BF16)
-    hipLaunchKernelGGL(gemm_tn_grouped256_kernel<bf16_t>, dim3(total_blocks), dim3(512), lds, s, probs, nprob, M, splits, rps);
+    eg_launch_lds<gemm_tn_grouped256_kernel<bf16_t>, lds>(dim3(total_blocks), dim3(512), s, probs, nprob, M, splits, rps);
   else
-    hipLaunchKernelGGL(gemm_tn_grouped256_kernel<f16_t>, dim3(total_blocks), dim3(512), lds, s, probs, nprob, M, splits, rps);
+    eg_launch_lds<gemm_tn_grouped256_kernel<f16_t>, lds>(dim3(total_blocks), dim3(512), s, probs, nprob, M, splits, rps);
   EG_LAUNCH_CHECK("gemm_tn_grouped256");
   return 0;
 }

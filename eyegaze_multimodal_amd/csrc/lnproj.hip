@@ -9,22 +9,22 @@
 // the fragment loads in the waves' in-order vmcnt queues, the reason the streamed form of this tile was dropped).
 //
 // One 256-thread workgroup per 80 rows, two per CU (80 KB of LDS):
-//   1. LDS-DMA: dy rows -> tile Y, x rows -> tile X ([80][512 B], 16-B pieces XOR-swizzled by 2 (row & 7));
+//   1. LDS-DMA: dy rows -> tile Y, x rows -> tile X (two resident tiles of rowtile.h, where the DMA map, the swizzle, the fragment
+//      order and the image epilogue of steps 3 and 4 are written down);
 //   2. a half-wave per row (32 lanes x 8 elements), rows hw, hw + 8, ..: EXACTLY layernorm_bwd256_kernel's arithmetic and reduction
 //      order (dr and dyo are bit-identical to eg_layernorm_bwd's); dr and dyo leave as 512-B rows, dyo also replaces the dy piece in
 //      tile Y in place -- tile Y becomes the product's A operand;
 //   3. dC: a wave owns 80 x 64 (5 x 4 accumulator tiles), K = 256 in 8 k-steps, weight fragments two k-steps ahead (eg_pack_table
-//      modes 5 / 6: [chunk][wave][k-step: 4][tile: 4][lane]); same k-ordered MFMA chains as eg_gemm_nt: dC is bit-identical to it;
-//   4. epilogue through a wave-private fp32 image (in tile X, free by then): 16-bit stores of dC.
-#include "common.h"
+//      modes 5 / 6: rt_frag_elem<4, 4>); same k-ordered MFMA chains as eg_gemm_nt: dC is bit-identical to it;
+//   4. epilogue through the wave-private fp32 image (in tile X, free by then): 16-bit stores of dC.
+#include "rowtile.h"
 
 namespace {
 
-constexpr int PR = 80;
-constexpr int PD = 256;
-constexpr int P_T = PR * PD * 2;              // 40,960 B per tile
+constexpr int PR = RT_ROWS;
+constexpr int PD = RT_COLS;
+constexpr int P_T = RT_TILEB;                 // 40,960 B per tile
 constexpr int P_LDS = 2 * P_T;                // 81,920 B
-constexpr int P_TP = 68;
 
 template <typename T>
 struct LnProjArgs {
@@ -34,16 +34,6 @@ struct LnProjArgs {
   int M;
   DropCfg d1, d2;
 };
-
-__device__ __forceinline__ void pdma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ float p_half_sum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void ln_bwd_proj_kernel(LnProjArgs<T> p) {
@@ -56,28 +46,21 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_proj_kernel(LnProjArgs<T> p) {
   const int l15 = lane & 15, g4 = lane >> 4;
   const int m0 = blockIdx.x * PR;
 
-  // ---- 1. both tiles by LDS-DMA: instruction q moves rows 2q, 2q + 1 (lane -> row half lane / 32, piece lane % 32 holding the row's
-  //         piece pos ^ 2 (row & 7)); wave w issues q = w, w + 4, .. ----
-  {
-    const int half = lane >> 5, pos = lane & 31;
+  // ---- 1. both tiles by LDS-DMA, their instructions interleaved (rows beyond M repeat row M - 1) ----
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      const int q = wn + 4 * i;
-      const int r = 2 * q + half;
-      const size_t row = (size_t)min(m0 + r, p.M - 1);
-      const int sw = (pos ^ ((r & 7) << 1)) << 4;
-      pdma16((const char*)(p.dy + row * PD) + sw, ty + q * 1024);
-      pdma16((const char*)(p.x + row * PD) + sw, tx + q * 1024);
-    }
+  for (int i = 0; i < RT_DMA_PER_WAVE; ++i) {
+    const size_t row = (size_t)min(m0 + rt_dma_row(wn, lane, i), p.M - 1);
+    rt_dma_issue((const char*)(p.dy + row * PD), ty, wn, lane, i);
+    rt_dma_issue((const char*)(p.x + row * PD), tx, wn, lane, i);
   }
   // weight fragments of the first two k-steps and this half-wave's statistics travel meanwhile
-  const char* const wu = (const char*)(p.Wf + (size_t)wn * (4 * 4 * 512));      // + c * (4*4*4*512) + (s4 * 4 + j) * 512   [elements]
+  const char* const wu = (const char*)(p.Wf + rt_frag_elem<4, 4>(0, wn, 0, 0));
   const uint32_t wl = (uint32_t)lane * 16u;
   frag wr[2][4];
   auto req_w = [&](int s, int slot) {            // k-step s = 0 .. 7: chunk s / 4, step s % 4
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      wr[slot][j] = *(const frag*)(wu + ((size_t)(s >> 2) * (4 * 4 * 4 * 512) + ((s & 3) * 4 + j) * 512) * 2 + wl);
+      wr[slot][j] = *(const frag*)(wu + rt_frag_elem<4, 4>(s >> 2, 0, s & 3, j) * 2 + wl);
   };
   const int l = lane & 31, hw = tid >> 5;        // half-wave hw = 0 .. 7 owns rows hw, hw + 8, .. (10 rows)
   float mean[10], rstd[10];
@@ -105,8 +88,8 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_proj_kernel(LnProjArgs<T> p) {
     const int r = hw + 8 * j;
     const int m = m0 + r;
     const bool ok = m < p.M;
-    char* const py = ty + r * 512 + ((l ^ ((r & 7) << 1)) << 4);
-    const char* const px = tx + r * 512 + ((l ^ ((r & 7) << 1)) << 4);
+    char* const py = ty + r * RT_ROWB + rt_piece(r, l);
+    const char* const px = tx + r * RT_ROWB + rt_piece(r, l);
     float xv[8], dv[8];
     load8((const T*)px, xv);
     load8((const T*)py, dv);
@@ -155,12 +138,11 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_proj_kernel(LnProjArgs<T> p) {
   for (int i = 0; i < 5; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int sw7 = (l15 & 7) << 1;      // chunk ^ 2 (row & 7): conflict-free under ds_read_b128's lane groups on 512-B rows (ffn.hip)
+  const int sw7 = rt_swz(l15);
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     frag xf[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) xf[i] = *(const frag*)(ty + (l15 + 16 * i) * 512 + (((4 * s + g4) ^ sw7) << 4));
+    rt_frags<T>(ty, l15, g4, sw7, s, xf);
 #pragma unroll
     for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -168,24 +150,18 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_proj_kernel(LnProjArgs<T> p) {
     if (s + 2 < 8) req_w(s + 2, s & 1);
   }
 
-  // ---- 4. epilogue: per 16-row tile through a wave-private fp32 image [16][68] (tile X, behind the 16 KB of sums) ----
-  float* timg = (float*)(tx + 16384 + wn * (16 * P_TP * 4));
+  // ---- 4. epilogue: per 16-row tile through the wave-private fp32 image (tile X, behind the 16 KB of sums) ----
+  float* timg = (float*)(tx + 16384 + wn * RT_IMGB);
   const int er = lane >> 2, ec = lane & 3;
   const int n = 64 * wn + 16 * ec;
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int m = m0 + 16 * i + er;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *(f32x4*)(timg + l15 * P_TP + 16 * j + 4 * g4) = acc[i][j];
+    rt_image_put(timg, acc[i], lane);
     if (m0 + 16 * i >= p.M) break;                 // workgroup-uniform: tiles wholly beyond M
     float v[16];
-    load8(timg + er * P_TP + 16 * ec, v);
-    load8(timg + er * P_TP + 16 * ec + 8, v + 8);
-    if (m < p.M) {
-      T* pc = p.dC + (size_t)m * PD + n;
-      store8(pc, v);
-      store8(pc + 8, v + 8);
-    }
+    rt_image_get(timg, lane, v);
+    if (m < p.M) rt_store16(p.dC + (size_t)m * PD + n, v);
   }
 }
 
@@ -196,12 +172,7 @@ static int lnproj_launch(const eg_ln_bwd_proj_desc* d, hipStream_t s) {
   p.dr = (T*)d->dx; p.dyo = (T*)d->dx_drop; p.dC = (T*)d->dC; p.partial = d->partial; p.st = d->state; p.M = d->M;
   p.d1 = make_drop(d->drop1_p, d->drop1_site);
   p.d2 = make_drop(d->drop2_p, d->drop2_site);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)ln_bwd_proj_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-    attr = true;
-  }
-  hipLaunchKernelGGL((ln_bwd_proj_kernel<T>), dim3((d->M + PR - 1) / PR), dim3(256), P_LDS, s, p);
+  eg_launch_lds<ln_bwd_proj_kernel<T>, P_LDS>(dim3((d->M + PR - 1) / PR), dim3(256), s, p);
   EG_LAUNCH_CHECK("ln_bwd_proj");
   return 0;
 }

@@ -3,7 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "common.h"
+#include "rowtile.h"      // rt_frag_elem: the fragment order that modes 3-8 write
 
 thread_local char eg_err_buf[512] = {0};
 int eg_fail(const char* fmt, ...) {
@@ -117,6 +117,14 @@ __global__ void pack_convT_weight_kernel(const float* __restrict__ w, T* __restr
 // blk0 is the entry's first block.
 // one block of one table entry (modes 0-8); `lb` is the block's index within the entry.  Shared by pack_table_kernel and
 // pack_table_ex_kernel, so both write the same bytes.
+// the shifts by which a fragment-order mode decodes tile j, k-step s, wave and chunk from its destination index (in 8-element
+// pieces) are those of rt_frag_elem<KS, TJ>
+template <int KS, int TJ>
+constexpr bool frag_shifts_ok(int sh_j, int sh_s, int sh_wn, int sh_c) {
+  return rt_frag_elem<KS, TJ>(0, 0, 0, 1) == (size_t)8 << sh_j && rt_frag_elem<KS, TJ>(0, 0, 1, 0) == (size_t)8 << sh_s &&
+         rt_frag_elem<KS, TJ>(0, 1, 0, 0) == (size_t)8 << sh_wn && rt_frag_elem<KS, TJ>(1, 0, 0, 0) == (size_t)8 << sh_c &&
+         rt_frag_elem<KS, TJ>(0, 0, 0, 0, 1) == 8;
+}
 struct PackArgs {
   uint64_t src, dst;
   int rows, cols, ldd, mode;
@@ -145,21 +153,22 @@ __device__ __forceinline__ void pack_block(const PackArgs& e, const int lb, floa
     const int u = lb * 256 + threadIdx.x;                  // 8192 chunks of 8 elements per [256, 256] source
     const int lane = u & 63, l15 = lane & 15, g4 = lane >> 4;
     int n, k0;
-    size_t q;
+    size_t q;                                              // destination element
     if (e.mode == 7) {
       const int s8 = (u >> 6) & 7, half = (u >> 9) & 1, th = (u >> 10) & 1, c = u >> 11;
       const int t = th * 6 + e.ldd * 2 + half, wn = t / 3, j = t % 3;
       n = (2 * c + th) * 32 + 16 * half + l15; k0 = 32 * s8 + 8 * g4;
-      q = ((((size_t)c * 4 + wn) * 8 + s8) * 3 + j) * 64 + lane;
+      q = rt_frag_elem<8, 3>(c, wn, s8, j, lane);
     } else {
+      static_assert(frag_shifts_ok<2, 4>(6, 8, 9, 11), "mode 8 decodes [chunk][wave][k-step: 2][tile: 4][lane]");
       const int j = (u >> 6) & 3, s2 = (u >> 8) & 1, wn = (u >> 9) & 3, c = u >> 11;
       n = 64 * wn + 16 * j + l15; k0 = 64 * c + 32 * s2 + 8 * g4;
-      q = (size_t)u;
+      q = (size_t)u * 8;
     }
     if (u < 8192) {
       float v[8];
       load8(src + (size_t)n * 256 + k0, v);
-      if constexpr (sizeof(T) == 2) store8((T*)e.dst + q * 8, v);
+      if constexpr (sizeof(T) == 2) store8((T*)e.dst + q, v);
     }
   } else if (e.mode >= 3 && e.mode <= 6) {
     // MFMA-fragment order of eg_ffn_chain's weights: destination chunk q (8 elements) is what lane q%64 of a wave loads as
@@ -169,6 +178,7 @@ __device__ __forceinline__ void pack_block(const PackArgs& e, const int lb, floa
     const bool tr = e.mode == 4 || e.mode == 6;
     const int lane = q & 63, l15 = lane & 15, g4 = lane >> 4;
     int n, k0, N, K;
+    static_assert(frag_shifts_ok<8, 2>(6, 7, 10, 12) && frag_shifts_ok<4, 4>(6, 8, 10, 12), "the decodes below are rt_frag_elem's inverse");
     if (e.mode <= 4) {                       // role 1: [chunk c][wn][s: 8][j: 2][lane]
       const int j = (q >> 6) & 1, s8 = (q >> 7) & 7, wn = (q >> 10) & 3, c = q >> 12;
       n = 128 * c + 32 * wn + 16 * j + l15; k0 = 32 * s8 + 8 * g4;
@@ -206,26 +216,11 @@ __device__ __forceinline__ void pack_block(const PackArgs& e, const int lb, floa
   }
 }
 
-// last entry with blk0 <= blockIdx.x (thread 0 searches, everyone reads the answer after the barrier)
-template <typename E>
-__device__ __forceinline__ int pack_find_entry(const E* __restrict__ tab, int nent, int* ent_s) {
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = nent - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (tab[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    *ent_s = lo;
-  }
-  __syncthreads();
-  return *ent_s;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void pack_table_kernel(const eg_pack_entry* __restrict__ tab, int nent) {
   __shared__ float tile[32][33];
   __shared__ int ent_s;
-  const eg_pack_entry e = tab[pack_find_entry(tab, nent, &ent_s)];
+  const eg_pack_entry e = tab[eg_find_entry(tab, nent, (int)blockIdx.x, &ent_s)];
   const PackArgs a = {e.src, e.dst, e.rows, e.cols, e.ldd, e.mode};
   pack_block<T>(a, blockIdx.x - e.blk0, tile);
 }
@@ -248,7 +243,7 @@ __global__ __launch_bounds__(256) void pack_table_ex_kernel(const eg_pack_entry_
   __shared__ float stage[PACK_STAGE];
   __shared__ int ent_s;
   static_assert(PACK_STAGE >= 32 * 33, "modes 0-8 use the buffer as a [32][33] tile");
-  const eg_pack_entry_ex e = tab[pack_find_entry(tab, nent, &ent_s)];
+  const eg_pack_entry_ex e = tab[eg_find_entry(tab, nent, (int)blockIdx.x, &ent_s)];
   const int lb = blockIdx.x - e.blk0;
   if (e.mode < 9) {
     const PackArgs a = {e.src, e.dst, e.rows, e.cols, e.ldd, e.mode};

@@ -22,7 +22,7 @@
 //     sets); waves 4-7 (the SIMD partners of waves 0-3) take these two independent halves in the opposite order, so one
 //     wave's matrix burst sits beside its partner's vector / LDS / store work.
 // Arithmetic is the same k-ordered MFMA chain as gemm_nt_kernel, so results are bit-identical to it.
-#include "common.h"
+#include "rowtile.h"
 #include <stdlib.h>
 
 namespace {
@@ -45,11 +45,6 @@ struct RsGemm {
   float gate_scale;
 };
 
-__device__ __forceinline__ void dma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the field is an immediate); n is rounded DOWN (= waits for more)
 __device__ __forceinline__ void wait_vmcnt(int n) {
   n = __builtin_amdgcn_readfirstlane(n) >> 1;      // even counts only: at most one more instruction is waited for
@@ -71,24 +66,6 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
     case 14: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); break;
   }
-}
-
-// 4 floats -> 4 elements of the 16-bit storage type (two packed converts)
-template <typename T> __device__ __forceinline__ u32x2 rs_pack4(const float v[4]);
-template <> __device__ __forceinline__ u32x2 rs_pack4<bf16_t>(const float v[4]) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  const bf16x2 lo = __builtin_convertvector((f32x2){v[0], v[1]}, bf16x2);
-  const bf16x2 hi = __builtin_convertvector((f32x2){v[2], v[3]}, bf16x2);
-  u32x2 o;
-  o[0] = __builtin_bit_cast(uint32_t, lo);
-  o[1] = __builtin_bit_cast(uint32_t, hi);
-  return o;
-}
-template <> __device__ __forceinline__ u32x2 rs_pack4<f16_t>(const float v[4]) {
-  u32x2 o;
-  o[0] = pack2h(v[0], v[1]);
-  o[1] = pack2h(v[2], v[3]);
-  return o;
 }
 
 // EMODE: 0 no epilogue operand, 1 residual (added last), 2 gate (ReLU backward: zero where gate <= 0)
@@ -120,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void rs_gemm_kernel(RsGemm<T> p) {
     for (int i = 0; i < 2; ++i) {
       const int r = 4 * wave + 2 * i + (lane >> 5);          // row within the pair
       const int row = min(row0 + pair * 32 + r, p.M - 1);
-      dma16((const char*)(p.A + (size_t)((uint32_t)row * (uint32_t)p.lda)) + ((dpos ^ (r & 15)) << 4),
+      eg_dma16((const char*)(p.A + (size_t)((uint32_t)row * (uint32_t)p.lda)) + ((dpos ^ (r & 15)) << 4),
             ringA + slot * RS_PAIR + (4 * wave + 2 * i) * 512);
     }
     vm_issued += 2;
@@ -130,7 +107,7 @@ __global__ __launch_bounds__(512, 2) void rs_gemm_kernel(RsGemm<T> p) {
     for (int i = 0; i < 2; ++i) {
       const int r = 4 * wave + 2 * i + (lane >> 5);
       const int row = min(row0 + pair * 32 + r, p.M - 1);
-      dma16((const char*)(p.E + (size_t)((uint32_t)row * (uint32_t)p.lde) + n0) + ((dpos ^ (r & 15)) << 4),
+      eg_dma16((const char*)(p.E + (size_t)((uint32_t)row * (uint32_t)p.lde) + n0) + ((dpos ^ (r & 15)) << 4),
             ringE + slot * RS_PAIR + (4 * wave + 2 * i) * 512);
     }
     vm_issued += 2;
@@ -220,7 +197,7 @@ __global__ __launch_bounds__(512, 2) void rs_gemm_kernel(RsGemm<T> p) {
       char* const tb = timg + b * (16 * RS_TP);
       if (p.out_pre) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) *(u32x2*)(tb + l15 * RS_TP + (16 * j + 4 * g4) * 2) = rs_pack4<T>(v[j]);
+        for (int j = 0; j < 2; ++j) *(u32x2*)(tb + l15 * RS_TP + (16 * j + 4 * g4) * 2) = pack4<T>(v[j]);
         const u32x4 o = *(const u32x4*)(tb + sr * RS_TP + sc * 16);
         *(u32x4*)(p.out_pre + (size_t)(ms * (uint32_t)p.ldp) + n0 + 32 * wave + 8 * sc) = o;
         vm_issued += 1;
@@ -234,7 +211,7 @@ __global__ __launch_bounds__(512, 2) void rs_gemm_kernel(RsGemm<T> p) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) v[j][q] += ev[q];
         }
-        *(u32x2*)(tb + l15 * RS_TP + (16 * j + 4 * g4) * 2) = rs_pack4<T>(v[j]);
+        *(u32x2*)(tb + l15 * RS_TP + (16 * j + 4 * g4) * 2) = pack4<T>(v[j]);
       }
       const u32x4 o = *(const u32x4*)(tb + sr * RS_TP + sc * 16);
       *(u32x4*)(p.C + (size_t)(ms * (uint32_t)p.ldc) + n0 + 32 * wave + 8 * sc) = o;
@@ -319,16 +296,7 @@ static int rs_gemm_launch(const eg_gemm_desc* d, hipStream_t s, int cus) {
   p.d2 = make_drop(d->drop2_p, d->drop2_site);
   p.gate_scale = d->gate_scale == 0.f ? 1.0f : d->gate_scale;
   const dim3 grid(p.groups * p.ns), blk(512);
-#define RS_LAUNCH(E_, R_, D_)                                                                                          \
-  do {                                                                                                                 \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)rs_gemm_kernel<T, E_, R_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                RS_LDS);                                                                               \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((rs_gemm_kernel<T, E_, R_, D_>), grid, blk, RS_LDS, s, p);                                      \
-  } while (0)
+#define RS_LAUNCH(E_, R_, D_) eg_launch_lds<rs_gemm_kernel<T, E_, R_, D_>, RS_LDS>(grid, blk, s, p)
 #define RS_PICK(E_)                                                                                                    \
   do {                                                                                                                 \
     if (relu) { if (drop) RS_LAUNCH(E_, 1, 1); else RS_LAUNCH(E_, 1, 0); }                                             \

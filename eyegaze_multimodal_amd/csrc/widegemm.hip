@@ -8,8 +8,9 @@
 // counted s_waitcnt vmcnt(N) waits, so two K steps of loads are always in flight behind the MFMAs.
 //   512 threads = 8 waves as 2 (row halves of 80) x 4 (column groups of 64); a wave holds 5 x 4 accumulator tiles (80 VGPRs).
 //   LDS rows are 128 B (one K step) with the 16-B-chunk XOR swizzle on the DMA's per-lane SOURCE address and on the fragment
-//   reads (conflict-free ds_read_b128).  Epilogue: accumulators -> wave-private fp32 LDS image (in the drained ring) -> whole
-//   128-B row segments with bias / activation / gate / dropout / second output / residual, exactly gemm_nt_kernel's order.
+//   reads (conflict-free ds_read_b128).  Epilogue: accumulators -> wave-private fp32 LDS image (rowtile.h; in the drained ring) ->
+//   whole 128-B row segments with bias / activation / gate / dropout / second output / residual, exactly gemm_nt_kernel's order
+//   (dropout, residual and stores are rowtile.h's row steps; activation, gate and second output are this kernel's own).
 // Arithmetic is the same k-ordered MFMA chain as gemm_nt_kernel (bit-identical results).
 //
 // The row count is a template parameter: 160 as above, or 128 (row halves of 64, 4 x 4 accumulator tiles per wave, a 16 KB A
@@ -18,7 +19,7 @@
 // (205 on 160 rows, with more bytes each), M = 33 280 stays on 160 rows (208 workgroups; 260 would be two rounds).
 // gemm_nt_wide_batch_kernel runs up to EG_GEMM_BATCH_MAX such products (own operands, row maps, M and K) as ONE grid: a
 // workgroup finds its product and row tile from the prefix table in the kernel arguments.
-#include "common.h"
+#include "rowtile.h"
 #include <stdlib.h>
 
 namespace {
@@ -26,7 +27,6 @@ namespace {
 constexpr int WBN = 256;
 constexpr int WST_W = WBN * 128;                                             // 32 KB of W per stage
 constexpr int WNST = 3;
-constexpr int WTP = 68;                                                      // fp32 image pitch (floats): 64 + 4
 constexpr int wide_lds(int BM) { return WNST * (BM * 128 + WST_W); }         // 160 rows: 159,744 B; 128 rows: 147,456 B
 
 template <typename T>
@@ -38,18 +38,6 @@ struct WideNT {
   DropCfg d1, d2;
   float gate_scale;
 };
-
-__device__ __forceinline__ void wdma16(const char* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-template <int ACT>
-__device__ __forceinline__ float wide_act(float v) {
-  if (ACT == EG_ACT_RELU) return fmaxf(v, 0.f);
-  if (ACT == EG_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-  return v;
-}
 
 // one BM x 256 output tile starting at row m0 of product p
 template <typename T, int ACT, int BM>
@@ -87,9 +75,9 @@ __device__ __forceinline__ void wide_tile(const WideNT<T>& args, const int m0, c
     const size_t ko = (size_t)kt * 128;
 #pragma unroll
     for (int i = 0; i < NAW; ++i)
-      if (i < na) wdma16(asrc[i] + ko, sa + (wave + 8 * i) * 1024);
+      if (i < na) eg_dma16(asrc[i] + ko, sa + (wave + 8 * i) * 1024);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) wdma16(wsrc[i] + ko, sa + WST_A + (wave + 8 * i) * 1024);
+    for (int i = 0; i < 4; ++i) eg_dma16(wsrc[i] + ko, sa + WST_A + (wave + 8 * i) * 1024);
   };
 
   f32x4 acc[TI][4];
@@ -130,8 +118,8 @@ __device__ __forceinline__ void wide_tile(const WideNT<T>& args, const int m0, c
   }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // every wave has left the ring: it becomes epilogue scratch
 
-  // ---- epilogue: per 16-row tile through a wave-private fp32 image [16][68]; a lane then owns 16 consecutive columns of a row ----
-  float* timg = (float*)(smem + wave * (16 * WTP * 4));
+  // ---- epilogue: per 16-row tile through the wave-private fp32 image; a lane then owns 16 consecutive columns of a row ----
+  float* timg = (float*)(smem + wave * RT_IMGB);
   uint32_t seed_lo = 0, seed_hi = 0;
   if (p.d1.thresh | p.d2.thresh) { seed_lo = p.st->seed_lo; seed_hi = p.st->seed_hi; }
   const int er = lane >> 2, ec = lane & 3;                   // row of the tile, 16-column group
@@ -158,15 +146,13 @@ __device__ __forceinline__ void wide_tile(const WideNT<T>& args, const int m0, c
 #pragma unroll
   for (int i = 0; i < TI; ++i) {
     const int m = m0 + HM * wm + 16 * i + er;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *(f32x4*)(timg + l15 * WTP + 16 * j + 4 * g4) = acc[i][j];
+    rt_image_put(timg, acc[i], lane);
     if (m0 + HM * wm + 16 * i >= p.M) break;                 // wave-uniform: tiles wholly beyond M
     float v[16];
-    load8(timg + er * WTP + 16 * ec, v);
-    load8(timg + er * WTP + 16 * ec + 8, v + 8);
+    rt_image_get(timg, lane, v);
     if (m < p.M) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = wide_act<ACT>(v[j] + bv[j]);
+      for (int j = 0; j < 16; ++j) v[j] = eg_act<ACT>(v[j] + bv[j]);
       const long long coff = row_off(p.c, m) + n;
       if (p.gate) {
         float gv[16];
@@ -180,29 +166,10 @@ __device__ __forceinline__ void wide_tile(const WideNT<T>& args, const int m0, c
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = gv[j] > 0.f ? v[j] * p.gate_scale : 0.f;
       }
-      if (p.d1.thresh | p.d2.thresh) {
-        const uint32_t idx = (uint32_t)m * (uint32_t)p.N + (uint32_t)n;
-        float (&v0)[8] = *(float (*)[8])v;
-        float (&v1)[8] = *(float (*)[8])(v + 8);
-        eg_dropout_run<8>(v0, p.d1, seed_lo, seed_hi, idx);
-        eg_dropout_run<8>(v0, p.d2, seed_lo, seed_hi, idx);
-        eg_dropout_run<8>(v1, p.d1, seed_lo, seed_hi, idx + 8);
-        eg_dropout_run<8>(v1, p.d2, seed_lo, seed_hi, idx + 8);
-      }
-      if (p.out_pre) {
-        T* po = p.out_pre + row_off(p.pm, m) + n;
-        store8(po, v);
-        store8(po + 8, v + 8);
-      }
-      if (p.residual) {
-        float rv[16];
-        load8((const T*)&eraw[i][0], rv);
-        load8((const T*)&eraw[i][1], rv + 8);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] += rv[j];
-      }
-      store8(p.C + coff, v);
-      store8(p.C + coff + 8, v + 8);
+      rt_dropout16(v, p.d1, p.d2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)p.N + (uint32_t)n);
+      if (p.out_pre) rt_store16(p.out_pre + row_off(p.pm, m) + n, v);
+      if (p.residual) rt_add16<T>(v, eraw[i][0], eraw[i][1]);
+      rt_store16(p.C + coff, v);
     }
   }
 }
@@ -269,19 +236,9 @@ int wide_pick_rows(long long tiles160, long long tiles128, int cus) {
   return r160 * (160 + WBN) < r128 * (128 + WBN) ? 160 : 128;
 }
 
-#define WIDE_ATTR(kern, lds)                                                                              \
-  do {                                                                                                    \
-    static bool attr = false;                                                                             \
-    if (!attr) {                                                                                          \
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);      \
-      attr = true;                                                                                        \
-    }                                                                                                     \
-  } while (0)
-
 template <typename T, int ACT, int BM>
 static void wide_launch_one(const eg_gemm_desc* d, hipStream_t s) {
-  WIDE_ATTR((gemm_nt_wide_kernel<T, ACT, BM>), wide_lds(BM));
-  hipLaunchKernelGGL((gemm_nt_wide_kernel<T, ACT, BM>), dim3((d->M + BM - 1) / BM), dim3(512), wide_lds(BM), s, wide_args<T>(d));
+  eg_launch_lds<gemm_nt_wide_kernel<T, ACT, BM>, wide_lds(BM)>(dim3((d->M + BM - 1) / BM), dim3(512), s, wide_args<T>(d));
 }
 
 template <typename T, int BM>
@@ -302,8 +259,7 @@ static void wide_launch_batch_one(const eg_gemm_desc* const* d, int n, hipStream
     b.tile_end[i] = end;
   }
   b.n = n;
-  WIDE_ATTR((gemm_nt_wide_batch_kernel<T, ACT, BM>), wide_lds(BM));
-  hipLaunchKernelGGL((gemm_nt_wide_batch_kernel<T, ACT, BM>), dim3(end), dim3(512), wide_lds(BM), s, b);
+  eg_launch_lds<gemm_nt_wide_batch_kernel<T, ACT, BM>, wide_lds(BM)>(dim3(end), dim3(512), s, b);
 }
 
 template <typename T, int BM>
