@@ -7,7 +7,7 @@
 //   tile's MFMAs and written to the other buffer after them: one barrier per tile).
 //   scores^T = K_tile * Q^T (v_mfma_f32_16x16x32_{bf16,f16}: key on rows, query on lanes), online soft-max in registers
 //   (running max and a per-lane partial of the running sum; lanes l, l^16, l^32, l^48 share a query), P rounded to the
-//   16-bit type and fed to O^T = V^T * P^T as the B operand without an LDS round trip (the key permutation of attention.hip).
+//   16-bit type and fed to O^T = V^T * P^T as the B operand without an LDS round trip (the key permutation of attnhead.h).
 // 16-bit backward (deterministic: every output element has exactly one writer, no atomics):
 //   delta = rowsum(dO * O) into caller scratch [NB, H, S];
 //   dK / dV: one workgroup per (key window, head, 64-key tile) walks every query tile of the paired query window
@@ -17,55 +17,14 @@
 // kernels (three passes max / sum / output in the forward), K / V / Q / dO tiles streamed through LDS.
 // Dropout: element e = ((w H + h) S + q) Sp2 + key in 64 bits, Sp2 = (S + 1) & ~1 (common.h: eg_hash_pair64); below 2^32
 // the masks equal those of attention.hip bit for bit.
-#include "common.h"
+#include "attnhead.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-template <typename T> using FR = typename H16<T>::frag;
-
 constexpr int LT = 64;                    // rows per tile: queries of a workgroup, keys of a K / V tile
 constexpr int IMG = LT * 64;              // bytes of one 64-row image of a 32-wide 16-bit head slice
-constexpr float kScale = 0.17677669529663687f;  // 1/sqrt(32)
 
-// ---- fragment helpers (the image layout and operand maps of attention.hip) ----
-template <typename T>
-__device__ __forceinline__ FR<T> ld_frag_global(const T* p, bool valid) {
-  u32x4 v = {0u, 0u, 0u, 0u};
-  if (valid) v = *(const u32x4*)p;
-  return __builtin_bit_cast(FR<T>, v);
-}
-// [rows][32 x 16 bit] = 64-B rows; the two 32-B halves of a row are swapped when (row>>2)&1 (conflict-free transposed reads)
-__device__ __forceinline__ int img_chunk_off(int row, int c4) {
-  return row * 64 + ((((c4 >> 1) ^ ((row >> 2) & 1))) << 5) + ((c4 & 1) << 4);
-}
-template <typename T>
-__device__ __forceinline__ FR<T> ld_frag_lds_row(const char* img, int row, int g) {
-  return *(const FR<T>*)(img + img_chunk_off(row, g));
-}
-// transposed fragment: slot 8g+j <-> row rbase + 16*(j>>2) + 4g + (j&3), column 16 dt + (lane&15)
-template <typename T>
-__device__ __forceinline__ FR<T> ld_frag_lds_tr(const char* img, int rbase, int dt, int lane) {
-  const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  s16x4 part[2];
-#pragma unroll
-  for (int h2 = 0; h2 < 2; ++h2) {
-    const int row = rbase + 16 * h2 + 4 * g + qq;
-    const int off = row * 64 + ((dt ^ (g & 1)) << 5) + pp * 8;
-    part[h2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(img + off));
-  }
-  s16x8 t = {part[0][0], part[0][1], part[0][2], part[0][3], part[1][0], part[1][1], part[1][2], part[1][3]};
-  return __builtin_bit_cast(FR<T>, t);
-}
-template <typename T>
-__device__ __forceinline__ FR<T> pack_frag(const f32x4& a, const f32x4& b) {
-  u32x4 v;
-  v[0] = H16<T>::pack2(a[0], a[1]);
-  v[1] = H16<T>::pack2(a[2], a[3]);
-  v[2] = H16<T>::pack2(b[0], b[1]);
-  v[3] = H16<T>::pack2(b[2], b[3]);
-  return __builtin_bit_cast(FR<T>, v);
-}
+// ---- tile staging (the head image, its operand reads and the dropout index: attnhead.h) ----
 // one 16-B chunk of a 64-row tile per thread (256 threads: row tid >> 2, chunk tid & 3); rows >= nrows read as zero
 template <typename T>
 __device__ __forceinline__ u32x4 tile_request(const T* src, long long ld, int row0, int S, int tid) {
@@ -74,7 +33,7 @@ __device__ __forceinline__ u32x4 tile_request(const T* src, long long ld, int ro
   if (row < S) v = *(const u32x4*)(src + (long long)row * ld + (tid & 3) * 8);
   return v;
 }
-__device__ __forceinline__ void tile_store(char* img, u32x4 v, int tid) { *(u32x4*)(img + img_chunk_off(tid >> 2, tid & 3)) = v; }
+__device__ __forceinline__ void tile_store(char* img, u32x4 v, int tid) { *(u32x4*)(img + hd_img_off(tid >> 2, tid & 3)) = v; }
 
 // (window, head, tile) of a workgroup: tiles fastest, so the workgroups of one head run side by side and share its K / V in L2
 struct TileIdx { int w, h, t; };
@@ -100,7 +59,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict_
   const T* vbase = kbase + D;
   const int q = ti.t * LT + wave * 16 + l15;
   u32x4 rk = tile_request<T>(kbase, ld, 0, S, tid), rv = tile_request<T>(vbase, ld, 0, S, tid);
-  const FR<T> qf = ld_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
+  const FR<T> qf = hd_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
   uint32_t seed_lo = 0, seed_hi = 0;
   if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
   const uint64_t rowe = (uint64_t)(((long long)b * H + h) * S + q) * (uint64_t)((S + 1) & ~1);
@@ -124,10 +83,10 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict_
     float tmax = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
-      s[kt] = H16<T>::mfma(ld_frag_lds_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
+      s[kt] = H16<T>::mfma(hd_frag_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = (full || kv0 + kt * 16 + 4 * g + r < S) ? s[kt][r] * kScale : -INFINITY;
+        const float v = (full || kv0 + kt * 16 + 4 * g + r < S) ? s[kt][r] * HD_SCALE : -INFINITY;
         s[kt][r] = v;
         tmax = fmaxf(tmax, v);
       }
@@ -160,9 +119,9 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict_
     }
 #pragma unroll
     for (int kp = 0; kp < 2; ++kp) {
-      const FR<T> pf = pack_frag<T>(s[2 * kp], s[2 * kp + 1]);
+      const FR<T> pf = hd_pack_frag<T>(s[2 * kp], s[2 * kp + 1]);
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt) o[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(vimg, 32 * kp, dt, lane), pf, o[dt]);
+      for (int dt = 0; dt < 2; ++dt) o[dt] = H16<T>::mfma(hd_frag_tr<T>(vimg, 32 * kp, dt, lane), pf, o[dt]);
     }
     if (more) {
       tile_store(sm[cur ^ 1][0], rk, tid);
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(256) void attn_long_delta_kernel(const T* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// 16-bit dK / dV: one workgroup per (key window, head, 64-key tile); query rows / key lanes (pass B of attention.hip)
+// 16-bit dK / dV: one workgroup per (key window, head, 64-key tile); query rows / key lanes
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict__ qkv, const T* __restrict__ dctx,
@@ -246,8 +205,8 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
   u32x4 rq, rd;
   float rl;
   request(0, rq, rd, rl);
-  const FR<T> kfr = ld_frag_global<T>(kbase + (long long)key * ld + g * 8, key < S);
-  const FR<T> vfr = ld_frag_global<T>(vbase + (long long)key * ld + g * 8, key < S);
+  const FR<T> kfr = hd_frag_global<T>(kbase + (long long)key * ld + g * 8, key < S);
+  const FR<T> vfr = hd_frag_global<T>(vbase + (long long)key * ld + g * 8, key < S);
   uint32_t seed_lo = 0, seed_hi = 0;
   if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
   const uint64_t Sp2 = (uint64_t)((S + 1) & ~1);
@@ -270,12 +229,12 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
         const int r16 = 32 * qp + 16 * h2;                 // first query of the 16-row block, within the tile
-        const f32x4 s = H16<T>::mfma(ld_frag_lds_row<T>(qimg, r16 + l15, g), kfr, zero4);
-        const f32x4 dp = H16<T>::mfma(ld_frag_lds_row<T>(doimg, r16 + l15, g), vfr, zero4);
+        const f32x4 s = H16<T>::mfma(hd_frag_row<T>(qimg, r16 + l15, g), kfr, zero4);
+        const f32x4 dp = H16<T>::mfma(hd_frag_row<T>(doimg, r16 + l15, g), vfr, zero4);
         const f32x4 l4 = *(const f32x4*)(lsel + r16 + 4 * g);
         const f32x4 d4 = *(const f32x4*)(dl + r16 + 4 * g);
         // One hash serves the elements (q, key) and (q, key ^ 1), which sit in neighbouring lanes: a lane hashes two of its
-        // four query rows (even keys rows 0-1, odd keys rows 2-3) and takes the other two from lane ^ 1 (as attention.hip).
+        // four query rows (even keys rows 0-1, odd keys rows 2-3) and takes the other two from lane ^ 1.
         uint32_t hh[4] = {0u, 0u, 0u, 0u};
         if (dc.thresh) {
           const uint32_t odd = (uint32_t)key & 1u;
@@ -289,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = q0 + r16 + 4 * g + r;
-          const float p = (key < S && qq < S) ? __expf(s[r] * kScale - l4[r]) : 0.f;
+          const float p = (key < S && qq < S) ? __expf(s[r] * HD_SCALE - l4[r]) : 0.f;
           float mk = 1.0f;
           if (dc.thresh) {
             const uint32_t half = ((uint32_t)key & 1u) ? (hh[r] >> 16) : (hh[r] & 0xFFFFu);
@@ -299,12 +258,12 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
           ds2[h2][r] = p * (dp[r] * mk - d4[r]);
         }
       }
-      const FR<T> pdf = pack_frag<T>(pd2[0], pd2[1]);
-      const FR<T> dsf = pack_frag<T>(ds2[0], ds2[1]);
+      const FR<T> pdf = hd_pack_frag<T>(pd2[0], pd2[1]);
+      const FR<T> dsf = hd_pack_frag<T>(ds2[0], ds2[1]);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        dv[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(doimg, 32 * qp, dt, lane), pdf, dv[dt]);
-        dk[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(qimg, 32 * qp, dt, lane), dsf, dk[dt]);
+        dv[dt] = H16<T>::mfma(hd_frag_tr<T>(doimg, 32 * qp, dt, lane), pdf, dv[dt]);
+        dk[dt] = H16<T>::mfma(hd_frag_tr<T>(qimg, 32 * qp, dt, lane), dsf, dk[dt]);
       }
     }
     if (more) store(cur ^ 1, rq, rd, rl);
@@ -313,7 +272,7 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
   if (key < S) {
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
-      float a[4] = {dk[dt][0] * kScale, dk[dt][1] * kScale, dk[dt][2] * kScale, dk[dt][3] * kScale};
+      float a[4] = {dk[dt][0] * HD_SCALE, dk[dt][1] * HD_SCALE, dk[dt][2] * HD_SCALE, dk[dt][3] * HD_SCALE};
       float c[4] = {dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]};
       T* row = dqkv + ((long long)bk * S + key) * ld + h * 32 + 16 * dt + 4 * g;
       store4(row + D, a);
@@ -323,7 +282,7 @@ __global__ __launch_bounds__(256) void attn_long_dkdv_kernel(const T* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// 16-bit dQ: one workgroup per (query window, head, 64-query tile); key rows / query lanes (pass A of attention.hip)
+// 16-bit dQ: one workgroup per (query window, head, 64-query tile); key rows / query lanes
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ dctx,
@@ -342,8 +301,8 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__
   const T* dobase = dctx + (long long)b * S * D + h * 32;
   const int q = ti.t * LT + wave * 16 + l15;
   u32x4 rk = tile_request<T>(kbase, ld, 0, S, tid), rv = tile_request<T>(vbase, ld, 0, S, tid);
-  const FR<T> qf = ld_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
-  const FR<T> dof = ld_frag_global<T>(dobase + (long long)q * D + g * 8, q < S);
+  const FR<T> qf = hd_frag_global<T>(qbase + (long long)q * ld + g * 8, q < S);
+  const FR<T> dof = hd_frag_global<T>(dobase + (long long)q * D + g * 8, q < S);
   const long long hq = ((long long)b * H + h) * S + q;
   const float lq = q < S ? lse[hq] : 0.f, dq = q < S ? delta[hq] : 0.f;
   uint32_t seed_lo = 0, seed_hi = 0;
@@ -366,22 +325,22 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__
     f32x4 ds[4];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
-      const f32x4 sT = H16<T>::mfma(ld_frag_lds_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
-      const f32x4 dpT = H16<T>::mfma(ld_frag_lds_row<T>(vimg, kt * 16 + l15, g), dof, zero4);
+      const f32x4 sT = H16<T>::mfma(hd_frag_row<T>(kimg, kt * 16 + l15, g), qf, zero4);
+      const f32x4 dpT = H16<T>::mfma(hd_frag_row<T>(vimg, kt * 16 + l15, g), dof, zero4);
       float dpv[4] = {dpT[0], dpT[1], dpT[2], dpT[3]};
       eg_dropout_run64<4>(dpv, dc, seed_lo, seed_hi, rowe + (uint64_t)(kv0 + kt * 16 + 4 * g));
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kv0 + kt * 16 + 4 * g + r;
-        const float p = key < S ? __expf(sT[r] * kScale - lq) : 0.f;
+        const float p = key < S ? __expf(sT[r] * HD_SCALE - lq) : 0.f;
         ds[kt][r] = p * (dpv[r] - dq);
       }
     }
 #pragma unroll
     for (int kp = 0; kp < 2; ++kp) {
-      const FR<T> dsf = pack_frag<T>(ds[2 * kp], ds[2 * kp + 1]);
+      const FR<T> dsf = hd_pack_frag<T>(ds[2 * kp], ds[2 * kp + 1]);
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt) acc[dt] = H16<T>::mfma(ld_frag_lds_tr<T>(kimg, 32 * kp, dt, lane), dsf, acc[dt]);
+      for (int dt = 0; dt < 2; ++dt) acc[dt] = H16<T>::mfma(hd_frag_tr<T>(kimg, 32 * kp, dt, lane), dsf, acc[dt]);
     }
     if (more) {
       tile_store(sm[cur ^ 1][0], rk, tid);
@@ -392,7 +351,7 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__
   if (q < S) {
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
-      float v[4] = {acc[dt][0] * kScale, acc[dt][1] * kScale, acc[dt][2] * kScale, acc[dt][3] * kScale};
+      float v[4] = {acc[dt][0] * HD_SCALE, acc[dt][1] * HD_SCALE, acc[dt][2] * HD_SCALE, acc[dt][3] * HD_SCALE};
       store4(dqkv + ((long long)b * S + q) * ld + h * 32 + 16 * dt + 4 * g, v);
     }
   }
@@ -404,12 +363,6 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__
 // ------------------------------------------------------------------------------------------------
 constexpr int F32_THREADS = 128;
 
-__device__ __forceinline__ float dot32(const float* a, const float* b) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = 0; d < 32; ++d) s = fmaf(a[d], b[d], s);
-  return s;
-}
 // rows [row0, row0 + 64) of a 32-wide fp32 head slice into dst [64][32]; rows >= S read as zero
 __device__ __forceinline__ void f32_tile_load(float* dst, const float* src, long long ld, int row0, int S) {
   for (int i = threadIdx.x; i < LT * 8; i += F32_THREADS) {
@@ -449,12 +402,12 @@ __global__ __launch_bounds__(F32_THREADS) void attn_long_fwd_f32_kernel(const fl
       if (pass == 2) f32_tile_load(Vl, vbase, ld, k0, S);
       __syncthreads();
       if (pass == 0) {
-        for (int k = 0; k < nk; ++k) mx = fmaxf(mx, dot32(qv, Kl + k * 32) * kScale);
+        for (int k = 0; k < nk; ++k) mx = fmaxf(mx, hd_dot32(qv, Kl + k * 32) * HD_SCALE);
       } else if (pass == 1) {
-        for (int k = 0; k < nk; ++k) sum += expf(dot32(qv, Kl + k * 32) * kScale - mx);
+        for (int k = 0; k < nk; ++k) sum += expf(hd_dot32(qv, Kl + k * 32) * HD_SCALE - mx);
       } else {
         for (int k = 0; k < nk; ++k) {
-          float p = expf(dot32(qv, Kl + k * 32) * kScale - mx) * inv;
+          float p = expf(hd_dot32(qv, Kl + k * 32) * HD_SCALE - mx) * inv;
           if (dc.thresh) p = eg_dropout64(p, dc, seed_lo, seed_hi, rowe + (uint64_t)(k0 + k));
 #pragma unroll
           for (int d = 0; d < 32; ++d) o[d] = fmaf(p, Vl[k * 32 + d], o[d]);
@@ -502,8 +455,8 @@ __global__ __launch_bounds__(F32_THREADS) void attn_long_dq_f32_kernel(const flo
     f32_tile_load(Vl, vbase, ld, k0, S);
     __syncthreads();
     for (int k = 0; k < nk; ++k) {
-      const float p = expf(dot32(qv, Kl + k * 32) * kScale - lq);
-      float dp = dot32(dov, Vl + k * 32);
+      const float p = expf(hd_dot32(qv, Kl + k * 32) * HD_SCALE - lq);
+      float dp = hd_dot32(dov, Vl + k * 32);
       if (dc.thresh) dp = eg_dropout64(dp, dc, seed_lo, seed_hi, rowe + (uint64_t)(k0 + k));
       const float ds = p * (dp - dq);
 #pragma unroll
@@ -512,7 +465,7 @@ __global__ __launch_bounds__(F32_THREADS) void attn_long_dq_f32_kernel(const flo
   }
   if (!valid) return;
 #pragma unroll
-  for (int d = 0; d < 32; ++d) dqkv[((long long)b * S + t_) * ld + h * 32 + d] = acc[d] * kScale;
+  for (int d = 0; d < 32; ++d) dqkv[((long long)b * S + t_) * ld + h * 32 + d] = acc[d] * HD_SCALE;
 }
 
 __global__ __launch_bounds__(F32_THREADS) void attn_long_dkdv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx,
@@ -556,8 +509,8 @@ __global__ __launch_bounds__(F32_THREADS) void attn_long_dkdv_f32_kernel(const f
     }
     __syncthreads();
     for (int i = 0; i < nqr; ++i) {
-      const float p = expf(dot32(Ql + i * 32, kv) * kScale - lsel[i]);
-      const float dpr = dot32(Dl + i * 32, vv);
+      const float p = expf(hd_dot32(Ql + i * 32, kv) * HD_SCALE - lsel[i]);
+      const float dpr = hd_dot32(Dl + i * 32, vv);
       float mk = 1.0f;
       if (dc.thresh) mk = eg_dropout64(1.0f, dc, seed_lo, seed_hi, (uint64_t)(headrow + q0 + i) * Sp2 + (uint64_t)t_);
       const float pd = p * mk, ds = p * (dpr * mk - dl[i]);
@@ -571,7 +524,7 @@ __global__ __launch_bounds__(F32_THREADS) void attn_long_dkdv_f32_kernel(const f
   if (!valid) return;
 #pragma unroll
   for (int d = 0; d < 32; ++d) {
-    dqkv[((long long)bk * S + t_) * ld + D + h * 32 + d] = ak[d] * kScale;
+    dqkv[((long long)bk * S + t_) * ld + D + h * 32 + d] = ak[d] * HD_SCALE;
     dqkv[((long long)bk * S + t_) * ld + 2 * D + h * 32 + d] = av[d];
   }
 }
@@ -607,7 +560,7 @@ __global__ __launch_bounds__(256) void attn_long_probs_kernel(const T* __restric
       float acc = 0.f;
 #pragma unroll
       for (int d = 0; d < 32; ++d) acc = fmaf(Ql[r][d], kv[d], acc);
-      out[(long long)r * S + k] = expf(acc * kScale - lq[r]);
+      out[(long long)r * S + k] = expf(acc * HD_SCALE - lq[r]);
     }
   }
 }
@@ -615,11 +568,7 @@ __global__ __launch_bounds__(256) void attn_long_probs_kernel(const T* __restric
 }  // namespace
 
 static int attn_long_check(const char* who, int NB, int S, int H, int kv_shift, int dtype, float p, const void* st) {
-  EG_CHECK(NB > 0 && S > 0 && H > 0, "%s: bad shape NB=%d S=%d H=%d", who, NB, S, H);
-  EG_CHECK(S <= EG_ATTN_LONG_MAX_S, "%s: S=%d exceeds the long-attention limit of %d", who, S, EG_ATTN_LONG_MAX_S);
-  EG_CHECK(kv_shift >= 0 && kv_shift < NB, "%s: kv_shift=%d out of range", who, kv_shift);
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F32 || dtype == EG_F16, "%s: bad dtype %d", who, dtype);
-  EG_CHECK(p >= 0.f && p < 1.f && (p == 0.f || st), "%s: dropout p=%f needs a step state", who, (double)p);
+  if (hd_check(who, NB, S, H, kv_shift, dtype, p, st, EG_ATTN_LONG_MAX_S, false)) return 1;
   // one workgroup per (window, head, 16-row tile) at most: the grid's x dimension
   EG_CHECK((long long)NB * H * ((S + PROBS_ROWS - 1) / PROBS_ROWS) < (1ll << 31), "%s: NB*H=%lld heads exceed the grid", who,
            (long long)NB * H);
@@ -637,12 +586,12 @@ extern "C" int eg_attention_long_fwd(const void* qkv, void* ctx, float* lse, int
   if (dtype == EG_F32)
     hipLaunchKernelGGL(attn_long_fwd_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
                        (const float*)qkv, (float*)ctx, lse, NB, S, H, kv_shift, dc, state);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(attn_long_fwd_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
-                       (f16_t*)ctx, lse, NB, S, H, kv_shift, dc, state);
   else
-    hipLaunchKernelGGL(attn_long_fwd_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
-                       (bf16_t*)ctx, lse, NB, S, H, kv_shift, dc, state);
+    eg_dispatch_16(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL(attn_long_fwd_kernel<T>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const T*)qkv, (T*)ctx, lse, NB, S,
+                         H, kv_shift, dc, state);
+    });
   EG_LAUNCH_CHECK("attention_long_fwd");
   return 0;
 }
@@ -658,24 +607,23 @@ extern "C" int eg_attention_long_bwd(const void* qkv, const void* ctx, const voi
   const DropCfg dc = make_drop(drop_p, drop_site);
   hipStream_t s = (hipStream_t)stream;
   const dim3 dgrid((unsigned)((n + 255) / 256));
+  const float* delta = scratch;
+  // delta -> dK / dV -> dQ
   if (dtype == EG_F32) {
-    hipLaunchKernelGGL(attn_long_delta_kernel<float>, dgrid, dim3(256), 0, s, (const float*)ctx, (const float*)dctx, scratch, n, S, H);
-    hipLaunchKernelGGL(attn_long_dkdv_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
-                       (const float*)qkv, (const float*)dctx, lse, (const float*)scratch, (float*)dqkv, NB, S, H, kv_shift, dc, state);
-    hipLaunchKernelGGL(attn_long_dq_f32_kernel, dim3(long_blocks(NB, H, S, F32_THREADS)), dim3(F32_THREADS), 0, s,
-                       (const float*)qkv, (const float*)dctx, lse, (const float*)scratch, (float*)dqkv, NB, S, H, kv_shift, dc, state);
-  } else if (dtype == EG_F16) {
-    hipLaunchKernelGGL(attn_long_delta_kernel<f16_t>, dgrid, dim3(256), 0, s, (const f16_t*)ctx, (const f16_t*)dctx, scratch, n, S, H);
-    hipLaunchKernelGGL(attn_long_dkdv_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
-                       (const f16_t*)dctx, lse, (const float*)scratch, (f16_t*)dqkv, NB, S, H, kv_shift, dc, state);
-    hipLaunchKernelGGL(attn_long_dq_kernel<f16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const f16_t*)qkv,
-                       (const f16_t*)dctx, lse, (const float*)scratch, (f16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+    const dim3 grid(long_blocks(NB, H, S, F32_THREADS)), block(F32_THREADS);
+    const float *q = (const float*)qkv, *d = (const float*)dctx;
+    hipLaunchKernelGGL(attn_long_delta_kernel<float>, dgrid, dim3(256), 0, s, (const float*)ctx, d, scratch, n, S, H);
+    hipLaunchKernelGGL(attn_long_dkdv_f32_kernel, grid, block, 0, s, q, d, lse, delta, (float*)dqkv, NB, S, H, kv_shift, dc, state);
+    hipLaunchKernelGGL(attn_long_dq_f32_kernel, grid, block, 0, s, q, d, lse, delta, (float*)dqkv, NB, S, H, kv_shift, dc, state);
   } else {
-    hipLaunchKernelGGL(attn_long_delta_kernel<bf16_t>, dgrid, dim3(256), 0, s, (const bf16_t*)ctx, (const bf16_t*)dctx, scratch, n, S, H);
-    hipLaunchKernelGGL(attn_long_dkdv_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
-                       (const bf16_t*)dctx, lse, (const float*)scratch, (bf16_t*)dqkv, NB, S, H, kv_shift, dc, state);
-    hipLaunchKernelGGL(attn_long_dq_kernel<bf16_t>, dim3(long_blocks(NB, H, S, LT)), dim3(256), 0, s, (const bf16_t*)qkv,
-                       (const bf16_t*)dctx, lse, (const float*)scratch, (bf16_t*)dqkv, NB, S, H, kv_shift, dc, state);
+    eg_dispatch_16(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      const dim3 grid(long_blocks(NB, H, S, LT)), block(256);
+      const T *q = (const T*)qkv, *d = (const T*)dctx;
+      hipLaunchKernelGGL(attn_long_delta_kernel<T>, dgrid, dim3(256), 0, s, (const T*)ctx, d, scratch, n, S, H);
+      hipLaunchKernelGGL(attn_long_dkdv_kernel<T>, grid, block, 0, s, q, d, lse, delta, (T*)dqkv, NB, S, H, kv_shift, dc, state);
+      hipLaunchKernelGGL(attn_long_dq_kernel<T>, grid, block, 0, s, q, d, lse, delta, (T*)dqkv, NB, S, H, kv_shift, dc, state);
+    });
   }
   EG_LAUNCH_CHECK("attention_long_bwd");
   return 0;
@@ -687,12 +635,10 @@ extern "C" int eg_attention_long_probs(const void* qkv, const float* lse, float*
   if (attn_long_check("eg_attention_long_probs", NB, S, H, kv_shift, dtype, 0.f, nullptr)) return 1;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(long_blocks(NB, H, S, PROBS_ROWS));
-  if (dtype == EG_F32)
-    hipLaunchKernelGGL(attn_long_probs_kernel<float>, grid, dim3(256), 0, s, (const float*)qkv, lse, probs, NB, S, H, kv_shift);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(attn_long_probs_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)qkv, lse, probs, NB, S, H, kv_shift);
-  else
-    hipLaunchKernelGGL(attn_long_probs_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)qkv, lse, probs, NB, S, H, kv_shift);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(attn_long_probs_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv, lse, probs, NB, S, H, kv_shift);
+  });
   EG_LAUNCH_CHECK("attention_long_probs");
   return 0;
 }

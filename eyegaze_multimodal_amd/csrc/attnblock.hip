@@ -16,7 +16,7 @@
 //       (120 MFMAs); the x fragments come from the LDS tile, the weights straight from L2 into registers in FRAGMENT ORDER
 //       (eg_pack_table modes 7 / 8: one contiguous 1-KB read per fragment, rolling ring 3 k-steps ahead);
 //       epilogue: + bias, round to 16 bit, 8-B writes into six [rows][32] LDS images (q, k, v of the two heads) in the attention
-//       core's swizzled row layout; the images are streamed to HBM as 128-B row segments (two adjacent heads);
+//       core's swizzled row layout (attnhead.h); the images are streamed to HBM as 128-B row segments (two adjacent heads);
 //   P2  attention: two waves per head (alternate query tiles), EXACTLY eg_attention_fwd's arithmetic (scores^T = K Q^T with the
 //       key on accumulator rows, soft-max in registers, the probabilities are the next MFMA's operand, V^T through
 //       ds_read_b64_tr_b16) with K / Q fragments read from the images; ctx overwrites the head's q image row by row;
@@ -30,20 +30,18 @@
 // of a head at S = 65), not by bandwidth; static s_setprio for the matrix phases measured no change (57.9 vs 58.2 us by HIP events).
 // Same MFMA chains, rounding points and dropout indices as the launches it replaces: q|k|v, lse, ctx and r1 are BIT-IDENTICAL
 // to eg_gemm_nt -> eg_attention_fwd -> eg_gemm_nt (tests/test_gpu_attnblock.py).
+#include "attnhead.h"
 #include "rowtile.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short ab_s16x8;
 
 constexpr int AR = RT_ROWS;                    // rows of the window tile (5 MFMA row tiles): S <= 80
 constexpr int AD = RT_COLS;                    // d_model
 constexpr int AH = 8;                          // heads of 32
 constexpr int A_XT = RT_TILEB;                 // 40,960 B: the window's x rows
-constexpr int A_QK = AR * 64;                  // 5,120 B: one [80][32] image
+constexpr int A_QK = AR * 64;                  // 5,120 B: one [80][32] head image (attnhead.h)
 constexpr int A_IMGH = 2 * A_QK + 96 * 64;     // 16,384 B per head of a chunk: q | k | v (v: 96 rows, rows 80..95 stay zero)
 constexpr int A_LDS = A_XT + 2 * A_IMGH;       // 73,728 B
-constexpr float kAScale = 0.17677669529663687f;   // 1/sqrt(32)
 
 template <typename T>
 struct ABArgs {
@@ -54,35 +52,6 @@ struct ABArgs {
   int NB, S;
   DropCfg da, d1;
 };
-
-// [rows][32] 16-bit image, 64-B rows; the two 32-B halves of a row are swapped when (row >> 2) & 1 (csrc/attention.hip)
-__device__ __forceinline__ int ab_img_off(int row, int c4) {
-  return row * 64 + ((((c4 >> 1) ^ ((row >> 2) & 1))) << 5) + ((c4 & 1) << 4);
-}
-template <typename T>
-__device__ __forceinline__ typename H16<T>::frag ab_frag_row(const char* img, int row, int g) {
-  return *(const typename H16<T>::frag*)(img + ab_img_off(row, g));
-}
-// transposed fragment: slot 8g+j <-> row rbase + 16*(j>>2) + 4g + (j&3), column 16*dt + (lane&15)
-template <typename T>
-__device__ __forceinline__ typename H16<T>::frag ab_frag_tr(const char* img, int rbase, int dt, int lane) {
-  const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  s16x4 part[2];
-#pragma unroll
-  for (int h2 = 0; h2 < 2; ++h2) {
-    const int row = rbase + 16 * h2 + 4 * g + qq;
-    const int off = row * 64 + ((dt ^ (g & 1)) << 5) + pp * 8;
-    part[h2] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(img + off));
-  }
-  ab_s16x8 t = {part[0][0], part[0][1], part[0][2], part[0][3], part[1][0], part[1][1], part[1][2], part[1][3]};
-  return __builtin_bit_cast(typename H16<T>::frag, t);
-}
-template <typename T>
-__device__ __forceinline__ typename H16<T>::frag ab_pack_frag(const f32x4& a, const f32x4& b) {
-  const float fa[4] = {a[0], a[1], a[2], a[3]}, fb[4] = {b[0], b[1], b[2], b[3]};
-  const u32x2 lo = pack4<T>(fa), hi = pack4<T>(fb);
-  return __builtin_bit_cast(typename H16<T>::frag, (u32x4){lo[0], lo[1], hi[0], hi[1]});
-}
 
 // NKTX > 0: the tile count is a compile-time constant (no wave-uniform branches inside the unrolled tile loops: the scheduler
 // sees one straight-line body per query tile); TAIL: the last key tile holds ONE valid key (S = 16 n + 1) and evaluates one
@@ -190,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = acc1[i][j][q] + b1[j][q];
-        *(u32x2*)(imgs + ioff[j] + ab_img_off(r, c4) + ((g4 & 1) << 3)) = pack4<T>(v);
+        *(u32x2*)(imgs + ioff[j] + hd_img_off(r, c4) + ((g4 & 1) << 3)) = pack4<T>(v);
       }
     }
     __syncthreads();        // (B) the chunk's q, k, v images are complete
@@ -200,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
     for (int idx = tid; idx < S * 16; idx += 256) {
       const int row = idx >> 4, pc = idx & 15;
       const int part = 1 + (pc >> 3), th = (pc >> 2) & 1, c4 = pc & 3;
-      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + part * A_QK + ab_img_off(row, c4));
+      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + part * A_QK + hd_img_off(row, c4));
       *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + part * AD + (2 * c + th) * 32 + c4 * 8) = o;
     }
 
@@ -210,13 +179,13 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
       constexpr int ktail = TAIL ? NKTX - 1 : -1;
       frag kf[5];
 #pragma unroll
-      for (int kt = 0; kt < 5; ++kt) kf[kt] = ab_frag_row<T>(kimg, kt * 16 + l15, g4);
+      for (int kt = 0; kt < 5; ++kt) kf[kt] = hd_frag_row<T>(kimg, kt * 16 + l15, g4);
       for (int qt = role; qt < nkt; qt += 2) {
         const int q = qt * 16 + l15;
-        const frag qf = ab_frag_row<T>(qimg, q, g4);
+        const frag qf = hd_frag_row<T>(qimg, q, g4);
         {                                                    // this tile's q rows leave the chip before ctx replaces them
           const int row = qt * 16 + (lane >> 2), c4 = lane & 3;
-          if (row < S) *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + h * 32 + c4 * 8) = *(const u32x4*)(qimg + ab_img_off(row, c4));
+          if (row < S) *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + h * 32 + c4 * 8) = *(const u32x4*)(qimg + hd_img_off(row, c4));
         }
         f32x4 s[6];
         float mx = -INFINITY;
@@ -226,14 +195,14 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
           if (kt < 5 && kt < nkt) {
             s[kt] = H16<T>::mfma(kf[kt < 5 ? kt : 0], qf, s[kt]);
             if (kt == ktail) {                               // single valid key: one accumulator register (csrc/attention.hip)
-              const float v = g4 == 0 ? s[kt][0] * kAScale : -INFINITY;
+              const float v = g4 == 0 ? s[kt][0] * HD_SCALE : -INFINITY;
               s[kt][0] = v;
               mx = fmaxf(mx, v);
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int key = kt * 16 + 4 * g4 + r;
-                const float v = key < S ? s[kt][r] * kAScale : -INFINITY;
+                const float v = key < S ? s[kt][r] * HD_SCALE : -INFINITY;
                 s[kt][r] = v;
                 mx = fmaxf(mx, v);
               }
@@ -284,10 +253,10 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
 #pragma unroll
         for (int kp = 0; kp < 3; ++kp) {
           if (2 * kp < nkt) {
-            const frag pf = ab_pack_frag<T>(s[2 * kp], s[2 * kp + 1]);
+            const frag pf = hd_pack_frag<T>(s[2 * kp], s[2 * kp + 1]);
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-              const frag vf = ab_frag_tr<T>(vimg, 32 * kp, dt, lane);
+              const frag vf = hd_frag_tr<T>(vimg, 32 * kp, dt, lane);
               o[dt] = H16<T>::mfma(vf, pf, o[dt]);
             }
           }
@@ -298,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
           u32x2 pk;
           pk[0] = H16<T>::pack2(o[dt][0], o[dt][1]);
           pk[1] = H16<T>::pack2(o[dt][2], o[dt][3]);
-          *(u32x2*)(qimg + ab_img_off(q, 2 * dt + (g4 >> 1)) + ((g4 & 1) << 3)) = pk;
+          *(u32x2*)(qimg + hd_img_off(q, 2 * dt + (g4 >> 1)) + ((g4 & 1) << 3)) = pk;
         }
       }
     }
@@ -312,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
     // the stored ctx rows: 128 contiguous bytes per row (heads 2c, 2c+1)
     for (int idx = tid; idx < S * 8; idx += 256) {
       const int row = idx >> 3, th = (idx >> 2) & 1, c4 = idx & 3;
-      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + ab_img_off(row, c4));
+      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + hd_img_off(row, c4));
       *(u32x4*)(p.CTX + (row0 + row) * AD + (2 * c + th) * 32 + c4 * 8) = o;
     }
 
@@ -321,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
     for (int s = 0; s < 2; ++s) {
       frag cf[5];
 #pragma unroll
-      for (int i = 0; i < 5; ++i) cf[i] = ab_frag_row<T>(imgs + s * A_IMGH, l15 + 16 * i, g4);
+      for (int i = 0; i < 5; ++i) cf[i] = hd_frag_row<T>(imgs + s * A_IMGH, l15 + 16 * i, g4);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll

@@ -390,6 +390,18 @@ static inline void eg_launch_lds(dim3 grid, dim3 block, hipStream_t s, const Arg
   hipLaunchKernelGGL(KERN, grid, block, LDS, s, args...);
 }
 
+// host: the dtype switch of an entry point, said once.  f is a generic lambda that receives a tag and names the element type as
+// `typename decltype(tag)::type`; its result is returned.  The dtype has been validated by the caller (anything else is bf16).
+template <typename T> struct eg_type { typedef T type; };
+template <typename F>
+static inline auto eg_dispatch_16(int dtype, F&& f) {
+  return dtype == EG_F16 ? f(eg_type<f16_t>{}) : f(eg_type<bf16_t>{});
+}
+template <typename F>
+static inline auto eg_dispatch_dtype(int dtype, F&& f) {
+  return dtype == EG_F32 ? f(eg_type<float>{}) : eg_dispatch_16(dtype, f);
+}
+
 // grouped row addressing: row r of a logical [M, *] matrix lives at
 //   base + (r / rows_per_group) * group_stride + (r % rows_per_group) * row_stride   (elements)
 struct RowMap {

@@ -9,6 +9,7 @@
 //     fragment load is one contiguous 1-KB read per wave;
 //   * final epilogue: per 16-row tile the wave's four accumulator tiles pass through a wave-private fp32 image [16][RT_IMG_PITCH]; lane
 //     (er = lane / 4, ec = lane % 4) then owns the 16 consecutive columns 16 ec .. of row er.
+// (attnblock.hip's [rows][32] head images are not a row-tile piece: their layout and reads are attnhead.h's.)
 // The ring kernels' K-loop fragment reads (tn_body256, wide_tile, rs_gemm_kernel) stay where they are: a compiler-visible LDS load
 // after an LDS-DMA gets a vmcnt(0) in front of it, which is why those sit behind counted waits.
 #pragma once

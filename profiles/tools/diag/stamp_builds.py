@@ -61,7 +61,7 @@ extern "C" int eg_debug_stamps(void* out) { return (int)hipMemcpyFromSymbol(out,
 
 def gen_attn():
     s = (CS / "attention.hip").read_text()
-    s = rep(s, '#include "common.h"', """#include "../eyegaze_multimodal_amd/csrc/common.h"
+    s = rep(s, '#include "attnhead.h"', """#include "../eyegaze_multimodal_amd/csrc/attnhead.h"
 __device__ unsigned long long eg_stamps[2048][4][8];
 #define STAMPV(v_) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\\n\\ts_waitcnt lgkmcnt(0)" : "=s"(v_) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 extern "C" int eg_debug_stamps(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(eg_stamps), sizeof(eg_stamps)); }
