@@ -532,22 +532,15 @@ void launch_bwd(const void* qkv, const void* ctx, const void* dctx, const float*
   // 272 B of scratch per lane it had lost at SP = 128) a5 (SP = 128) 7.38 -> 7.04 ms, a5c32 (SP = 160, 186 registers, two waves per
   // SIMD) 14.49 -> 13.84 ms.
   constexpr int lds1 = 2 * (3 * SP * 64 + 2 * SP * 4 + 2 * 2 * 32 * 32);
-  static bool attr1 = false;
-  if (!attr1) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd1_kernel<T, SP, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-    (void)hipFuncSetAttribute((const void*)attn_bwd1_kernel<T, 96, 5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-    attr1 = true;
-  }
   if (SP == 96 && S == 65)           // class token + 64 positions: exact tile count, single-key tail tile
-    hipLaunchKernelGGL((attn_bwd1_kernel<T, 96, 5, true>), dim3(nblk), dim3(256), lds1, s, (const T*)qkv, (const T*)ctx,
-                       (const T*)dctx, lse, (T*)dqkv, NB, S, H, kv_shift, dc, st);
+    eg_launch_lds<attn_bwd1_kernel<T, 96, 5, true>, lds1>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx, (const T*)dctx, lse,
+                                                          (T*)dqkv, NB, S, H, kv_shift, dc, st);
   else
-    hipLaunchKernelGGL((attn_bwd1_kernel<T, SP, 0, false>), dim3(nblk), dim3(256), lds1, s, (const T*)qkv, (const T*)ctx,
-                       (const T*)dctx, lse, (T*)dqkv, NB, S, H, kv_shift, dc, st);
+    eg_launch_lds<attn_bwd1_kernel<T, SP, 0, false>, lds1>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx, (const T*)dctx, lse,
+                                                           (T*)dqkv, NB, S, H, kv_shift, dc, st);
 }
 
 // the 16-bit kernels' instantiation for (dtype, S): f(type tag, SP tag), SP = the tile-padded capacity 96 / 128 / HD_MAX_S
-template <int N> struct eg_int { static constexpr int value = N; };
 template <typename F>
 void dispatch_16_sp(int dtype, int S, F&& f) {
   eg_dispatch_16(dtype, [&](auto t) {
@@ -561,8 +554,8 @@ void dispatch_16_sp(int dtype, int S, F&& f) {
 
 extern "C" int eg_attention_fwd(const void* qkv, void* ctx, float* lse, int NB, int S, int H, int kv_shift, int dtype,
                                 float drop_p, uint32_t drop_site, const eg_step_state* state, void* stream) {
-  EG_CHECK(qkv && ctx && lse, "eg_attention_fwd: null pointer");
   if (hd_check("eg_attention_fwd", NB, S, H, kv_shift, dtype, drop_p, state, HD_MAX_S, true)) return 1;
+  EG_CHECK(qkv && ctx && lse, "eg_attention_fwd: null pointer");
   DropCfg dc = make_drop(drop_p, drop_site);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == EG_F32) {
@@ -581,8 +574,8 @@ extern "C" int eg_attention_fwd(const void* qkv, void* ctx, float* lse, int NB, 
 extern "C" int eg_attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int NB,
                                 int S, int H, int kv_shift, int dtype, float drop_p, uint32_t drop_site,
                                 const eg_step_state* state, void* stream) {
-  EG_CHECK(qkv && ctx && dctx && lse && dqkv, "eg_attention_bwd: null pointer");
   if (hd_check("eg_attention_bwd", NB, S, H, kv_shift, dtype, drop_p, state, HD_MAX_S, true)) return 1;
+  EG_CHECK(qkv && ctx && dctx && lse && dqkv, "eg_attention_bwd: null pointer");
   DropCfg dc = make_drop(drop_p, drop_site);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == EG_F32) {
@@ -636,8 +629,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q
 
 extern "C" int eg_attention_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int kv_shift,
                                   int dtype, void* stream) {
-  EG_CHECK(qkv && lse && probs, "eg_attention_probs: null pointer");
   if (hd_check("eg_attention_probs", NB, S, H, kv_shift, dtype, 0.f, nullptr, HD_MAX_S, true)) return 1;
+  EG_CHECK(qkv && lse && probs, "eg_attention_probs: null pointer");
   const int lds = 2 * S * 33 * 4;
   hipStream_t s = (hipStream_t)stream;
   eg_dispatch_dtype(dtype, [&](auto t) {

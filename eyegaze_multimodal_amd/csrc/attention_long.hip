@@ -579,8 +579,8 @@ static inline int long_blocks(int NB, int H, int S, int rows) { return NB * H * 
 
 extern "C" int eg_attention_long_fwd(const void* qkv, void* ctx, float* lse, int NB, int S, int H, int kv_shift, int dtype,
                                      float drop_p, uint32_t drop_site, const eg_step_state* state, void* stream) {
-  EG_CHECK(qkv && ctx && lse, "eg_attention_long_fwd: null pointer");
   if (attn_long_check("eg_attention_long_fwd", NB, S, H, kv_shift, dtype, drop_p, state)) return 1;
+  EG_CHECK(qkv && ctx && lse, "eg_attention_long_fwd: null pointer");
   const DropCfg dc = make_drop(drop_p, drop_site);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == EG_F32)
@@ -599,8 +599,8 @@ extern "C" int eg_attention_long_fwd(const void* qkv, void* ctx, float* lse, int
 extern "C" int eg_attention_long_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int NB,
                                      int S, int H, int kv_shift, int dtype, float drop_p, uint32_t drop_site,
                                      const eg_step_state* state, float* scratch, int64_t scratch_elems, void* stream) {
-  EG_CHECK(qkv && ctx && dctx && lse && dqkv && scratch, "eg_attention_long_bwd: null pointer");
   if (attn_long_check("eg_attention_long_bwd", NB, S, H, kv_shift, dtype, drop_p, state)) return 1;
+  EG_CHECK(qkv && ctx && dctx && lse && dqkv && scratch, "eg_attention_long_bwd: null pointer");
   const long long n = (long long)NB * H * S;
   EG_CHECK(scratch_elems >= n, "eg_attention_long_bwd: scratch holds %lld floats, NB*H*S = %lld are needed",
            (long long)scratch_elems, n);
@@ -631,8 +631,8 @@ extern "C" int eg_attention_long_bwd(const void* qkv, const void* ctx, const voi
 
 extern "C" int eg_attention_long_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int kv_shift,
                                        int dtype, void* stream) {
-  EG_CHECK(qkv && lse && probs, "eg_attention_long_probs: null pointer");
   if (attn_long_check("eg_attention_long_probs", NB, S, H, kv_shift, dtype, 0.f, nullptr)) return 1;
+  EG_CHECK(qkv && lse && probs, "eg_attention_long_probs: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(long_blocks(NB, H, S, PROBS_ROWS));
   eg_dispatch_dtype(dtype, [&](auto t) {

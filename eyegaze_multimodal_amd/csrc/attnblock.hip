@@ -372,5 +372,5 @@ extern "C" int eg_attn_block_fwd(const eg_attn_block_desc* d, void* stream) {
   EG_CHECK(((uintptr_t)d->x | (uintptr_t)d->wqkv_frag | (uintptr_t)d->wo_frag | (uintptr_t)d->qkv | (uintptr_t)d->ctx |
             (uintptr_t)d->r1 | (uintptr_t)d->bqkv | (uintptr_t)d->bo) % 16 == 0, "eg_attn_block_fwd: operands must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
-  return d->dtype == EG_F16 ? ab_launch<f16_t>(d, s) : ab_launch<bf16_t>(d, s);
+  return eg_dispatch_16(d->dtype, [&](auto t) { return ab_launch<typename decltype(t)::type>(d, s); });
 }

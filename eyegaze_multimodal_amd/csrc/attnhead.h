@@ -67,12 +67,13 @@ __device__ __forceinline__ float hd_dot32(const float* a, const float* b) {
 }
 
 // host: the argument check of eg_attention_* (max_s = HD_MAX_S, idx32: element indices of the dropout hash are 32 bit) and of
-// eg_attention_long_* (max_s = EG_ATTN_LONG_MAX_S, 64-bit indices)
+// eg_attention_long_* (max_s = EG_ATTN_LONG_MAX_S, 64-bit indices).  The dtype comes first, so the entry points call it before
+// they look at their pointers.
 static inline int hd_check(const char* who, int NB, int S, int H, int kv_shift, int dtype, float p, const void* st, int max_s, bool idx32) {
+  if (eg_dtype_check(who, dtype, true)) return 1;
   EG_CHECK(NB > 0 && S > 0 && H > 0, "%s: bad shape NB=%d S=%d H=%d", who, NB, S, H);
   EG_CHECK(S <= max_s, "%s: S=%d exceeds the %s limit of %d", who, S, idx32 ? "register-resident" : "long-attention", max_s);
   EG_CHECK(kv_shift >= 0 && kv_shift < NB, "%s: kv_shift=%d out of range", who, kv_shift);
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F32 || dtype == EG_F16, "%s: bad dtype %d", who, dtype);
   EG_CHECK(p >= 0.f && p < 1.f && (p == 0.f || st), "%s: dropout p=%f needs a step state", who, (double)p);
   EG_CHECK(!idx32 || (long long)NB * H * S * (S + 1) < (1ll << 32), "%s: NB*H*S*S exceeds the 32-bit dropout index", who);
   return 0;

@@ -401,6 +401,14 @@ template <typename F>
 static inline auto eg_dispatch_dtype(int dtype, F&& f) {
   return dtype == EG_F32 ? f(eg_type<float>{}) : eg_dispatch_16(dtype, f);
 }
+// an integer as a tag, for a dispatcher that also selects a compile-time size: f(type tag, eg_int<96>{}) reads it as decltype(n)::value
+template <int N> struct eg_int { static constexpr int value = N; };
+// the validation in front of the dispatchers, and the FIRST check of every entry point that takes a dtype: a call that is wrong in
+// several ways reports its dtype (tests/test_dtype_check_host.py calls every entry point with a bad dtype and nothing else)
+static inline int eg_dtype_check(const char* who, int dtype, bool f32_ok) {
+  if (dtype == EG_BF16 || dtype == EG_F16 || (f32_ok && dtype == EG_F32)) return 0;
+  return f32_ok ? eg_fail("%s: bad dtype %d", who, dtype) : eg_fail("%s: dtype %d (bf16 / fp16 only)", who, dtype);
+}
 
 // grouped row addressing: row r of a logical [M, *] matrix lives at
 //   base + (r / rows_per_group) * group_stride + (r % rows_per_group) * row_stride   (elements)

@@ -382,7 +382,7 @@ extern "C" int eg_ffn_chain(const eg_ffn_desc* d, void* stream) {
   EG_CHECK(((uintptr_t)d->A | (uintptr_t)d->W1 | (uintptr_t)d->W2 | (uintptr_t)d->H | (uintptr_t)d->C | (uintptr_t)d->gate |
             (uintptr_t)d->residual) % 16 == 0, "eg_ffn_chain: operands must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
-  return d->dtype == EG_F16 ? ffn_launch<f16_t>(d, s) : ffn_launch<bf16_t>(d, s);
+  return eg_dispatch_16(d->dtype, [&](auto t) { return ffn_launch<typename decltype(t)::type>(d, s); });
 }
 
 extern "C" int64_t eg_ffn_gate_bits_bytes(int M, int F) {

@@ -859,7 +859,7 @@ extern "C" int eg_gemm_nt(const eg_gemm_desc* d, void* stream) {
     if (rc == 0) return 0;
     if (rc != -1) return eg_fail("rs_gemm launch failed");
   }
-  return d->dtype == EG_BF16 ? launch_gemm_nt<bf16_t>(d, s) : d->dtype == EG_F16 ? launch_gemm_nt<f16_t>(d, s) : launch_gemm_nt<float>(d, s);
+  return eg_dispatch_dtype(d->dtype, [&](auto t) { return launch_gemm_nt<typename decltype(t)::type>(d, s); });
 }
 
 static int gemm_nt_batch_check(const eg_gemm_desc* descs, int n) {
@@ -941,7 +941,7 @@ extern "C" int eg_gemm_tn(const eg_gemm_tn_desc* d, void* stream) {
                                               (d->x_tile_stride == 0 || d->x_tile_stride == 128)),
            "eg_gemm_tn: tile=%d (256 needs a 16-bit dtype, N and K multiples of 256, contiguous X rows)", d->tile);
   hipStream_t s = (hipStream_t)stream;
-  return d->dtype == EG_BF16 ? launch_gemm_tn<bf16_t>(d, s) : d->dtype == EG_F16 ? launch_gemm_tn<f16_t>(d, s) : launch_gemm_tn<float>(d, s);
+  return eg_dispatch_dtype(d->dtype, [&](auto t) { return launch_gemm_tn<typename decltype(t)::type>(d, s); });
 }
 
 extern "C" int eg_reduce_partials(float* partial, float* out, int64_t n, int splits, int64_t split_stride,
@@ -994,40 +994,30 @@ extern "C" int eg_unpack_conv_wgrad(const float* partial, float* dW, int splits,
 
 extern "C" int eg_colsum(const void* Y, eg_rowmap y, int M, int N, float* partial, int nblk, int dtype,
                          void* stream) {
+  if (eg_dtype_check("eg_colsum", dtype, true)) return 1;
   EG_CHECK(Y && partial && M > 0 && N > 0 && nblk > 0, "eg_colsum: bad arguments");
   EG_CHECK(N % 8 == 0 && N <= 1024, "eg_colsum: N=%d must be a multiple of 8 and <= 1024", N);
   const int rpb = (M + nblk - 1) / nblk;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)Y,
-                       to_rowmap(y), M, N, rpb, partial);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(colsum_kernel<f16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const f16_t*)Y,
-                       to_rowmap(y), M, N, rpb, partial);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const float*)Y,
-                       to_rowmap(y), M, N, rpb, partial);
-  else
-    return eg_fail("eg_colsum: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(colsum_kernel<T>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const T*)Y, to_rowmap(y), M, N, rpb, partial);
+  });
   EG_LAUNCH_CHECK("colsum");
   return 0;
 }
 
 extern "C" int eg_gemm_tn_grouped(const eg_tn_problem* probs, int nprob, int total_blocks, int M, int splits, int dtype,
                                   void* stream) {
+  if (eg_dtype_check("eg_gemm_tn_grouped", dtype, true)) return 1;
   EG_CHECK(probs && nprob > 0 && total_blocks > 0 && M > 0 && splits > 0, "eg_gemm_tn_grouped: bad arguments");
-  EG_CHECK(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "eg_gemm_tn_grouped: bad dtype %d", dtype);
   int rps = (M + splits - 1) / splits;
   rps = (rps + 63) / 64 * 64;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel<bf16_t>, dim3(total_blocks), dim3(256), 2 * TNCfg<bf16_t>::STAGE_ROWS * TNCfg<bf16_t>::ROWB,
-                       s, probs, nprob, M, splits, rps);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel<f16_t>, dim3(total_blocks), dim3(256), 2 * TNCfg<f16_t>::STAGE_ROWS * TNCfg<f16_t>::ROWB,
-                       s, probs, nprob, M, splits, rps);
-  else
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel<float>, dim3(total_blocks), dim3(256), 2 * TNCfg<float>::STAGE_ROWS * TNCfg<float>::ROWB,
-                       s, probs, nprob, M, splits, rps);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(gemm_tn_grouped_kernel<T>, dim3(total_blocks), dim3(256), 2 * TNCfg<T>::STAGE_ROWS * TNCfg<T>::ROWB, s, probs, nprob,
+                       M, splits, rps);
+  });
   EG_LAUNCH_CHECK("gemm_tn_grouped");
   return 0;
 }
@@ -1035,16 +1025,16 @@ extern "C" int eg_gemm_tn_grouped(const eg_tn_problem* probs, int nprob, int tot
 // the same problem table served by 256 x 256 tiles: blk0 counts (N/256) * (K/256) * splits blocks per problem
 extern "C" int eg_gemm_tn_grouped256(const eg_tn_problem* probs, int nprob, int total_blocks, int M, int splits, int dtype,
                                      void* stream) {
+  if (eg_dtype_check("eg_gemm_tn_grouped256", dtype, false)) return 1;
   EG_CHECK(probs && nprob > 0 && total_blocks > 0 && M > 0 && splits > 0, "eg_gemm_tn_grouped256: bad arguments");
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F16, "eg_gemm_tn_grouped256: 16-bit dtypes only (got %d)", dtype);
   int rps = (M + splits - 1) / splits;
   rps = (rps + 63) / 64 * 64;
   hipStream_t s = (hipStream_t)stream;
   constexpr int lds = 4 * 2 * 32 * 512;                  // tn_body256's four-stage ring
-  if (dtype == EG_BF16)
-    eg_launch_lds<gemm_tn_grouped256_kernel<bf16_t>, lds>(dim3(total_blocks), dim3(512), s, probs, nprob, M, splits, rps);
-  else
-    eg_launch_lds<gemm_tn_grouped256_kernel<f16_t>, lds>(dim3(total_blocks), dim3(512), s, probs, nprob, M, splits, rps);
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    eg_launch_lds<gemm_tn_grouped256_kernel<T>, lds>(dim3(total_blocks), dim3(512), s, probs, nprob, M, splits, rps);
+  });
   EG_LAUNCH_CHECK("gemm_tn_grouped256");
   return 0;
 }

@@ -901,36 +901,30 @@ __global__ __launch_bounds__(256) void heads_bwd_pool_kernel(const T* __restrict
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F16, CALL_F32, who) \
-  if ((dtype) == EG_BF16) { CALL_BF16; }                      \
-  else if ((dtype) == EG_F16) { CALL_F16; }                   \
-  else if ((dtype) == EG_F32) { CALL_F32; }                   \
-  else return eg_fail("%s: bad dtype %d", who, (int)(dtype));
-
 extern "C" int eg_rows_bcast_f32(const float* src, const float* pos, void* seq, int NB, int S, int D, int R, int off,
                                  int src_nb, int dtype, void* stream) {
+  if (eg_dtype_check("eg_rows_bcast_f32", dtype, true)) return 1;
   EG_CHECK(src && seq && NB > 0 && R > 0 && off >= 0 && off + R <= S && src_nb > 0, "eg_rows_bcast_f32: bad arguments");
   dim3 grid(R, NB);
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(rows_bcast_f32_kernel<bf16_t>, grid, dim3(256), 0, s, src, pos, (bf16_t*)seq, NB, S, D, R, off, src_nb),
-             hipLaunchKernelGGL(rows_bcast_f32_kernel<f16_t>, grid, dim3(256), 0, s, src, pos, (f16_t*)seq, NB, S, D, R, off, src_nb),
-             hipLaunchKernelGGL(rows_bcast_f32_kernel<float>, grid, dim3(256), 0, s, src, pos, (float*)seq, NB, S, D, R, off, src_nb),
-             "eg_rows_bcast_f32");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(rows_bcast_f32_kernel<T>, grid, dim3(256), 0, s, src, pos, (T*)seq, NB, S, D, R, off, src_nb);
+  });
   EG_LAUNCH_CHECK("rows_bcast_f32");
   return 0;
 }
 
 extern "C" int eg_rows_copy(void* seq, int S, int D, int R, int off, int b_src0, int b_dst0, int nb, int dtype,
                             void* stream) {
+  if (eg_dtype_check("eg_rows_copy", dtype, true)) return 1;
   EG_CHECK(seq && nb > 0 && R > 0 && off >= 0 && off + R <= S, "eg_rows_copy: bad arguments");
   dim3 grid(R, nb);
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(rows_copy_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)seq, S, D, R, off, b_src0, b_dst0),
-             hipLaunchKernelGGL(rows_copy_kernel<f16_t>, grid, dim3(256), 0, s, (f16_t*)seq, S, D, R, off, b_src0, b_dst0),
-             hipLaunchKernelGGL(rows_copy_kernel<float>, grid, dim3(256), 0, s, (float*)seq, S, D, R, off, b_src0, b_dst0),
-             "eg_rows_copy");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(rows_copy_kernel<T>, grid, dim3(256), 0, s, (T*)seq, S, D, R, off, b_src0, b_dst0);
+  });
   EG_LAUNCH_CHECK("rows_copy");
   return 0;
 }
@@ -938,15 +932,16 @@ extern "C" int eg_rows_copy(void* seq, int S, int D, int R, int off, int b_src0,
 extern "C" int eg_pool_fuse_fwd(const void* z, float* cls1, float* cls2, void* comb, void* zf, float* ibs_pool_f,
                                 void* ibs_pool, int B, int S, int D, int off, int n_ibs, int ibs_first, int dtype,
                                 void* stream) {
+  if (eg_dtype_check("eg_pool_fuse_fwd", dtype, true)) return 1;
   EG_CHECK(z && cls1 && cls2 && comb && zf, "eg_pool_fuse_fwd: null pointer");
   EG_CHECK(B > 0 && off > 0 && off < S, "eg_pool_fuse_fwd: bad shape");
   EG_CHECK(n_ibs == 0 || (ibs_pool_f && ibs_pool && ibs_first >= 1 && ibs_first + n_ibs <= S), "eg_pool_fuse_fwd: ibs range");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(pool_fuse_fwd_kernel<bf16_t>, dim3(B), dim3(256), 0, s, (const bf16_t*)z, cls1, cls2, (bf16_t*)comb, (bf16_t*)zf, ibs_pool_f, (bf16_t*)ibs_pool, B, S, D, off, n_ibs, ibs_first),
-             hipLaunchKernelGGL(pool_fuse_fwd_kernel<f16_t>, dim3(B), dim3(256), 0, s, (const f16_t*)z, cls1, cls2, (f16_t*)comb, (f16_t*)zf, ibs_pool_f, (f16_t*)ibs_pool, B, S, D, off, n_ibs, ibs_first),
-             hipLaunchKernelGGL(pool_fuse_fwd_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)z, cls1, cls2, (float*)comb, (float*)zf, ibs_pool_f, (float*)ibs_pool, B, S, D, off, n_ibs, ibs_first),
-             "eg_pool_fuse_fwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pool_fuse_fwd_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)z, cls1, cls2, (T*)comb, (T*)zf, ibs_pool_f,
+                       (T*)ibs_pool, B, S, D, off, n_ibs, ibs_first);
+  });
   EG_LAUNCH_CHECK("pool_fuse_fwd");
   return 0;
 }
@@ -954,14 +949,15 @@ extern "C" int eg_pool_fuse_fwd(const void* z, float* cls1, float* cls2, void* c
 extern "C" int eg_pool_fuse_bwd(const void* z, const void* dcomb, const void* dzf, const float* gcls1, const float* gcls2,
                                 const void* dibs_pool, const float* gibs_pool, void* dz, int B, int S, int D, int off,
                                 int n_ibs, int ibs_first, int dtype, void* stream) {
+  if (eg_dtype_check("eg_pool_fuse_bwd", dtype, true)) return 1;
   EG_CHECK(z && dcomb && dzf && dz, "eg_pool_fuse_bwd: null pointer");
   EG_CHECK(B > 0 && off > 0 && off < S, "eg_pool_fuse_bwd: bad shape");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(pool_fuse_bwd_kernel<bf16_t>, dim3(B), dim3(256), 0, s, (const bf16_t*)z, (const bf16_t*)dcomb, (const bf16_t*)dzf, gcls1, gcls2, (const bf16_t*)dibs_pool, gibs_pool, (bf16_t*)dz, B, S, D, off, n_ibs, ibs_first),
-             hipLaunchKernelGGL(pool_fuse_bwd_kernel<f16_t>, dim3(B), dim3(256), 0, s, (const f16_t*)z, (const f16_t*)dcomb, (const f16_t*)dzf, gcls1, gcls2, (const f16_t*)dibs_pool, gibs_pool, (f16_t*)dz, B, S, D, off, n_ibs, ibs_first),
-             hipLaunchKernelGGL(pool_fuse_bwd_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)z, (const float*)dcomb, (const float*)dzf, gcls1, gcls2, (const float*)dibs_pool, gibs_pool, (float*)dz, B, S, D, off, n_ibs, ibs_first),
-             "eg_pool_fuse_bwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pool_fuse_bwd_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)z, (const T*)dcomb, (const T*)dzf, gcls1, gcls2,
+                       (const T*)dibs_pool, gibs_pool, (T*)dz, B, S, D, off, n_ibs, ibs_first);
+  });
   EG_LAUNCH_CHECK("pool_fuse_bwd");
   return 0;
 }
@@ -969,16 +965,17 @@ extern "C" int eg_pool_fuse_bwd(const void* z, const void* dcomb, const void* dz
 extern "C" int eg_classifier_ce_fwd(const void* h, const float* W, const float* bias, const int64_t* labels,
                                     float* logits, float* sample_loss, float* loss, int B, int K, int ncls, int dtype,
                                     void* stream) {
+  if (eg_dtype_check("eg_classifier_ce_fwd", dtype, true)) return 1;
   EG_CHECK(h && W && bias && logits, "eg_classifier_ce_fwd: null pointer");
   EG_CHECK(B > 0 && K > 0 && ncls > 0 && ncls <= 16, "eg_classifier_ce_fwd: ncls=%d must be in [1,16]", ncls);
   EG_CHECK(!labels || (sample_loss && loss), "eg_classifier_ce_fwd: labels need sample_loss and loss outputs");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B + 3) / 4);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(classifier_ce_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)h, W, bias, (const long long*)labels, logits, sample_loss, B, K, ncls),
-             hipLaunchKernelGGL(classifier_ce_fwd_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)h, W, bias, (const long long*)labels, logits, sample_loss, B, K, ncls),
-             hipLaunchKernelGGL(classifier_ce_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)h, W, bias, (const long long*)labels, logits, sample_loss, B, K, ncls),
-             "eg_classifier_ce_fwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(classifier_ce_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)h, W, bias, (const long long*)labels, logits,
+                       sample_loss, B, K, ncls);
+  });
   if (labels) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, sample_loss, loss, B);
   EG_LAUNCH_CHECK("classifier_ce_fwd");
   return 0;
@@ -988,44 +985,44 @@ extern "C" int eg_classifier_ce_bwd(const void* h, const float* W, const float* 
                                     const float* gloss, const float* glogits, float* dlogits, void* dh, float* dW,
                                     float* db, int B, int K, int ncls, int use_gate, float gate_scale, int dtype,
                                     void* stream) {
+  if (eg_dtype_check("eg_classifier_ce_bwd", dtype, true)) return 1;
   EG_CHECK(h && W && logits && dlogits && dh && dW && db, "eg_classifier_ce_bwd: null pointer");
   EG_CHECK(B > 0 && K > 0 && ncls > 0 && ncls <= 16, "eg_classifier_ce_bwd: bad shape");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B + 3) / 4);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(classifier_ce_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (bf16_t*)dh, B, K, ncls, use_gate, gate_scale);
-             hipLaunchKernelGGL(classifier_wgrad_kernel<bf16_t>, dim3(ncls, (K + 63) / 64), dim3(256), 0, s, (const bf16_t*)h, dlogits, dW, db, B, K, ncls),
-             hipLaunchKernelGGL(classifier_ce_bwd_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (f16_t*)dh, B, K, ncls, use_gate, gate_scale);
-             hipLaunchKernelGGL(classifier_wgrad_kernel<f16_t>, dim3(ncls, (K + 63) / 64), dim3(256), 0, s, (const f16_t*)h, dlogits, dW, db, B, K, ncls),
-             hipLaunchKernelGGL(classifier_ce_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (float*)dh, B, K, ncls, use_gate, gate_scale);
-             hipLaunchKernelGGL(classifier_wgrad_kernel<float>, dim3(ncls, (K + 63) / 64), dim3(256), 0, s, (const float*)h, dlogits, dW, db, B, K, ncls),
-             "eg_classifier_ce_bwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(classifier_ce_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)h, W, logits, (const long long*)labels, gloss,
+                       glogits, dlogits, (T*)dh, B, K, ncls, use_gate, gate_scale);
+    hipLaunchKernelGGL(classifier_wgrad_kernel<T>, dim3(ncls, (K + 63) / 64), dim3(256), 0, s, (const T*)h, dlogits, dW, db, B, K, ncls);
+  });
   EG_LAUNCH_CHECK("classifier_ce_bwd");
   return 0;
 }
 
 extern "C" int eg_batch_rowsum(const void* dseq, float* out, int NB, int S, int D, int rows, int dtype, void* stream) {
+  if (eg_dtype_check("eg_batch_rowsum", dtype, true)) return 1;
   EG_CHECK(dseq && out && NB > 0 && rows > 0 && rows <= S, "eg_batch_rowsum: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(batch_rowsum_kernel<bf16_t>, dim3(rows, (D + 63) / 64), dim3(256), 0, s, (const bf16_t*)dseq, out, NB, S, D),
-             hipLaunchKernelGGL(batch_rowsum_kernel<f16_t>, dim3(rows, (D + 63) / 64), dim3(256), 0, s, (const f16_t*)dseq, out, NB, S, D),
-             hipLaunchKernelGGL(batch_rowsum_kernel<float>, dim3(rows, (D + 63) / 64), dim3(256), 0, s, (const float*)dseq, out, NB, S, D),
-             "eg_batch_rowsum");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(batch_rowsum_kernel<T>, dim3(rows, (D + 63) / 64), dim3(256), 0, s, (const T*)dseq, out, NB, S, D);
+  });
   EG_LAUNCH_CHECK("batch_rowsum");
   return 0;
 }
 
 extern "C" int eg_rows_gather_gate(const void* src, const void* gate, void* dst, eg_rowmap dmap, int nb, int S, int D,
                                    int R, int off, int pair_shift, float gate_scale, int dtype, void* stream) {
+  if (eg_dtype_check("eg_rows_gather_gate", dtype, true)) return 1;
   EG_CHECK(src && dst && nb > 0 && R > 0 && off >= 0 && off + R <= S && D % 4 == 0, "eg_rows_gather_gate: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(R, nb);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(rows_gather_gate_kernel<bf16_t>, grid, dim3(64), 0, s, (const bf16_t*)src, (const bf16_t*)gate, (bf16_t*)dst, to_rowmap(dmap), S, D, R, off, pair_shift, gate_scale),
-             hipLaunchKernelGGL(rows_gather_gate_kernel<f16_t>, grid, dim3(64), 0, s, (const f16_t*)src, (const f16_t*)gate, (f16_t*)dst, to_rowmap(dmap), S, D, R, off, pair_shift, gate_scale),
-             hipLaunchKernelGGL(rows_gather_gate_kernel<float>, grid, dim3(64), 0, s, (const float*)src, (const float*)gate, (float*)dst, to_rowmap(dmap), S, D, R, off, pair_shift, gate_scale),
-             "eg_rows_gather_gate");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(rows_gather_gate_kernel<T>, grid, dim3(64), 0, s, (const T*)src, (const T*)gate, (T*)dst, to_rowmap(dmap), S, D, R,
+                       off, pair_shift, gate_scale);
+  });
   EG_LAUNCH_CHECK("rows_gather_gate");
   return 0;
 }
@@ -1033,24 +1030,21 @@ extern "C" int eg_rows_gather_gate(const void* src, const void* gate, void* dst,
 // ------------------------------------------------------------------------------------------------
 // fused tail entry points (16-bit compute dtypes, d_model == 256)
 // ------------------------------------------------------------------------------------------------
-#define DISPATCH_H16(dtype, CALL_BF16, CALL_F16, who)         \
-  if ((dtype) == EG_BF16) { CALL_BF16; }                      \
-  else if ((dtype) == EG_F16) { CALL_F16; }                   \
-  else return eg_fail("%s: dtype %d (bf16 / fp16 only)", who, (int)(dtype));
-
 extern "C" int eg_token_grad_tail(const void* dseq, const void* gate, void* dst, eg_rowmap dmap, float* pos_grad,
                                   float* cls_grad, int NB, int S, int D, int R, int off, float gate_scale, int dtype,
                                   void* stream) {
+  if (eg_dtype_check("eg_token_grad_tail", dtype, false)) return 1;
   EG_CHECK(dseq && gate && dst && pos_grad, "eg_token_grad_tail: null pointer");
   EG_CHECK(NB > 0 && S > 0 && R > 0 && off >= 0 && off + R <= S, "eg_token_grad_tail: bad shape NB=%d S=%d R=%d off=%d", NB, S, R, off);
   EG_CHECK(D > 0 && D % 64 == 0, "eg_token_grad_tail: D=%d must be a multiple of 64", D);
   EG_CHECK(dmap.row_stride % 4 == 0 && dmap.group_stride % 4 == 0, "eg_token_grad_tail: destination rows must be 8-B aligned");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(S, D / 64);
-  DISPATCH_H16(dtype,
-               hipLaunchKernelGGL(token_grad_tail_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dseq, (const bf16_t*)gate, (bf16_t*)dst, to_rowmap(dmap), pos_grad, cls_grad, NB, S, D, R, off, gate_scale),
-               hipLaunchKernelGGL(token_grad_tail_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)dseq, (const f16_t*)gate, (f16_t*)dst, to_rowmap(dmap), pos_grad, cls_grad, NB, S, D, R, off, gate_scale),
-               "eg_token_grad_tail");
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(token_grad_tail_kernel<T>, grid, dim3(256), 0, s, (const T*)dseq, (const T*)gate, (T*)dst, to_rowmap(dmap), pos_grad,
+                       cls_grad, NB, S, D, R, off, gate_scale);
+  });
   EG_LAUNCH_CHECK("token_grad_tail");
   return 0;
 }
@@ -1072,6 +1066,7 @@ extern "C" int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* W
                             const float* bc0, const float* W3, const float* b3, const int64_t* labels, float* logits,
                             float* sample_loss, float* loss, uint32_t* counter, int B, int D, int ncls, float drop_p,
                             uint32_t drop_site, const eg_step_state* state, int dtype, void* stream) {
+  if (eg_dtype_check("eg_heads_fwd", dtype, false)) return 1;
   EG_CHECK(comb && zf && hcl && Wsf && bsf && Wc0 && bc0 && W3 && b3 && logits, "eg_heads_fwd: null pointer");
   EG_CHECK(D == HD, "eg_heads_fwd: d_model=%d (the fused heads are built for 256)", D);
   EG_CHECK(B > 0 && ncls > 0 && ncls <= 16, "eg_heads_fwd: B=%d, ncls=%d must be in [1,16]", B, ncls);
@@ -1080,10 +1075,10 @@ extern "C" int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* W
   EG_CHECK(((uintptr_t)comb | (uintptr_t)zf | (uintptr_t)hcl | (uintptr_t)Wsf | (uintptr_t)Wc0 | (uintptr_t)bsf | (uintptr_t)bc0) % 16 == 0,
            "eg_heads_fwd: alignment");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_H16(dtype,
-               launch_heads_fwd<bf16_t>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B, ncls, drop_p, drop_site, state, s),
-               launch_heads_fwd<f16_t>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B, ncls, drop_p, drop_site, state, s),
-               "eg_heads_fwd");
+  eg_dispatch_16(dtype, [&](auto t) {
+    launch_heads_fwd<typename decltype(t)::type>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B,
+                                                 ncls, drop_p, drop_site, state, s);
+  });
   EG_LAUNCH_CHECK("heads_fwd");
   return 0;
 }
@@ -1092,22 +1087,25 @@ extern "C" int eg_classifier_ce_bwd_fused(const void* h, const float* W, const f
                                           const float* gloss, const float* glogits, float* dlogits, void* dh, float* dW,
                                           float* db, int B, int K, int ncls, int use_gate, float gate_scale, int dtype,
                                           void* stream) {
+  if (eg_dtype_check("eg_classifier_ce_bwd_fused", dtype, false)) return 1;
   EG_CHECK(h && W && logits && dlogits && dh && dW && db, "eg_classifier_ce_bwd_fused: null pointer");
   EG_CHECK(B > 0 && B <= 256 && K > 0 && ncls > 0 && ncls <= 16, "eg_classifier_ce_bwd_fused: bad shape B=%d (<= 256) K=%d ncls=%d", B, K, ncls);
   EG_CHECK((uintptr_t)h % 16 == 0, "eg_classifier_ce_bwd_fused: alignment");
   hipStream_t s = (hipStream_t)stream;
   const int nce = (B + 3) / 4;
   dim3 grid(nce + (K + 63) / 64);
-  DISPATCH_H16(dtype,
-               hipLaunchKernelGGL(classifier_ce_bwd_fused_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (bf16_t*)dh, dW, db, B, K, ncls, use_gate, gate_scale, nce),
-               hipLaunchKernelGGL(classifier_ce_bwd_fused_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)h, W, logits, (const long long*)labels, gloss, glogits, dlogits, (f16_t*)dh, dW, db, B, K, ncls, use_gate, gate_scale, nce),
-               "eg_classifier_ce_bwd_fused");
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(classifier_ce_bwd_fused_kernel<T>, grid, dim3(256), 0, s, (const T*)h, W, logits, (const long long*)labels, gloss,
+                       glogits, dlogits, (T*)dh, dW, db, B, K, ncls, use_gate, gate_scale, nce);
+  });
   EG_LAUNCH_CHECK("classifier_ce_bwd_fused");
   return 0;
 }
 
 extern "C" int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void* sfT, const void* zf, void* dzf, void* dcomb,
                                   float* dWc0, float* dbc0, int B, int D, int dtype, void* stream) {
+  if (eg_dtype_check("eg_heads_bwd_chain", dtype, false)) return 1;
   EG_CHECK(dhcl && c0T && sfT && zf && dzf && dcomb && dWc0 && dbc0, "eg_heads_bwd_chain: null pointer");
   EG_CHECK(D == HD, "eg_heads_bwd_chain: d_model=%d (the fused heads are built for 256)", D);
   EG_CHECK(B > 0 && B <= 256, "eg_heads_bwd_chain: B=%d (the in-launch weight gradients sum at most 256 rows)", B);
@@ -1116,10 +1114,11 @@ extern "C" int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void*
   hipStream_t s = (hipStream_t)stream;
   const int nrt = (B + 15) / 16;
   dim3 grid(nrt + (HD / 64) * (HK / 64));
-  DISPATCH_H16(dtype,
-               hipLaunchKernelGGL(heads_bwd_chain_kernel<bf16_t>, grid, dim3(512), 0, s, (const bf16_t*)dhcl, (const bf16_t*)c0T, (const bf16_t*)sfT, (const bf16_t*)zf, (bf16_t*)dzf, (bf16_t*)dcomb, dWc0, dbc0, B, nrt),
-               hipLaunchKernelGGL(heads_bwd_chain_kernel<f16_t>, grid, dim3(512), 0, s, (const f16_t*)dhcl, (const f16_t*)c0T, (const f16_t*)sfT, (const f16_t*)zf, (f16_t*)dzf, (f16_t*)dcomb, dWc0, dbc0, B, nrt),
-               "eg_heads_bwd_chain");
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(heads_bwd_chain_kernel<T>, grid, dim3(512), 0, s, (const T*)dhcl, (const T*)c0T, (const T*)sfT, (const T*)zf,
+                       (T*)dzf, (T*)dcomb, dWc0, dbc0, B, nrt);
+  });
   EG_LAUNCH_CHECK("heads_bwd_chain");
   return 0;
 }
@@ -1127,6 +1126,7 @@ extern "C" int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void*
 extern "C" int eg_heads_bwd_pool(const void* z, const void* dcomb, const void* dzf, const float* gcls1, const float* gcls2,
                                  const void* dibs_pool, const float* gibs_pool, void* dz, const void* comb, float* dWsf,
                                  float* dbsf, int B, int S, int D, int off, int n_ibs, int ibs_first, int dtype, void* stream) {
+  if (eg_dtype_check("eg_heads_bwd_pool", dtype, false)) return 1;
   EG_CHECK(z && dcomb && dzf && dz && comb && dWsf && dbsf, "eg_heads_bwd_pool: null pointer");
   EG_CHECK(D == HD, "eg_heads_bwd_pool: d_model=%d (the fused heads are built for 256)", D);
   EG_CHECK(B > 0 && B <= 256 && off > 0 && off < S, "eg_heads_bwd_pool: bad shape B=%d (<= 256) S=%d off=%d", B, S, off);
@@ -1134,10 +1134,11 @@ extern "C" int eg_heads_bwd_pool(const void* z, const void* dcomb, const void* d
   EG_CHECK(((uintptr_t)dzf | (uintptr_t)comb | (uintptr_t)dWsf) % 16 == 0, "eg_heads_bwd_pool: alignment");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(B + (HD / 64) * (HK / 64));
-  DISPATCH_H16(dtype,
-               hipLaunchKernelGGL(heads_bwd_pool_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)z, (const bf16_t*)dcomb, (const bf16_t*)dzf, gcls1, gcls2, (const bf16_t*)dibs_pool, gibs_pool, (bf16_t*)dz, (const bf16_t*)comb, dWsf, dbsf, B, S, D, off, n_ibs, ibs_first),
-               hipLaunchKernelGGL(heads_bwd_pool_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)z, (const f16_t*)dcomb, (const f16_t*)dzf, gcls1, gcls2, (const f16_t*)dibs_pool, gibs_pool, (f16_t*)dz, (const f16_t*)comb, dWsf, dbsf, B, S, D, off, n_ibs, ibs_first),
-               "eg_heads_bwd_pool");
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(heads_bwd_pool_kernel<T>, grid, dim3(256), 0, s, (const T*)z, (const T*)dcomb, (const T*)dzf, gcls1, gcls2,
+                       (const T*)dibs_pool, gibs_pool, (T*)dz, (const T*)comb, dWsf, dbsf, B, S, D, off, n_ibs, ibs_first);
+  });
   EG_LAUNCH_CHECK("heads_bwd_pool");
   return 0;
 }

@@ -194,5 +194,5 @@ extern "C" int eg_ln_bwd_proj(const eg_ln_bwd_proj_desc* d, void* stream) {
   EG_CHECK(((uintptr_t)d->dy | (uintptr_t)d->x | (uintptr_t)d->W_frag | (uintptr_t)d->dx | (uintptr_t)d->dx_drop | (uintptr_t)d->dC) % 16 == 0,
            "eg_ln_bwd_proj: operands must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
-  return d->dtype == EG_F16 ? lnproj_launch<f16_t>(d, s) : lnproj_launch<bf16_t>(d, s);
+  return eg_dispatch_16(d->dtype, [&](auto t) { return lnproj_launch<typename decltype(t)::type>(d, s); });
 }

@@ -261,35 +261,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd256_kernel(const T* __restri
 
 extern "C" int eg_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats, int M, int D,
                                 int dtype, void* stream) {
+  if (eg_dtype_check("eg_layernorm_fwd", dtype, true)) return 1;
   EG_CHECK(x && gamma && beta && y, "eg_layernorm_fwd: null pointer");
   EG_CHECK(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "eg_layernorm_fwd: D=%d must be a multiple of 4, <= 1024", D);
-  dim3 grid((M + 3) / 4);
-  if (D == 256 && (dtype == EG_BF16 || dtype == EG_F32 || dtype == EG_F16)) {
-    dim3 g8((M + 7) / 8);
-    if (dtype == EG_BF16)
-      hipLaunchKernelGGL(layernorm_fwd256_kernel<bf16_t>, g8, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gamma, beta,
-                         (bf16_t*)y, stats, M);
-    else if (dtype == EG_F16)
-      hipLaunchKernelGGL(layernorm_fwd256_kernel<f16_t>, g8, dim3(256), 0, (hipStream_t)stream, (const f16_t*)x, gamma, beta,
-                         (f16_t*)y, stats, M);
+  hipStream_t s = (hipStream_t)stream;
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (D == 256)
+      hipLaunchKernelGGL(layernorm_fwd256_kernel<T>, dim3((M + 7) / 8), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, stats, M);
     else
-      hipLaunchKernelGGL(layernorm_fwd256_kernel<float>, g8, dim3(256), 0, (hipStream_t)stream, (const float*)x, gamma, beta,
-                         (float*)y, stats, M);
-    EG_LAUNCH_CHECK("layernorm_fwd256");
-    return 0;
-  }
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gamma,
-                       beta, (bf16_t*)y, stats, M, D);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const f16_t*)x, gamma,
-                       beta, (f16_t*)y, stats, M, D);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, gamma, beta,
-                       (float*)y, stats, M, D);
-  else
-    return eg_fail("eg_layernorm_fwd: bad dtype %d", dtype);
-  EG_LAUNCH_CHECK("layernorm_fwd");
+      hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3((M + 3) / 4), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, stats, M, D);
+  });
+  EG_LAUNCH_CHECK(D == 256 ? "layernorm_fwd256" : "layernorm_fwd");
   return 0;
 }
 
@@ -297,6 +280,7 @@ extern "C" int eg_layernorm_bwd(const void* dy, const void* x, const float* stat
                                 void* dx_drop, float* partial, int nblk, int partial_capacity_blocks, int M, int D, int dtype,
                                 float drop1_p, uint32_t drop1_site, float drop2_p, uint32_t drop2_site,
                                 const eg_step_state* state, void* stream) {
+  if (eg_dtype_check("eg_layernorm_bwd", dtype, true)) return 1;
   EG_CHECK(dy && x && stats && gamma && dx && partial, "eg_layernorm_bwd: null pointer");
   EG_CHECK(M > 0 && D > 0 && D % 4 == 0 && D <= 1024 && nblk > 0, "eg_layernorm_bwd: bad shape");
   // every workgroup writes its own [2, D] row of `partial`: a grid larger than the buffer is an out-of-bounds store (round 2: a
@@ -306,30 +290,16 @@ extern "C" int eg_layernorm_bwd(const void* dy, const void* x, const float* stat
   EG_CHECK((drop1_p == 0.f && drop2_p == 0.f) || state, "eg_layernorm_bwd: dropout needs a step state");
   EG_CHECK((long long)M * D < (1ll << 32), "eg_layernorm_bwd: M*D exceeds the 32-bit dropout index");
   DropCfg d1 = make_drop(drop1_p, drop1_site), d2 = make_drop(drop2_p, drop2_site);
-  if (D == 256 && (dtype == EG_BF16 || dtype == EG_F32 || dtype == EG_F16)) {
-    if (dtype == EG_BF16)
-      hipLaunchKernelGGL(layernorm_bwd256_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                         (const bf16_t*)x, stats, gamma, (bf16_t*)dx, (bf16_t*)dx_drop, partial, M, d1, d2, state);
-    else if (dtype == EG_F16)
-      hipLaunchKernelGGL(layernorm_bwd256_kernel<f16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const f16_t*)dy,
-                         (const f16_t*)x, stats, gamma, (f16_t*)dx, (f16_t*)dx_drop, partial, M, d1, d2, state);
+  hipStream_t s = (hipStream_t)stream;
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (D == 256)
+      hipLaunchKernelGGL(layernorm_bwd256_kernel<T>, dim3(nblk), dim3(256), 0, s, (const T*)dy, (const T*)x, stats, gamma, (T*)dx,
+                         (T*)dx_drop, partial, M, d1, d2, state);
     else
-      hipLaunchKernelGGL(layernorm_bwd256_kernel<float>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
-                         (const float*)x, stats, gamma, (float*)dx, (float*)dx_drop, partial, M, d1, d2, state);
-    EG_LAUNCH_CHECK("layernorm_bwd256");
-    return 0;
-  }
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(layernorm_bwd_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, stats, gamma, (bf16_t*)dx, (bf16_t*)dx_drop, partial, M, D, d1, d2, state);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(layernorm_bwd_kernel<f16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const f16_t*)dy,
-                       (const f16_t*)x, stats, gamma, (f16_t*)dx, (f16_t*)dx_drop, partial, M, D, d1, d2, state);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(layernorm_bwd_kernel<float>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
-                       (const float*)x, stats, gamma, (float*)dx, (float*)dx_drop, partial, M, D, d1, d2, state);
-  else
-    return eg_fail("eg_layernorm_bwd: bad dtype %d", dtype);
-  EG_LAUNCH_CHECK("layernorm_bwd");
+      hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nblk), dim3(256), 0, s, (const T*)dy, (const T*)x, stats, gamma, (T*)dx,
+                         (T*)dx_drop, partial, M, D, d1, d2, state);
+  });
+  EG_LAUNCH_CHECK(D == 256 ? "layernorm_bwd256" : "layernorm_bwd");
   return 0;
 }

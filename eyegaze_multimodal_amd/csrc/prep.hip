@@ -339,8 +339,8 @@ __global__ __launch_bounds__(256) void pack_table_ex_kernel(const eg_pack_entry_
 // rules, alignment, and -- wherever the caller states the extents of the buffers behind src / dst -- that no block reads or
 // writes past them.  The convolution modes must state both extents.
 extern "C" int eg_pack_table_ex_check(const eg_pack_entry_ex* table, int nentries, int dtype, int* total_blocks) {
+  if (eg_dtype_check("eg_pack_table_ex_check", dtype, true)) return 1;
   EG_CHECK(table && nentries > 0 && total_blocks, "eg_pack_table_ex_check: bad arguments");
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F16 || dtype == EG_F32, "eg_pack_table_ex_check: bad dtype %d", dtype);
   long long blk = 0;
   for (int i = 0; i < nentries; ++i) {
     const eg_pack_entry_ex& e = table[i];
@@ -406,129 +406,96 @@ extern "C" int eg_pack_table_ex_check(const eg_pack_entry_ex* table, int nentrie
 }
 
 extern "C" int eg_pack_table_ex(const eg_pack_entry_ex* table, int nentries, int total_blocks, int dtype, void* stream) {
+  if (eg_dtype_check("eg_pack_table_ex", dtype, true)) return 1;
   EG_CHECK(table && nentries > 0 && total_blocks > 0, "eg_pack_table_ex: bad arguments");
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(pack_table_ex_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(pack_table_ex_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(pack_table_ex_kernel<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else
-    return eg_fail("eg_pack_table_ex: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pack_table_ex_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
+  });
   EG_LAUNCH_CHECK("pack_table_ex");
   return 0;
 }
 
 extern "C" int eg_pack_table(const eg_pack_entry* table, int nentries, int total_blocks, int dtype, void* stream) {
+  if (eg_dtype_check("eg_pack_table", dtype, true)) return 1;
   EG_CHECK(table && nentries > 0 && total_blocks > 0, "eg_pack_table: bad arguments");
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(pack_table_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(pack_table_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(pack_table_kernel<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
-  else
-    return eg_fail("eg_pack_table: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pack_table_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, nentries);
+  });
   EG_LAUNCH_CHECK("pack_table");
   return 0;
 }
 
 extern "C" int eg_window_pack(const float* x, void* xt, int NB, int C, int T, int Cp, int pad_front, int Tp, int dtype,
                               void* stream) {
+  if (eg_dtype_check("eg_window_pack", dtype, true)) return 1;
   EG_CHECK(x && xt, "eg_window_pack: null pointer");
   EG_CHECK(NB > 0 && C > 0 && T > 0, "eg_window_pack: bad shape NB=%d C=%d T=%d", NB, C, T);
   EG_CHECK(Cp >= C && Cp % 8 == 0 && Cp <= 256, "eg_window_pack: Cp=%d must be a multiple of 8 in [C, 256]", Cp);
   EG_CHECK(pad_front >= 0 && Tp >= T + pad_front, "eg_window_pack: Tp=%d < T+pad_front", Tp);
   dim3 grid((Tp + 255) / 256, NB);
   const size_t lds = 256 * (Cp + 1) * sizeof(float);
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(window_pack_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, x, (bf16_t*)xt, C, T, Cp,
-                       pad_front, Tp);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(window_pack_kernel<f16_t>, grid, dim3(256), lds, (hipStream_t)stream, x, (f16_t*)xt, C, T, Cp,
-                       pad_front, Tp);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(window_pack_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, x, (float*)xt, C, T, Cp,
-                       pad_front, Tp);
-  else
-    return eg_fail("eg_window_pack: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;      // (T is the window length here)
+    hipLaunchKernelGGL(window_pack_kernel<E>, grid, dim3(256), lds, (hipStream_t)stream, x, (E*)xt, C, T, Cp, pad_front, Tp);
+  });
   EG_LAUNCH_CHECK("window_pack");
   return 0;
 }
 
 extern "C" int eg_cast(const float* src, void* dst, int64_t n, int dtype, void* stream) {
+  if (eg_dtype_check("eg_cast", dtype, true)) return 1;
   EG_CHECK(src && dst && n > 0, "eg_cast: bad arguments");
   EG_CHECK(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 8 == 0), "eg_cast: alignment");
   const long long nt = (n + 3) / 4;
   dim3 grid((unsigned)((nt + 255) / 256));
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(cast_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long long)n);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(cast_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (f16_t*)dst, (long long)n);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(cast_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, (long long)n);
-  else
-    return eg_fail("eg_cast: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(cast_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, (T*)dst, (long long)n);
+  });
   EG_LAUNCH_CHECK("cast");
   return 0;
 }
 
 extern "C" int eg_transpose_cast(const float* src, void* dst, int R, int Cc, int ldd, int dtype, void* stream) {
+  if (eg_dtype_check("eg_transpose_cast", dtype, true)) return 1;
   EG_CHECK(src && dst && R > 0 && Cc > 0 && ldd >= R, "eg_transpose_cast: bad arguments");
   dim3 grid((Cc + 31) / 32, (R + 31) / 32);
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(transpose_cast_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, R, Cc,
-                       ldd);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(transpose_cast_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (f16_t*)dst, R, Cc,
-                       ldd);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(transpose_cast_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, R, Cc,
-                       ldd);
-  else
-    return eg_fail("eg_transpose_cast: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(transpose_cast_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, (T*)dst, R, Cc, ldd);
+  });
   EG_LAUNCH_CHECK("transpose_cast");
   return 0;
 }
 
 extern "C" int eg_pack_conv_weight(const float* w, void* dst, int N, int Cin, int k, int Cp, int Kp, int dtype,
                                    void* stream) {
+  if (eg_dtype_check("eg_pack_conv_weight", dtype, true)) return 1;
   EG_CHECK(w && dst && N > 0 && Cin > 0 && k > 0, "eg_pack_conv_weight: bad arguments");
   EG_CHECK(Cp >= Cin && Kp >= k * Cp, "eg_pack_conv_weight: Cp=%d Kp=%d too small", Cp, Kp);
   const long long n = (long long)N * Kp;
   dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(pack_conv_weight_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)dst, N, Cin,
-                       k, Cp, Kp);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(pack_conv_weight_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, (f16_t*)dst, N, Cin,
-                       k, Cp, Kp);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(pack_conv_weight_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, w, (float*)dst, N, Cin, k,
-                       Cp, Kp);
-  else
-    return eg_fail("eg_pack_conv_weight: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pack_conv_weight_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, w, (T*)dst, N, Cin, k, Cp, Kp);
+  });
   EG_LAUNCH_CHECK("pack_conv_weight");
   return 0;
 }
 
 extern "C" int eg_pack_convT_weight(const float* w, void* dst, int N, int Cin, int k, int stride, int dtype,
                                     void* stream) {
+  if (eg_dtype_check("eg_pack_convT_weight", dtype, true)) return 1;
   EG_CHECK(w && dst && N > 0 && Cin > 0 && k > 0 && stride > 0, "eg_pack_convT_weight: bad arguments");
   const int J = (k + stride - 1) / stride;
   const long long n = (long long)stride * Cin * J * N;
   dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(pack_convT_weight_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)dst, N,
-                       Cin, k, stride, J);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(pack_convT_weight_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, w, (f16_t*)dst, N,
-                       Cin, k, stride, J);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(pack_convT_weight_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, w, (float*)dst, N, Cin,
-                       k, stride, J);
-  else
-    return eg_fail("eg_pack_convT_weight: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pack_convT_weight_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, w, (T*)dst, N, Cin, k, stride, J);
+  });
   EG_LAUNCH_CHECK("pack_convT_weight");
   return 0;
 }

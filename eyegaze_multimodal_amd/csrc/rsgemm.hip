@@ -334,5 +334,5 @@ int eg_rs_gemm_try(const eg_gemm_desc* d, hipStream_t s) {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
     cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  return d->dtype == EG_F16 ? rs_gemm_launch<f16_t>(d, s, cus) : rs_gemm_launch<bf16_t>(d, s, cus);
+  return eg_dispatch_16(d->dtype, [&](auto t) { return rs_gemm_launch<typename decltype(t)::type>(d, s, cus); });
 }

@@ -839,79 +839,62 @@ extern "C" int eg_stft_logmag(const float* x, const float* window, float* img, i
 
 extern "C" int eg_ibs_inorm(const float* conn, const int* fidx, const float* gamma, const float* beta, void* out,
                             float* xhat, int B, int nbands, int nfeat, int E, int use_norm, int dtype, void* stream) {
+  if (eg_dtype_check("eg_ibs_inorm", dtype, true)) return 1;
   EG_CHECK(conn && fidx && out && B > 0 && B < 65536 && nbands > 0 && nbands <= MAX_BANDS && nfeat > 0 && nfeat <= 7 && E > 0,
            "eg_ibs_inorm: bad arguments");
   EG_CHECK(!use_norm || (gamma && beta && xhat), "eg_ibs_inorm: instance norm needs gamma, beta and xhat");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(ibs_inorm_kernel<bf16_t>, dim3((E + 255) / 256, B), dim3(256), 0, s, conn, fidx, gamma, beta, (bf16_t*)out, xhat, B,
-                       nbands, nfeat, E, use_norm);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(ibs_inorm_kernel<f16_t>, dim3((E + 255) / 256, B), dim3(256), 0, s, conn, fidx, gamma, beta, (f16_t*)out, xhat, B,
-                       nbands, nfeat, E, use_norm);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(ibs_inorm_kernel<float>, dim3((E + 255) / 256, B), dim3(256), 0, s, conn, fidx, gamma, beta, (float*)out, xhat, B, nbands,
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ibs_inorm_kernel<T>, dim3((E + 255) / 256, B), dim3(256), 0, s, conn, fidx, gamma, beta, (T*)out, xhat, B, nbands,
                        nfeat, E, use_norm);
-  else
-    return eg_fail("eg_ibs_inorm: bad dtype %d", dtype);
+  });
   EG_LAUNCH_CHECK("ibs_inorm");
   return 0;
 }
 
 extern "C" int eg_gelu_fwd(const void* u, void* h, int64_t n, int dtype, float drop_p, uint32_t drop_site,
                            const eg_step_state* state, void* stream) {
+  if (eg_dtype_check("eg_gelu_fwd", dtype, true)) return 1;
   EG_CHECK(u && h && n > 0 && n < (1ll << 32), "eg_gelu_fwd: bad arguments");
   EG_CHECK(drop_p == 0.f || state, "eg_gelu_fwd: dropout needs a step state");
   DropCfg dc = make_drop(drop_p, drop_site);
   dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(gelu_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)u, (bf16_t*)h, (long long)n, dc, state);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(gelu_fwd_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)u, (f16_t*)h, (long long)n, dc, state);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(gelu_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)u, (float*)h, (long long)n, dc, state);
-  else
-    return eg_fail("eg_gelu_fwd: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(gelu_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)u, (T*)h, (long long)n, dc, state);
+  });
   EG_LAUNCH_CHECK("gelu_fwd");
   return 0;
 }
 
 extern "C" int eg_gelu_bwd(const void* u, const void* dh, void* du, int64_t n, int dtype, float drop_p, uint32_t drop_site,
                            const eg_step_state* state, void* stream) {
+  if (eg_dtype_check("eg_gelu_bwd", dtype, true)) return 1;
   EG_CHECK(u && dh && du && n > 0 && n < (1ll << 32), "eg_gelu_bwd: bad arguments");
   EG_CHECK(drop_p == 0.f || state, "eg_gelu_bwd: dropout needs a step state");
   DropCfg dc = make_drop(drop_p, drop_site);
   dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)u, (const bf16_t*)dh, (bf16_t*)du,
-                       (long long)n, dc, state);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(gelu_bwd_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)u, (const f16_t*)dh, (f16_t*)du,
-                       (long long)n, dc, state);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(gelu_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)u, (const float*)dh, (float*)du,
-                       (long long)n, dc, state);
-  else
-    return eg_fail("eg_gelu_bwd: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(gelu_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)u, (const T*)dh, (T*)du, (long long)n, dc, state);
+  });
   EG_LAUNCH_CHECK("gelu_bwd");
   return 0;
 }
 
 extern "C" int eg_affine_grad(const void* dy, const float* xhat, float* partial, int nsplit, int M, int E, int dtype,
                               void* stream) {
+  if (eg_dtype_check("eg_affine_grad", dtype, true)) return 1;
   EG_CHECK(dy && xhat && partial && M > 0 && E > 0 && nsplit > 0 && nsplit <= 65535, "eg_affine_grad: bad arguments");
   dim3 grid((E + 63) / 64, nsplit);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(affine_grad_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dy, xhat, partial, M, E, nsplit);
-  else if (dtype == EG_F16)
-    hipLaunchKernelGGL(affine_grad_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)dy, xhat, partial, M, E, nsplit);
-  else if (dtype == EG_F32)
-    hipLaunchKernelGGL(affine_grad_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, xhat, partial, M, E, nsplit);
-  else
-    return eg_fail("eg_affine_grad: bad dtype %d", dtype);
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(affine_grad_kernel<T>, grid, dim3(256), 0, s, (const T*)dy, xhat, partial, M, E, nsplit);
+  });
   EG_LAUNCH_CHECK("affine_grad");
   return 0;
 }

@@ -501,12 +501,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_flat_kernel(const T* __restrict
 
 }  // namespace
 
-#define SPEC_DISPATCH(dtype, BF, F16, F32, who)   \
-  if ((dtype) == EG_BF16) { BF; }                  \
-  else if ((dtype) == EG_F16) { F16; }             \
-  else if ((dtype) == EG_F32) { F32; }             \
-  else return eg_fail("%s: bad dtype %d", who, (int)(dtype));
-
 static int spec_shape_ok(const char* who, int nimg, int F, int nfr) {
   EG_CHECK(nimg > 0 && F >= 8 && F % 8 == 0 && nfr >= 8 && (nfr / 2) % 4 == 0,
            "%s: image %dx%d unsupported (F %% 8 == 0 and floor(frames/2) %% 4 == 0 required)", who, F, nfr);
@@ -515,69 +509,69 @@ static int spec_shape_ok(const char* who, int nimg, int F, int nfr) {
 
 extern "C" int eg_spec_conv1_fwd(const float* img, const float* w, const float* bias, void* p1, int nimg, int F, int nfr,
                                  int dtype, void* stream) {
+  if (eg_dtype_check("eg_spec_conv1_fwd", dtype, true)) return 1;
   EG_CHECK(img && w && bias && p1, "eg_spec_conv1_fwd: null pointer");
   if (spec_shape_ok("eg_spec_conv1_fwd", nimg, F, nfr)) return 1;
   const int lds = ((F + 2) * (nfr + 2) + C1 * 10) * 4;
   hipStream_t s = (hipStream_t)stream;
-  SPEC_DISPATCH(dtype,
-                hipLaunchKernelGGL(spec_conv1_fwd_kernel<bf16_t>, dim3(nimg), dim3(256), lds, s, img, w, bias, (bf16_t*)p1, F, nfr),
-                hipLaunchKernelGGL(spec_conv1_fwd_kernel<f16_t>, dim3(nimg), dim3(256), lds, s, img, w, bias, (f16_t*)p1, F, nfr),
-                hipLaunchKernelGGL(spec_conv1_fwd_kernel<float>, dim3(nimg), dim3(256), lds, s, img, w, bias, (float*)p1, F, nfr),
-                "eg_spec_conv1_fwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_conv1_fwd_kernel<T>, dim3(nimg), dim3(256), lds, s, img, w, bias, (T*)p1, F, nfr);
+  });
   EG_LAUNCH_CHECK("spec_conv1_fwd");
   return 0;
 }
 
 extern "C" int eg_spec_conv1_bwd(const float* img, const float* w, const float* bias, const void* dp1, float* partial,
                                  int nimg, int F, int nfr, int dtype, void* stream) {
+  if (eg_dtype_check("eg_spec_conv1_bwd", dtype, true)) return 1;
   EG_CHECK(img && w && bias && dp1 && partial, "eg_spec_conv1_bwd: null pointer");
   if (spec_shape_ok("eg_spec_conv1_bwd", nimg, F, nfr)) return 1;
   const int lds = ((F + 2) * (nfr + 2) + C1 * 10 + 8 * C1 * 10) * 4;
   hipStream_t s = (hipStream_t)stream;
-  SPEC_DISPATCH(dtype,
-                hipLaunchKernelGGL(spec_conv1_bwd_kernel<bf16_t>, dim3(nimg), dim3(256), lds, s, img, w, bias, (const bf16_t*)dp1, partial, F, nfr),
-                hipLaunchKernelGGL(spec_conv1_bwd_kernel<f16_t>, dim3(nimg), dim3(256), lds, s, img, w, bias, (const f16_t*)dp1, partial, F, nfr),
-                hipLaunchKernelGGL(spec_conv1_bwd_kernel<float>, dim3(nimg), dim3(256), lds, s, img, w, bias, (const float*)dp1, partial, F, nfr),
-                "eg_spec_conv1_bwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_conv1_bwd_kernel<T>, dim3(nimg), dim3(256), lds, s, img, w, bias, (const T*)dp1, partial, F, nfr);
+  });
   EG_LAUNCH_CHECK("spec_conv1_bwd");
   return 0;
 }
 
 extern "C" int eg_spec_avgpool_fwd(const void* out2, void* pooled, int nimg, int Hp, int Wp, int dtype, void* stream) {
+  if (eg_dtype_check("eg_spec_avgpool_fwd", dtype, true)) return 1;
   EG_CHECK(out2 && pooled && nimg > 0 && Hp % 4 == 0 && Wp % 4 == 0, "eg_spec_avgpool_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  SPEC_DISPATCH(dtype,
-                hipLaunchKernelGGL(spec_avgpool_fwd_kernel<bf16_t>, dim3(nimg), dim3(128), 0, s, (const bf16_t*)out2, (bf16_t*)pooled, Hp, Wp),
-                hipLaunchKernelGGL(spec_avgpool_fwd_kernel<f16_t>, dim3(nimg), dim3(128), 0, s, (const f16_t*)out2, (f16_t*)pooled, Hp, Wp),
-                hipLaunchKernelGGL(spec_avgpool_fwd_kernel<float>, dim3(nimg), dim3(128), 0, s, (const float*)out2, (float*)pooled, Hp, Wp),
-                "eg_spec_avgpool_fwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_avgpool_fwd_kernel<T>, dim3(nimg), dim3(128), 0, s, (const T*)out2, (T*)pooled, Hp, Wp);
+  });
   EG_LAUNCH_CHECK("spec_avgpool_fwd");
   return 0;
 }
 
 extern "C" int eg_spec_avgpool_bwd(const void* out2, const void* dpooled, void* d2, int nimg, int Hp, int Wp, int dtype,
                                    void* stream) {
+  if (eg_dtype_check("eg_spec_avgpool_bwd", dtype, true)) return 1;
   EG_CHECK(out2 && dpooled && d2 && nimg > 0 && Hp % 4 == 0 && Wp % 4 == 0, "eg_spec_avgpool_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  SPEC_DISPATCH(dtype,
-                hipLaunchKernelGGL(spec_avgpool_bwd_kernel<bf16_t>, dim3(nimg), dim3(256), 0, s, (const bf16_t*)out2, (const bf16_t*)dpooled, (bf16_t*)d2, Hp, Wp),
-                hipLaunchKernelGGL(spec_avgpool_bwd_kernel<f16_t>, dim3(nimg), dim3(256), 0, s, (const f16_t*)out2, (const f16_t*)dpooled, (f16_t*)d2, Hp, Wp),
-                hipLaunchKernelGGL(spec_avgpool_bwd_kernel<float>, dim3(nimg), dim3(256), 0, s, (const float*)out2, (const float*)dpooled, (float*)d2, Hp, Wp),
-                "eg_spec_avgpool_bwd");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_avgpool_bwd_kernel<T>, dim3(nimg), dim3(256), 0, s, (const T*)out2, (const T*)dpooled, (T*)d2, Hp, Wp);
+  });
   EG_LAUNCH_CHECK("spec_avgpool_bwd");
   return 0;
 }
 
 extern "C" int eg_pack_conv2d_weight(const float* w, void* dst, int N, int Cin, int transposed, int dtype, void* stream) {
+  if (eg_dtype_check("eg_pack_conv2d_weight", dtype, true)) return 1;
   EG_CHECK(w && dst && N > 0 && Cin > 0, "eg_pack_conv2d_weight: bad arguments");
   const long long n = (long long)N * Cin * 12;
   dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  SPEC_DISPATCH(dtype,
-                hipLaunchKernelGGL(pack_conv2d_weight_kernel<bf16_t>, grid, dim3(256), 0, s, w, (bf16_t*)dst, N, Cin, transposed),
-                hipLaunchKernelGGL(pack_conv2d_weight_kernel<f16_t>, grid, dim3(256), 0, s, w, (f16_t*)dst, N, Cin, transposed),
-                hipLaunchKernelGGL(pack_conv2d_weight_kernel<float>, grid, dim3(256), 0, s, w, (float*)dst, N, Cin, transposed),
-                "eg_pack_conv2d_weight");
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pack_conv2d_weight_kernel<T>, grid, dim3(256), 0, s, w, (T*)dst, N, Cin, transposed);
+  });
   EG_LAUNCH_CHECK("pack_conv2d_weight");
   return 0;
 }
@@ -601,27 +595,20 @@ extern "C" int eg_unpack_conv2d_wgrad(float* partial, float* dW, int splits, int
 
 extern "C" int eg_conv2d_wgrad_flat(const void* d2, const void* p1, float* partial, float* bias_partial, long long Q, long long p1_rows,
                                     int rowpx, int splits, int dtype, void* stream) {
+  if (eg_dtype_check("eg_conv2d_wgrad_flat", dtype, false)) return 1;     // (fp32 goes through eg_gemm_tn)
   EG_CHECK(d2 && p1 && partial && Q > 0 && rowpx >= 4 && 2 * rowpx + 2 <= CW_HALO && splits > 0, "eg_conv2d_wgrad_flat: bad arguments");
   EG_CHECK(p1_rows >= Q + 2 * rowpx + 2, "eg_conv2d_wgrad_flat: p1 holds %lld pixel rows, the windows of %lld pixels reach %lld", p1_rows, Q,
            Q + 2 * rowpx + 2);
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F16, "eg_conv2d_wgrad_flat: 16-bit operands only (dtype %d); fp32 goes through eg_gemm_tn", dtype);
   // rows per split: a multiple of the 256-row stage; every split must own at least one row
   long long rps = ((Q + splits - 1) / splits + CW_QC - 1) / CW_QC * CW_QC;
   EG_CHECK((long long)(splits - 1) * rps < Q, "eg_conv2d_wgrad_flat: %d splits of %lld rows overrun Q = %lld (use eg_conv2d_wgrad_flat_splits)",
            splits, rps, Q);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv2d_wgrad_flat_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_YB + CW_XB);
-    (void)hipFuncSetAttribute((const void*)conv2d_wgrad_flat_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, CW_YB + CW_XB);
-    attr = true;
-  }
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == EG_BF16)
-    hipLaunchKernelGGL(conv2d_wgrad_flat_kernel<bf16_t>, dim3(splits), dim3(256), CW_YB + CW_XB, s, (const bf16_t*)d2, (const bf16_t*)p1,
-                       partial, bias_partial, Q, p1_rows, rowpx, rps);
-  else
-    hipLaunchKernelGGL(conv2d_wgrad_flat_kernel<f16_t>, dim3(splits), dim3(256), CW_YB + CW_XB, s, (const f16_t*)d2, (const f16_t*)p1,
-                       partial, bias_partial, Q, p1_rows, rowpx, rps);
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    eg_launch_lds<conv2d_wgrad_flat_kernel<T>, CW_YB + CW_XB>(dim3(splits), dim3(256), s, (const T*)d2, (const T*)p1, partial, bias_partial, Q,
+                                                              p1_rows, rowpx, rps);
+  });
   EG_LAUNCH_CHECK("conv2d_wgrad_flat");
   return 0;
 }
@@ -640,9 +627,9 @@ extern "C" int eg_conv2d_wgrad_flat_splits(long long Q, int want) {
 
 extern "C" int eg_conv2d_flat(const void* in, const void* W, const float* bias, void* out, long long Q, long long in_rows, int rowpx,
                               int Wp, int cin, int nout, int act, int splits, int dtype, void* stream) {
+  if (eg_dtype_check("eg_conv2d_flat", dtype, false)) return 1;           // (fp32 goes through eg_gemm_nt)
   EG_CHECK(in && W && out && Q > 0 && Q < (1ll << 31) - 4096 && in_rows < (1ll << 31) && rowpx >= 4 && 2 * rowpx + 2 <= CW_HALO &&
            Wp > 0 && Wp <= rowpx && splits > 0, "eg_conv2d_flat: bad arguments");
-  EG_CHECK(dtype == EG_BF16 || dtype == EG_F16, "eg_conv2d_flat: 16-bit operands only (dtype %d); fp32 goes through eg_gemm_nt", dtype);
   EG_CHECK((cin == 32 && nout == 64) || (cin == 64 && nout == 32), "eg_conv2d_flat: %d -> %d channels (32 -> 64 or 64 -> 32)", cin, nout);
   EG_CHECK(act == EG_ACT_NONE || act == EG_ACT_RELU, "eg_conv2d_flat: act %d (none or ReLU)", act);
   EG_CHECK(in_rows >= Q + 2 * rowpx + 2, "eg_conv2d_flat: the input holds %lld pixel rows, the windows of %lld pixels reach %lld", in_rows, Q,
@@ -652,15 +639,20 @@ extern "C" int eg_conv2d_flat(const void* in, const void* W, const float* bias, 
   const int nblk = (int)((Q + rps - 1) / rps);
   const int lds = (qc + CW_HALO) * (cin == 32 ? CfImg<32>::PITCH : CfImg<64>::PITCH);
   hipStream_t s = (hipStream_t)stream;
-#define EG_CF_LAUNCH(T, A, CI, NO) \
-  hipLaunchKernelGGL((conv2d_flat_kernel<T, A, CI, NO>), dim3(nblk), dim3(256), lds, s, (const T*)in, (const T*)W, bias, (T*)out, (int)Q, \
-                     (int)in_rows, rowpx, Wp, (int)rps)
-#define EG_CF_SHAPE(T) \
-  if (cin == 32) { if (act == EG_ACT_RELU) EG_CF_LAUNCH(T, EG_ACT_RELU, 32, 64); else EG_CF_LAUNCH(T, EG_ACT_NONE, 32, 64); } \
-  else           { if (act == EG_ACT_RELU) EG_CF_LAUNCH(T, EG_ACT_RELU, 64, 32); else EG_CF_LAUNCH(T, EG_ACT_NONE, 64, 32); }
-  if (dtype == EG_BF16) { EG_CF_SHAPE(bf16_t) } else { EG_CF_SHAPE(f16_t) }
-#undef EG_CF_SHAPE
-#undef EG_CF_LAUNCH
+  eg_dispatch_16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto launch = [&](auto a, auto ci, auto no) {
+      hipLaunchKernelGGL((conv2d_flat_kernel<T, decltype(a)::value, decltype(ci)::value, decltype(no)::value>), dim3(nblk), dim3(256), lds, s,
+                         (const T*)in, (const T*)W, bias, (T*)out, (int)Q, (int)in_rows, rowpx, Wp, (int)rps);
+    };
+    if (cin == 32) {
+      if (act == EG_ACT_RELU) launch(eg_int<EG_ACT_RELU>{}, eg_int<32>{}, eg_int<64>{});
+      else launch(eg_int<EG_ACT_NONE>{}, eg_int<32>{}, eg_int<64>{});
+    } else {
+      if (act == EG_ACT_RELU) launch(eg_int<EG_ACT_RELU>{}, eg_int<64>{}, eg_int<32>{});
+      else launch(eg_int<EG_ACT_NONE>{}, eg_int<64>{}, eg_int<32>{});
+    }
+  });
   EG_LAUNCH_CHECK("conv2d_flat");
   return 0;
 }

@@ -287,8 +287,10 @@ bool eg_wide_gemm_ok(const eg_gemm_desc* d) {
 int eg_wide_gemm_try(const eg_gemm_desc* d, hipStream_t s) {
   if (!eg_wide_gemm_ok(d)) return -1;
   const int rows = g_force_rows ? g_force_rows : eg_gemm_wide_rows(d->M, device_cus());
-  if (rows == 128) return d->dtype == EG_F16 ? wide_launch<f16_t, 128>(d, s) : wide_launch<bf16_t, 128>(d, s);
-  return d->dtype == EG_F16 ? wide_launch<f16_t, 160>(d, s) : wide_launch<bf16_t, 160>(d, s);
+  return eg_dispatch_16(d->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return rows == 128 ? wide_launch<T, 128>(d, s) : wide_launch<T, 160>(d, s);
+  });
 }
 
 // the epilogue steps a product takes (one bit each) and its activation; the products of a batch must agree on them
@@ -317,8 +319,10 @@ int eg_wide_gemm_batch_try(const eg_gemm_desc* descs, int n, hipStream_t s) {
   for (int i = 0; i < n; ++i) { t160 += (d[i]->M + 159) / 160; t128 += (d[i]->M + 127) / 128; }
   const int rows = g_force_rows ? g_force_rows : wide_pick_rows(t160, t128, device_cus());
   if ((rows == 128 ? t128 : t160) > 0x7fffffffll) return -1;     // the tiles must fit one grid
-  if (rows == 128) return d[0]->dtype == EG_F16 ? wide_launch_batch<f16_t, 128>(d, n, s) : wide_launch_batch<bf16_t, 128>(d, n, s);
-  return d[0]->dtype == EG_F16 ? wide_launch_batch<f16_t, 160>(d, n, s) : wide_launch_batch<bf16_t, 160>(d, n, s);
+  return eg_dispatch_16(d[0]->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return rows == 128 ? wide_launch_batch<T, 128>(d, n, s) : wide_launch_batch<T, 160>(d, n, s);
+  });
 }
 
 extern "C" int eg_gemm_wide_rows(int M, int cus) {
