@@ -145,6 +145,9 @@ SIGNATURES = {
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
     "eg_attention_long_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P, _L, _P],
     "eg_attention_long_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "eg_attention_dk_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _U, _P, _P],
+    "eg_attention_dk_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _U, _P, _P, _L, _P],
+    "eg_attention_dk_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "eg_rows_bcast_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_rows_copy": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_pool_fuse_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

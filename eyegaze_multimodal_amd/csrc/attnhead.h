@@ -1,5 +1,6 @@
 // The pieces of the attention family (attention.hip, attention_long.hip, attnblock.hip), each written once: the LDS image of a head
-// slice, its MFMA operand reads, and the argument check of the two stand-alone cores.  d_k = 32 everywhere.
+// slice, its MFMA operand reads, and the argument check of the two stand-alone cores.  d_k = 32 everywhere but in attention_long.hip,
+// whose kernels also come 64 wide: a 64-wide head slice is TWO of the images below, [half][rows][32], and every piece here serves a half.
 //   * head image: [rows][32] 16-bit elements = 64-B rows of four 16-B chunks.  The two 32-B halves of a row are SWAPPED when
 //     (row >> 2) & 1: a transposed read touches 8 consecutive rows per lane group at one 32-B half, and with the swap those land in 8
 //     distinct 32-B slots of the 256-B bank row instead of 4 slots twice;
@@ -19,6 +20,7 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 template <typename T> using FR = typename H16<T>::frag;
 
 constexpr float HD_SCALE = 0.17677669529663687f;  // 1/sqrt(32)
+template <int DK> constexpr float hd_scale() { return DK == 32 ? HD_SCALE : 0.125f; }   // 1/sqrt(DK), DK = 32 or 64
 constexpr int HD_MAX_S = 160;                     // eg_attention_*: a whole window's scores in one wave's registers (SP = 96 / 128 / 160)
 
 template <typename T>
@@ -59,12 +61,14 @@ __device__ __forceinline__ FR<T> hd_pack_frag(const f32x4& a, const f32x4& b) {
   return __builtin_bit_cast(FR<T>, v);
 }
 // the fp32 parity kernels' dot product: one fmaf chain in ascending d
-__device__ __forceinline__ float hd_dot32(const float* a, const float* b) {
+template <int DK>
+__device__ __forceinline__ float hd_dot(const float* a, const float* b) {
   float s = 0.f;
 #pragma unroll
-  for (int d = 0; d < 32; ++d) s = fmaf(a[d], b[d], s);
+  for (int d = 0; d < DK; ++d) s = fmaf(a[d], b[d], s);
   return s;
 }
+__device__ __forceinline__ float hd_dot32(const float* a, const float* b) { return hd_dot<32>(a, b); }
 
 // host: the argument check of eg_attention_* (max_s = HD_MAX_S, idx32: element indices of the dropout hash are 32 bit) and of
 // eg_attention_long_* (max_s = EG_ATTN_LONG_MAX_S, 64-bit indices).  The dtype comes first, so the entry points call it before

@@ -71,6 +71,17 @@ def sequence_length(cfg, T: int) -> int:
     return S
 
 
+ATTN_HEAD_DIMS = (32, 64)   # head widths the attention kernels are built for (csrc/attention_long.hip; the short core and the block: 32)
+
+
+def attention_head_dim(cfg) -> int:
+    """Head width d_model / num_heads of a model config, 32 or 64; needs no device.  Raises EgError naming both otherwise."""
+    d, H = cfg.d_model, cfg.num_heads
+    if H <= 0 or d % H != 0 or d // H not in ATTN_HEAD_DIMS:
+        raise L.EgError(f"HIP attention core needs d_model/num_heads == 32 or 64 (got {d}/{H})")
+    return d // H
+
+
 class FlatParams:
     """All parameters of a module as views of one flat fp32 buffer (+ a flat gradient buffer).
     Segment offsets are multiples of 4 floats so every kernel can use 16-B accesses."""
@@ -476,9 +487,8 @@ class Engine(EngineBase):
         super().__init__(model, B, device, dtype)
         cfg = model.cfg
         self.cfg, self.T = cfg, T
-        d, H = cfg.d_model, cfg.num_heads
-        if d % H != 0 or d // H != 32:
-            raise L.EgError(f"HIP attention core needs d_model/num_heads == 32 (got {d}/{H})")
+        d = cfg.d_model
+        self.head_dim = attention_head_dim(cfg)
         if cfg.conv_layers != 2:
             raise L.EgError("HIP path implements the reference's 2-layer temporal conv front-end (conv_layers=2)")
         if d % 64 != 0 or cfg.d_ff % 64 != 0:
@@ -517,7 +527,11 @@ class Engine(EngineBase):
         half = dtype != EG_F32
         self.scaler_on = dtype == EG_F16 and env.get("EYEGAZE_LOSS_SCALING", "1") != "0"
         # S > 160: the long-sequence attention core (eg_attention_long_*) at all four call sites; S <= 160 keeps the short one
-        self.attn_long = self.S > ATTN_SHORT_MAX_S
+        # 64-wide heads: the same core through eg_attention_dk_* at EVERY S (the short core and the fused block are 32 wide only)
+        wide = self.head_dim != 32
+        self.attn_long = self.S > ATTN_SHORT_MAX_S or wide
+        self._attn_core = "eg_attention_dk" if wide else "eg_attention_long" if self.attn_long else "eg_attention"
+        self._attn_heads = (cfg.num_heads, self.head_dim) if wide else (cfg.num_heads,)    # H [, head_dim] of the core's arguments
         # attention half of an encoder layer (q|k|v projection, attention core, out-proj + dropout + residual) as ONE launch with a
         # workgroup per window (csrc/attnblock.hip): 16-bit compute dtypes, d_model == 256, 8 heads, S <= 80
         self.attn_block = bool(env.get("EYEGAZE_ATTN_BLOCK", "1") != "0" and half
@@ -717,10 +731,10 @@ class Engine(EngineBase):
     def attn_unfused_fwd(self, x, l, kv_shift, sites, p):
         """Stage l's forward as three launches: q|k|v = x W^T + b (A:203-205) fused over the three projections (the row-stream
         GEMM at K = 256), the attention core, out-proj + dropout + residual.  kv_shift = B pairs window b with b + B (D:966-974)."""
-        M, d, H = self.M, self.cfg.d_model, self.cfg.num_heads
+        M, d = self.M, self.cfg.d_model
         pre, qkv, lse, ctx, r = self._attn_stage(l)
         self.gemm(ptr(x), ptr(self.w[f"qkv{l}"]), ptr(qkv), M, 3 * d, d, bias=ptr(self.w[f"bqkv{l}"]))
-        call("eg_attention_long_fwd" if self.attn_long else "eg_attention_fwd", ptr(qkv), ptr(ctx), ptr(lse), self.NB, self.S, H,
+        call(self._attn_core + "_fwd", ptr(qkv), ptr(ctx), ptr(lse), self.NB, self.S, *self._attn_heads,
              kv_shift, self.dtype, p, sites["attn"], self.st_ptr, self.stream)
         self._probs_hook(self.model.get_submodule(pre + "dropout"), qkv, lse, kv_shift)
         self.gemm(ptr(ctx), ptr(self.w[f"o{l}"]), ptr(r), M, d, d, bias=self.fp.p_ptr(pre + "out_proj.bias"),
@@ -789,8 +803,7 @@ class Engine(EngineBase):
             return
         NB, B, S, H = self.NB, self.B, self.S, self.cfg.num_heads
         probs = torch.empty(NB, H, S, S, device=self.device, dtype=torch.float32)
-        call("eg_attention_long_probs" if self.attn_long else "eg_attention_probs", ptr(qkv), ptr(lse), ptr(probs), NB, S, H,
-             kv_shift, self.dtype, self.stream)
+        call(self._attn_core + "_probs", ptr(qkv), ptr(lse), ptr(probs), NB, S, *self._attn_heads, kv_shift, self.dtype, self.stream)
         was = drop_module.training
         drop_module.training = False      # the module call is only the hook carrier: identity, no torch RNG use
         try:
@@ -1131,8 +1144,8 @@ class Engine(EngineBase):
             if not dctx_done:       # (eg_ln_bwd_proj has written dctx together with dr / drm)
                 self.gemm(ptr(drm), ptr(w[f"oT{l}"]), ptr(g["dctx"]), M, d, d)
             delta = (ptr(g["attn_delta"]), g["attn_delta"].numel()) if self.attn_long else ()    # (the long core's scratch)
-            call("eg_attention_long_bwd" if self.attn_long else "eg_attention_bwd", ptr(qkv), ptr(ctx), ptr(g["dctx"]), ptr(lse),
-                 ptr(dqkv), NB, S, H, kv_shift, self.dtype, p, site_attn, self.st_ptr, *delta, st)
+            call(self._attn_core + "_bwd", ptr(qkv), ptr(ctx), ptr(g["dctx"]), ptr(lse),
+                 ptr(dqkv), NB, S, *self._attn_heads, kv_shift, self.dtype, p, site_attn, self.st_ptr, *delta, st)
             if not defer:
                 self.wgrad(ptr(dqkv), ptr(x_in), 0, M, 3 * d, d, linear=names)
             self.gemm(ptr(dqkv), ptr(w[f"qkvT{l}"]), ptr(dx_out), M, d, 3 * d, residual=ptr(dr))

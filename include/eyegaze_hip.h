@@ -385,6 +385,20 @@ int eg_attention_long_probs(const void* qkv, const float* lse, float* probs, int
                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The long-sequence core with the head width as an argument: head_dim = d_model / num_heads is 32 or 64, anything else is
+ * refused.  qkv [NB*S, 3*H*head_dim], ctx [NB*S, H*head_dim], lse [NB, H, S], scores scaled by 1/sqrt(head_dim); S, kv_shift,
+ * scratch (NB*H*S floats), dropout indices and determinism as eg_attention_long_*.  head_dim = 32 launches exactly what
+ * eg_attention_long_* launch; head_dim = 64 serves every S from 1 up (there is no 64-wide register-resident core).
+ * ------------------------------------------------------------------------------------------- */
+int eg_attention_dk_fwd(const void* qkv, void* ctx, float* lse, int NB, int S, int H, int head_dim, int kv_shift, int dtype,
+                        float drop_p, uint32_t drop_site, const eg_step_state* state, void* stream);
+int eg_attention_dk_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int NB, int S, int H,
+                        int head_dim, int kv_shift, int dtype, float drop_p, uint32_t drop_site, const eg_step_state* state,
+                        float* scratch, int64_t scratch_elems, void* stream);
+int eg_attention_dk_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int head_dim, int kv_shift,
+                          int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sequence assembly and heads (all [B, d]-sized, latency-bound single launches)
  *   eg_rows_bcast_f32  seq[b, off+r, :] = src[b % src_nb, r, :] + pos[off+r, :]   (cls_token expand + pos, D:1157,1178)
  *   eg_rows_copy       seq[b_dst0+b, off+r, :] = seq[b_src0+b, off+r, :]          (shared IBS tokens, D:1163-1165)
