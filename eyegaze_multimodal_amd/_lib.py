@@ -161,6 +161,7 @@ SIGNATURES = {
     "eg_heads_bwd_chain": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "eg_heads_bwd_pool": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_token_grad_tail": [_P, _P, _P, RowMap, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "eg_eval_accumulate": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "eg_grad_sqnorm": [_P, _L, _P, _I, _P],
     "eg_grad_accumulate": [_P, _P, _L, _I, _P, _I, _P],
     "eg_clip_coef": [_P, _I, _F, _P, _P],

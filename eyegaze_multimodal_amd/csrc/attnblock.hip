@@ -57,7 +57,10 @@ struct ABArgs {
 // sees one straight-line body per query tile); TAIL: the last key tile holds ONE valid key (S = 16 n + 1) and evaluates one
 // accumulator register per lane.  <0, false> is the general form.  LNF: the layer's first LayerNorm (A:293) runs in the final
 // epilogue on the rows the workgroup has just completed (eg_epilogue_layernorm256) instead of as a launch that re-reads r1.
-template <typename T, int NKTX, bool TAIL, bool LNF>
+// KEEP = false is the LEAN form of a forward that nobody differentiates (LNF only): the same images, MFMA chains, rounding points and
+// dropout code, but q|k|v, lse, ctx, r1 and the LayerNorm statistics are never stored -- LN_OUT is the launch's only global store
+// (34 MB instead of 108 MB per launch at the benchmark size), bit-identical to the keeping form's.
+template <typename T, int NKTX, bool TAIL, bool LNF, bool KEEP = true>
 __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
   typedef typename H16<T>::frag frag;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -137,6 +140,8 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
         for (int j = 0; j < 3; ++j) acc1[i][j] = H16<T>::mfma(w1r[s % 3][j], xf[i], acc1[i][j]);
       if (s < 5) req_w1(c, s + 3, s % 3);       // ring three k-steps ahead (the next chunk's first fragments are requested after
     }                                             // the attention phase: held across it they pushed the kernel into scratch)
+    // (lean form: without this the bias loads below are hoisted into the MFMA loop and the general form needs all 256 registers)
+    if constexpr (!KEEP) __builtin_amdgcn_sched_barrier(0);
     float b1[3][4];
     int ioff[3];                                             // byte offset of tile j's images
 #pragma unroll
@@ -166,11 +171,15 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
 
     // the stored k and v rows: per row and part 128 contiguous bytes (heads 2c, 2c+1), 16 B per thread.  (The q rows are
     // stored below by the wave that is about to overwrite them with ctx: no barrier needed between this loop and that write.)
-    for (int idx = tid; idx < S * 16; idx += 256) {
-      const int row = idx >> 4, pc = idx & 15;
-      const int part = 1 + (pc >> 3), th = (pc >> 2) & 1, c4 = pc & 3;
-      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + part * A_QK + hd_img_off(row, c4));
-      *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + part * AD + (2 * c + th) * 32 + c4 * 8) = o;
+    if constexpr (KEEP) {
+      for (int idx = tid; idx < S * 16; idx += 256) {
+        const int row = idx >> 4, pc = idx & 15;
+        const int part = 1 + (pc >> 3), th = (pc >> 2) & 1, c4 = pc & 3;
+        const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + part * A_QK + hd_img_off(row, c4));
+        *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + part * AD + (2 * c + th) * 32 + c4 * 8) = o;
+      }
+    } else {
+      __builtin_amdgcn_sched_barrier(0);     // the scheduling region still ends where the store loop ended it (registers, see infer_isa.txt)
     }
 
     // ================= P2: attention of head 2c + hh, query tiles role, role + 2, .. =================
@@ -183,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
       for (int qt = role; qt < nkt; qt += 2) {
         const int q = qt * 16 + l15;
         const frag qf = hd_frag_row<T>(qimg, q, g4);
-        {                                                    // this tile's q rows leave the chip before ctx replaces them
+        if constexpr (KEEP) {                                // this tile's q rows leave the chip before ctx replaces them
           const int row = qt * 16 + (lane >> 2), c4 = lane & 3;
           if (row < S) *(u32x4*)(p.QKV + (row0 + row) * (3 * AD) + h * 32 + c4 * 8) = *(const u32x4*)(qimg + hd_img_off(row, c4));
         }
@@ -232,7 +241,9 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
-        if (g4 == 0 && q < S) p.LSE[((size_t)b * AH + h) * S + q] = mx + __logf(sum);
+        if constexpr (KEEP) {
+          if (g4 == 0 && q < S) p.LSE[((size_t)b * AH + h) * S + q] = mx + __logf(sum);
+        }
         const uint32_t rowidx = (uint32_t)((b * AH + h) * S + q) * (uint32_t)((S + 1) & ~1);
 #pragma unroll
         for (int kt = 0; kt < 5; ++kt) {
@@ -279,10 +290,14 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
     __syncthreads();        // (C) ctx of both heads is complete (in the q images)
 
     // the stored ctx rows: 128 contiguous bytes per row (heads 2c, 2c+1)
-    for (int idx = tid; idx < S * 8; idx += 256) {
-      const int row = idx >> 3, th = (idx >> 2) & 1, c4 = idx & 3;
-      const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + hd_img_off(row, c4));
-      *(u32x4*)(p.CTX + (row0 + row) * AD + (2 * c + th) * 32 + c4 * 8) = o;
+    if constexpr (KEEP) {
+      for (int idx = tid; idx < S * 8; idx += 256) {
+        const int row = idx >> 3, th = (idx >> 2) & 1, c4 = idx & 3;
+        const u32x4 o = *(const u32x4*)(imgs + th * A_IMGH + hd_img_off(row, c4));
+        *(u32x4*)(p.CTX + (row0 + row) * AD + (2 * c + th) * 32 + c4 * 8) = o;
+      }
+    } else {
+      __builtin_amdgcn_sched_barrier(0);
     }
 
     // ================= P3: out-proj partial sums over the chunk's 64 ctx columns =================
@@ -324,12 +339,13 @@ __global__ __launch_bounds__(256, 2) void attn_block_fwd_kernel(ABArgs<T> p) {
       const size_t m = row0 + r;
       u32x4 e0, e1;
       rt_tile_row16(xt, r, n, e0, e1);
-      rt_row_epilogue<T, LNF>(v, bv, p.d1, DropCfg{0u, 1.f, 0u}, seed_lo, seed_hi, (uint32_t)m * (uint32_t)AD + (uint32_t)n, true, e0, e1,
-                              p.R1 + m * AD + n, vv[LNF ? i : 0]);
+      rt_row_epilogue<T, LNF, KEEP>(v, bv, p.d1, DropCfg{0u, 1.f, 0u}, seed_lo, seed_hi, (uint32_t)m * (uint32_t)AD + (uint32_t)n, true, e0,
+                                    e1, KEEP ? p.R1 + m * AD + n : nullptr, vv[LNF ? i : 0]);
     }
   }
   if constexpr (LNF)
-    eg_epilogue_layernorm256<T>(vv, (float*)(imgs + 4 * RT_IMGB), wn, lane, S, row0, p.ln_gamma, p.ln_beta, p.LN_OUT, p.ln_stats);
+    eg_epilogue_layernorm256<T>(vv, (float*)(imgs + 4 * RT_IMGB), wn, lane, S, row0, p.ln_gamma, p.ln_beta, p.LN_OUT,
+                                KEEP ? p.ln_stats : nullptr);
 }
 
 template <typename T>
@@ -342,9 +358,13 @@ static int ab_launch(const eg_attn_block_desc* d, hipStream_t s) {
   p.d1 = make_drop(d->out_drop_p, d->out_drop_site);
   p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.LN_OUT = (T*)d->ln_out; p.ln_stats = d->ln_stats;
   const bool lnf = d->ln_out != nullptr;
-#define AB_LAUNCH(N_, T_, L_) eg_launch_lds<attn_block_fwd_kernel<T, N_, T_, L_>, A_LDS>(dim3(d->NB), dim3(256), s, p)
-  if (d->S == 65) { if (lnf) AB_LAUNCH(5, true, true); else AB_LAUNCH(5, true, false); }     // class token + 64 positions
-  else { if (lnf) AB_LAUNCH(0, false, true); else AB_LAUNCH(0, false, false); }
+  const bool lean = d->qkv == nullptr;                                                       // (all four stored results null, checked below)
+#define AB_LAUNCH(N_, T_, L_, K_) eg_launch_lds<attn_block_fwd_kernel<T, N_, T_, L_, K_>, A_LDS>(dim3(d->NB), dim3(256), s, p)
+  if (d->S == 65) {                                                                          // class token + 64 positions
+    if (lean) AB_LAUNCH(5, true, true, false); else if (lnf) AB_LAUNCH(5, true, true, true); else AB_LAUNCH(5, true, false, true);
+  } else {
+    if (lean) AB_LAUNCH(0, false, true, false); else if (lnf) AB_LAUNCH(0, false, true, true); else AB_LAUNCH(0, false, false, true);
+  }
 #undef AB_LAUNCH
   EG_LAUNCH_CHECK("attn_block_fwd");
   return 0;
@@ -357,11 +377,14 @@ extern "C" int eg_attn_block_ok(int S, int d_model, int num_heads, int dtype) {
 }
 
 extern "C" int eg_attn_block_fwd(const eg_attn_block_desc* d, void* stream) {
-  EG_CHECK(d && d->x && d->wqkv_frag && d->wo_frag && d->bqkv && d->bo && d->qkv && d->ctx && d->lse && d->r1,
-           "eg_attn_block_fwd: null operand");
+  EG_CHECK(d && d->x && d->wqkv_frag && d->wo_frag && d->bqkv && d->bo, "eg_attn_block_fwd: null operand");
+  const int nstored = (d->qkv != nullptr) + (d->ctx != nullptr) + (d->lse != nullptr) + (d->r1 != nullptr);
   EG_CHECK(eg_attn_block_ok(d->S, d->d_model, d->num_heads, d->dtype),
            "eg_attn_block_fwd: needs a 16-bit dtype, d_model == 256, 8 heads and S <= 80 (got dtype %d, d %d, H %d, S %d)", d->dtype,
            d->d_model, d->num_heads, d->S);
+  EG_CHECK(nstored == 4 || (nstored == 0 && d->ln_out),
+           "eg_attn_block_fwd: qkv, ctx, lse and r1 are all given (the keeping form) or all null (the lean form, which needs ln_out); "
+           "got %d of the four, ln_out %s", nstored, d->ln_out ? "given" : "null");
   EG_CHECK(d->NB > 0 && (long long)d->NB * d->S * 768 < (1ll << 31), "eg_attn_block_fwd: NB=%d", d->NB);
   EG_CHECK(!d->ln_out || (d->ln_gamma && d->ln_beta && (uintptr_t)d->ln_out % 16 == 0),
            "eg_attn_block_fwd: the fused LayerNorm needs gamma, beta and a 16-B aligned output");

@@ -55,7 +55,10 @@ struct FfnArgs {
 // EPI selects epilogue 1's bias / ReLU at compile time: 3 = bias + ReLU (the forward pass), 0 = neither (the backward pass),
 // 4 = as the descriptor says at run time (a per-value select on the flag -- 80 extra vector instructions per chunk).
 // LNF: the layer's second LayerNorm runs on the completed C rows in the final epilogue (eg_epilogue_layernorm256).
-template <typename T, int GATE, int BOUT, int EPI, bool LNF = false>
+// KEEP = false is the LEAN form of a forward that nobody differentiates (<T, 0, 0, 3, true> only): H, C and the LayerNorm statistics
+// are never stored, LN_OUT is the launch's only global store.  The hidden chunk still passes through LDS rounded to 16 bit as
+// product 2's operand and C is still rounded to 16 bit in front of the LayerNorm, so LN_OUT is bit-identical to the keeping form's.
+template <typename T, int GATE, int BOUT, int EPI, bool LNF = false, bool KEEP = true>
 __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
   typedef typename H16<T>::frag frag;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -255,13 +258,15 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
     __syncthreads();        // chunk c is complete in LDS; nobody reads buffer (c+1)&1 (chunk c-1) any more
 
     // ---- the stored result: whole 256-B row segments of the chunk, 16 B per thread ----
-    int tq = tid >> 4;
-    asm volatile("" : "+v"(tq));                               // (same: no loop-invariant address registers)
+    if constexpr (KEEP) {
+      int tq = tid >> 4;
+      asm volatile("" : "+v"(tq));                             // (same: no loop-invariant address registers)
 #pragma unroll
-    for (int ps = 0; ps < 5; ++ps) {
-      const int r = 16 * ps + tq, ch = tid & 15;
-      const u32x4 o = *(const u32x4*)(hc + r * 256 + rt_piece(r, ch));
-      if (m0 + r < p.M) *(u32x4*)(p.H + (size_t)(m0 + r) * (size_t)p.ldh + FC * c + 8 * ch) = o;
+      for (int ps = 0; ps < 5; ++ps) {
+        const int r = 16 * ps + tq, ch = tid & 15;
+        const u32x4 o = *(const u32x4*)(hc + r * 256 + rt_piece(r, ch));
+        if (m0 + r < p.M) *(u32x4*)(p.H + (size_t)(m0 + r) * (size_t)p.ldh + FC * c + 8 * ch) = o;
+      }
     }
 
     // ---- product 2: acc2[i][j] += sum_h W2[col][h] * H[row][h] over the chunk's 128 hidden columns ----
@@ -316,12 +321,12 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
     float v[16];
     rt_image_get(timg, lane, v);
     if (m < p.M)
-      rt_row_epilogue<T, LNF>(v, bv, p.dc1, p.dc2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)FD + (uint32_t)n, p.residual != nullptr,
-                              eraw[i][0], eraw[i][1], p.C + (size_t)m * (size_t)p.ldc + n, vv[LNF ? i : 0]);
+      rt_row_epilogue<T, LNF, KEEP>(v, bv, p.dc1, p.dc2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)FD + (uint32_t)n, p.residual != nullptr,
+                                    eraw[i][0], eraw[i][1], KEEP ? p.C + (size_t)m * (size_t)p.ldc + n : nullptr, vv[LNF ? i : 0]);
   }
   if constexpr (LNF)
     eg_epilogue_layernorm256<T>(vv, (float*)(hb + 4 * RT_IMGB), wn, lane, min(FR, p.M - m0), (size_t)m0, p.ln_gamma, p.ln_beta,
-                                p.LN_OUT, p.ln_stats);
+                                p.LN_OUT, KEEP ? p.ln_stats : nullptr);
 }
 
 template <typename T>
@@ -344,7 +349,8 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   const int gsel = d->gate_bits_in ? 2 : d->gate ? 1 : 0;
   const bool bout = d->gate_bits_out != nullptr;
   const bool lnf = d->ln_out != nullptr;                                                                      // (forward form only, checked below)
-  if (gsel == 0 && d->bias1 && p.relu) {                                                                      // the forward pass
+  if (!d->H) eg_launch_lds<ffn_chain_kernel<T, 0, 0, 3, true, false>, F_LDS>(grid, dim3(256), s, p);         // lean (forward form, LNF, no bits: checked below)
+  else if (gsel == 0 && d->bias1 && p.relu) {                                                                 // the forward pass
     if (lnf) { if (bout) FFN_LAUNCH(0, 1, 3, true); else FFN_LAUNCH(0, 0, 3, true); }
     else { if (bout) FFN_LAUNCH(0, 1, 3, false); else FFN_LAUNCH(0, 0, 3, false); }
   }
@@ -362,18 +368,25 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
 }  // namespace
 
 extern "C" int eg_ffn_chain(const eg_ffn_desc* d, void* stream) {
-  EG_CHECK(d && d->A && d->W1 && d->W2 && d->H && d->C, "eg_ffn_chain: null operand");
+  EG_CHECK(d && d->A && d->W1 && d->W2, "eg_ffn_chain: null operand");
   EG_CHECK(d->dtype == EG_BF16 || d->dtype == EG_F16, "eg_ffn_chain: 16-bit compute dtypes only (got %d)", d->dtype);
+  const bool lean = !d->H && !d->C;
+  EG_CHECK(lean || (d->H && d->C), "eg_ffn_chain: H and C are both given (the keeping form) or both null (the lean form); got %s only",
+           d->H ? "H" : "C");
+  EG_CHECK(!lean || (d->bias1 && d->act1 == EG_ACT_RELU && !d->gate && !d->gate_bits_in),
+           "eg_ffn_chain: the lean form (H and C null) serves the forward form only: bias1, ReLU, no gate, no gate_bits_in");
+  EG_CHECK(!lean || d->ln_out, "eg_ffn_chain: the lean form (H and C null) needs ln_out, its only result");
+  EG_CHECK(!lean || !d->gate_bits_out, "eg_ffn_chain: the lean form (H and C null) writes no gate_bits_out");
   EG_CHECK(d->M > 0 && d->F > 0 && d->F % FC == 0, "eg_ffn_chain: M=%d, F=%d (F must be a multiple of %d)", d->M, d->F, FC);
   EG_CHECK(d->act1 == EG_ACT_NONE || d->act1 == EG_ACT_RELU, "eg_ffn_chain: act1 %d", d->act1);
-  EG_CHECK(d->lda >= FD && d->ldc >= FD && d->ldh >= d->F && d->lda % 8 == 0 && d->ldc % 8 == 0 && d->ldh % 8 == 0,
+  EG_CHECK(d->lda >= FD && d->lda % 8 == 0 && (lean || (d->ldc >= FD && d->ldh >= d->F && d->ldc % 8 == 0 && d->ldh % 8 == 0)),
            "eg_ffn_chain: row strides must be 16-B multiples covering the rows");
   EG_CHECK(!d->gate || (d->ldg >= d->F && d->ldg % 4 == 0), "eg_ffn_chain: gate stride");
   EG_CHECK(!(d->gate_bits_out && (d->gate_bits_in || d->gate)), "eg_ffn_chain: a launch either writes gate bits or applies a gate");
   EG_CHECK(((uintptr_t)d->gate_bits_in | (uintptr_t)d->gate_bits_out) % 8 == 0, "eg_ffn_chain: gate bit words must be 8-B aligned");
   EG_CHECK(!d->residual || (d->ldr >= FD && d->ldr % 8 == 0), "eg_ffn_chain: residual stride");
   EG_CHECK((long long)d->M * d->F < (1ll << 32), "eg_ffn_chain: M*F exceeds the 32-bit dropout index");
-  EG_CHECK(!d->ln_out || (d->ln_gamma && d->ln_beta && d->ldc == FD && !d->gate && !d->gate_bits_in && d->bias1 && d->act1 == EG_ACT_RELU &&
+  EG_CHECK(!d->ln_out || (d->ln_gamma && d->ln_beta && (lean || d->ldc == FD) &&!d->gate && !d->gate_bits_in && d->bias1 && d->act1 == EG_ACT_RELU &&
                           (uintptr_t)d->ln_out % 16 == 0),
            "eg_ffn_chain: the fused LayerNorm serves the forward form (bias + ReLU, no gate) with contiguous C rows");
   const float ps[3] = {d->drop_h_p, d->drop_c1_p, d->drop_c2_p};

@@ -1240,3 +1240,49 @@ extern "C" int eg_fuzzy_gate_fwd(const float* z_img, const float* z_eeg, const f
   EG_LAUNCH_CHECK("fuzzy_gate_fwd");
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Evaluation tail of one batch on the device (T:258-314 per batch: argmax, confusion matrix, loss sum), so that an evaluation loop
+// syncs the host once at its end instead of twice per batch.  One workgroup: B is a few thousand rows at the most and ncls <= 16.
+// The batch's histogram is built in LDS (LDS atomics) and added to the running matrix with plain loads and stores: launches on one
+// stream are ordered, so the read-modify-write of confusion / loss_sum needs no global atomic.
+// ---------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void eval_accumulate_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                              const float* __restrict__ loss, int* __restrict__ pred,
+                                                              int* __restrict__ confusion, float* __restrict__ loss_sum, int B, int ncls) {
+  __shared__ int hist[16 * 16];
+  const int tid = threadIdx.x;
+  hist[tid] = 0;
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {
+    const float* row = logits + (size_t)b * ncls;
+    float best = row[0];
+    int arg = 0;
+    for (int c = 1; c < ncls; ++c) {
+      const float v = row[c];
+      if (v > best) { best = v; arg = c; }         // strict: the lowest index wins a tie
+    }
+    pred[b] = arg;
+    if (confusion) {
+      const long long y = labels[b];
+      if (y >= 0 && y < ncls) atomicAdd(&hist[(int)y * ncls + arg], 1);      // (a label outside the classes counts nowhere)
+    }
+  }
+  __syncthreads();
+  if (confusion && tid < ncls * ncls) confusion[tid] += hist[tid];
+  if (tid == 0 && loss && loss_sum) *loss_sum += *loss;
+}
+}  // namespace
+
+extern "C" int eg_eval_accumulate(const float* logits, const int64_t* labels, const float* loss, int32_t* pred, int32_t* confusion,
+                                  float* loss_sum, int B, int ncls, void* stream) {
+  EG_CHECK(ncls >= 1 && ncls <= 16, "eg_eval_accumulate: ncls=%d outside [1, 16]", ncls);
+  EG_CHECK(B > 0, "eg_eval_accumulate: B=%d", B);
+  EG_CHECK(logits && pred, "eg_eval_accumulate: null logits or pred");
+  EG_CHECK(!confusion || labels, "eg_eval_accumulate: a confusion matrix needs labels");
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, (const long long*)labels, loss, pred,
+                     confusion, loss_sum, B, ncls);
+  EG_LAUNCH_CHECK("eval_accumulate");
+  return 0;
+}

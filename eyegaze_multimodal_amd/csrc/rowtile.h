@@ -95,8 +95,10 @@ __device__ __forceinline__ void rt_store16(T* pc, const float (&v)[16]) {
   store8(pc, v);
   store8(pc + 8, v + 8);
 }
-// + bias, dropout sites, + residual (its two raw pieces), store; LNF: vv = what was stored, for eg_epilogue_layernorm256
-template <typename T, bool LNF>
+// + bias, dropout sites, + residual (its two raw pieces), store; LNF: vv = what was stored, for eg_epilogue_layernorm256.
+// STORE = false (the lean forms of eg_attn_block_fwd / eg_ffn_chain): the row is not written and pc is not read; vv still holds the
+// values rounded to 16 bit, so the LayerNorm that follows sees what a keeping launch would have stored.
+template <typename T, bool LNF, bool STORE = true>
 __device__ __forceinline__ void rt_row_epilogue(float (&v)[16], const float (&bv)[16], const DropCfg& d1, const DropCfg& d2,
                                                 uint32_t seed_lo, uint32_t seed_hi, uint32_t idx, bool has_res, const u32x4& e0,
                                                 const u32x4& e1, T* pc, float (&vv)[16]) {
@@ -104,7 +106,7 @@ __device__ __forceinline__ void rt_row_epilogue(float (&v)[16], const float (&bv
   for (int j = 0; j < 16; ++j) v[j] += bv[j];
   rt_dropout16(v, d1, d2, seed_lo, seed_hi, idx);
   if (has_res) rt_add16<T>(v, e0, e1);
-  rt_store16(pc, v);
+  if constexpr (STORE) rt_store16(pc, v);
   if (LNF) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) vv[j] = round_store<T>(v[j]);

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import Engine, FlatParams
+from .engine import Engine, FlatParams, InferenceEngine
 
 
 class _Holder(nn.Module):
@@ -240,6 +240,7 @@ class DualEEGTransformer(nn.Module):
         self._dtype = _resolve_dtype(compute_dtype)
         self._flat = FlatParams(self)
         self._engines: Dict[tuple, Engine] = {}
+        self._infer_engines: Dict[tuple, InferenceEngine] = {}     # predict()'s own pool: it never evicts a training engine
         self._step_states: Dict[str, torch.Tensor] = {}
         self._state_ready: Dict[str, bool] = {}
         self._fwd_count = 0
@@ -266,6 +267,23 @@ class DualEEGTransformer(nn.Module):
                               init_scale=eng.scaler_cfg["init_scale"])
                 self._state_ready[str(device)] = True
             self._engines[key] = eng
+        return eng
+
+    def inference_engine(self, B: int, T: int, device: torch.device) -> InferenceEngine:
+        """The forward-only engine of predict() for this batch shape, from a pool of its own (bounded like the training pool, keyed
+        (B, T, device, dtype)).  It shares nothing with the training engines but the flat parameter buffer: no step state, no
+        gradient buffer, no forward counter."""
+        L.lib()
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._flat.ensure(device, need_grad=False)
+        key = (B, T, str(device), self._dtype)
+        eng = self._infer_engines.get(key)
+        if eng is None:
+            if len(self._infer_engines) >= 4:
+                self._infer_engines.pop(next(iter(self._infer_engines)))
+            eng = self._infer_engines[key] = InferenceEngine(self, B, T, device, self._dtype)
         return eng
 
     def _state_for(self, device: torch.device) -> torch.Tensor:
@@ -295,6 +313,46 @@ class DualEEGTransformer(nn.Module):
             out["loss_ce"] = a["loss"].clone().reshape(())
             if self.cfg.use_ibs:
                 out["loss_ibs_cls"] = a["ibs_loss"].clone().reshape(())
+        return out
+
+    def _check_windows(self, eeg1, eeg2, labels):
+        if not eeg1.is_cuda:
+            raise L.EgError("DualEEGTransformer (HIP) needs device tensors; there is no CPU fallback "
+                            "(the CPU restatement lives in oracle/ and is test infrastructure)")
+        if eeg1.shape != eeg2.shape or eeg1.dim() != 3 or eeg1.shape[1] != self.cfg.in_channels:
+            raise L.EgError(f"expected two [B, {self.cfg.in_channels}, T] windows, got {tuple(eeg1.shape)} / {tuple(eeg2.shape)}")
+        if labels is not None:
+            labels = labels.to(device=eeg1.device, dtype=torch.int64).contiguous()
+        return eeg1.contiguous().float(), eeg2.contiguous().float(), labels
+
+    def _run_predict(self, eeg1, eeg2, labels, pack: bool = True) -> Dict[str, torch.Tensor]:
+        """predict()'s body behind eyegaze::dual_eeg_predict: the inference engine's forward and copies of its results"""
+        eng = self.inference_engine(eeg1.shape[0], eeg1.shape[2], eeg1.device)
+        eng.forward(eeg1, eeg2, labels, pack=pack)
+        a = eng.a
+        out = {"logits": a["logits"].clone(), "cls1": a["cls1"].clone(), "cls2": a["cls2"].clone()}
+        if self.cfg.use_ibs:
+            out["ibs_logits"] = a["ibs_logits"].clone()
+            out["ibs_token"] = a["ibs_pool_f"].clone()
+        if labels is not None:
+            out["loss_ce"] = a["loss"].clone().reshape(())
+            if self.cfg.use_ibs:
+                out["loss_ibs_cls"] = a["ibs_loss"].clone().reshape(())
+        return out
+
+    @torch.no_grad()
+    def predict(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None) -> dict:
+        """What an eval-mode forward() returns -- the same keys and bits, the losses included when labels are given -- from the
+        forward-only engine: no activation is kept for a backward, nothing of the training state (step state, forward counter,
+        dropout seeds, gradient buffers) is read or written, so it may run between a forward and its backward or between two steps.
+        Works in any module mode, under or outside no_grad; the results do not require grad."""
+        eeg1, eeg2, labels = self._check_windows(eeg1, eeg2, labels)
+        self.inference_engine(eeg1.shape[0], eeg1.shape[2], eeg1.device)     # (re)flattens the parameters before they are handed over
+        from . import ops
+        vals = torch.ops.eyegaze.dual_eeg_predict(eeg1, eeg2, labels, [p.detach() for p in self._flat.params], self._op_handle)
+        out = {k: v for k, v in zip(ops.OUTPUT_KEYS, vals) if v.numel() > 0}
+        if labels is not None:
+            out["loss"] = out["loss_ce"]
         return out
 
     def _run_backward(self, shape, fwd_id: int, gouts: Dict[str, Optional[torch.Tensor]]):

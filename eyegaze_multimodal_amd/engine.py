@@ -102,8 +102,9 @@ class FlatParams:
         self.grad: Optional[torch.Tensor] = None
         self.acc: Optional[torch.Tensor] = None      # gradient accumulator over micro-batches (accumulator(): made on first use)
 
-    def ensure(self, device: torch.device):
-        """(Re)flattens when the module was moved / re-created since the last call."""
+    def ensure(self, device: torch.device, need_grad: bool = True):
+        """(Re)flattens when the module was moved / re-created since the last call.  need_grad=False (the forward-only route)
+        leaves the gradient buffer to the first caller that needs one."""
         ok = self.flat is not None and self.flat.device == device
         if ok:
             base = self.flat.data_ptr()
@@ -112,6 +113,8 @@ class FlatParams:
                     ok = False
                     break
         if ok:
+            if need_grad and self.grad is None:
+                self.grad = torch.zeros(self.total, device=device, dtype=torch.float32)
             return
         flat = torch.zeros(self.total, device=device, dtype=torch.float32)
         for n, p in zip(self.names, self.params):
@@ -119,7 +122,7 @@ class FlatParams:
             flat[o:o + p.numel()].copy_(p.data.reshape(-1).to(device=device, dtype=torch.float32))
             p.data = flat[o:o + p.numel()].view(p.shape)
         self.flat = flat
-        self.grad = torch.zeros(self.total, device=device, dtype=torch.float32)
+        self.grad = torch.zeros(self.total, device=device, dtype=torch.float32) if need_grad else None
         self.acc = None                # belongs to the buffers it was made beside: re-made on the next accumulator()
 
     def accumulator(self) -> torch.Tensor:
@@ -740,10 +743,11 @@ class Engine(EngineBase):
         self.gemm(ptr(ctx), ptr(self.w[f"o{l}"]), ptr(r), M, d, d, bias=self.fp.p_ptr(pre + "out_proj.bias"),
                   drop1=(p, sites["drop1"]), residual=ptr(x))
 
-    def attn_block_fwd(self, x, l, p, sites, ln=None):
-        """eg_attn_block_fwd (csrc/attnblock.hip): A:202-213 + the residual of A:292-293 for encoder layer l in one launch"""
+    def attn_block_fwd(self, x, l, p, sites, ln=None, lean=False):
+        """eg_attn_block_fwd (csrc/attnblock.hip): A:202-213 + the residual of A:292-293 for encoder layer l in one launch.
+        lean: the forward-only form -- nothing but ln's rows is stored (no q|k|v, lse, ctx, r1, no statistics)"""
         w, fp, d = self.w, self.fp, self.cfg.d_model
-        pre, qkv, lse, ctx, r1 = self._attn_stage(l)
+        pre, qkv, lse, ctx, r1 = (f"encoder.layers.{l}.mha.", None, None, None, None) if lean else self._attn_stage(l)
         dsc = L.AttnBlockDesc()
         dsc.x, dsc.wqkv_frag, dsc.wo_frag = ptr(x), ptr(w[f"wqkvb{l}"]), ptr(w[f"wob{l}"])
         dsc.bqkv, dsc.bo = ptr(w[f"bqkv{l}"]), fp.p_ptr(pre + "out_proj.bias")
@@ -762,6 +766,8 @@ class Engine(EngineBase):
             nbytes = self.es * (M * d * 3 + M * 3 * d + 4 * d * d) + 4 * (self.NB * H * S + 4 * d)    # x, ctx, r1 | qkv | weights | lse, biases
             if ln is not None:
                 nbytes += self.es * M * d + 8 * M + 8 * d                                             # norm1 rows, statistics, gain / bias
+            if lean:
+                nbytes = self.es * (2 * M * d + 4 * d * d) + 4 * 4 * d + 8 * d                        # x, norm1 rows | weights | biases, gain / bias
             return flops, float(nbytes), (M, 3 * d, d), 8
         probe = self._timed(work)
         call("eg_attn_block_fwd", C.byref(dsc), self.stream)
@@ -772,7 +778,7 @@ class Engine(EngineBase):
         """eg_ffn_chain: H = epi1(A W1^T), C = epi2(H W2^T) in one launch (weights in fragment order)."""
         d = self.cfg.d_model
         dsc = L.FfnDesc()
-        dsc.A, dsc.W1, dsc.W2, dsc.H, dsc.C = A, W1f, W2f, H, Cout
+        dsc.A, dsc.W1, dsc.W2, dsc.H, dsc.C = A, W1f, W2f, H or None, Cout or None      # (both None: the forward-only form, ln's rows alone)
         dsc.bias1, dsc.bias2, dsc.gate, dsc.residual = bias1 or None, bias2 or None, gate or None, residual or None
         dsc.gate_bits_out, dsc.gate_bits_in = bits_out or None, bits_in or None
         dsc.state = self.st_ptr
@@ -790,6 +796,8 @@ class Engine(EngineBase):
             es = self.es
             nbytes = es * (M * d * (2 + (1 if residual and residual != A else 0)) + M * F * (1 + (1 if gate else 0)) + 2 * F * d) \
                 + (M * F // 8 if (bits_out or bits_in) else 0) + 4 * (F + d) + ((es * M * d + 8 * M + 8 * d) if ln is not None else 0)
+            if not H:
+                nbytes = es * (2 * M * d + 2 * F * d) + 4 * (F + d) + 8 * d                           # A, norm2 rows | weights | biases, gain / bias
             return 4.0 * M * F * d, float(nbytes), (M, F, d), 4
         probe = self._timed(work)
         call("eg_ffn_chain", C.byref(dsc), self.stream)
@@ -975,24 +983,7 @@ class Engine(EngineBase):
         p01 = 0.1 if train else 0.0
         self.train_flags = (p, p01, train)
         self.pack_params()
-        for i, x in enumerate((eeg1, eeg2)):
-            if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, self.C, self.T):
-                raise L.EgError(f"input windows must be contiguous f32 [{B},{self.C},{self.T}], got {tuple(x.shape)} {x.dtype}")
-            call("eg_window_pack", ptr(x), ptr(a["xt"]) + i * B * self.Tp * self.Cp * es, B, self.C, self.T, self.Cp,
-                 self.pad, self.Tp, self.dtype, st)
-        # K1: conv0 as a GEMM over overlapping channel-last rows (D:154,171)
-        self.gemm(ptr(a["xt"]), ptr(w["conv0"]), ptr(a["h0pad"]) + self.pad * d * es, NB * self.T1, d, self.K0,
-                  a=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1), c=rowmap(d, self.R0 * d, self.T1),
-                  bias=fp.p_ptr("temporal_conv.convs.0.bias"), act=L.ACT_RELU, drop1=(p01, SITE_CONV0))
-        # K2: conv1, epilogue writes token rows [off:] of the sequence with the positional rows added (D:158,171,174; A:120-126)
-        self.gemm(ptr(a["h0pad"]), ptr(w["conv1"]), ptr(a["x0"]) + self.off * d * es, NB * self.T2, d, self.k * d,
-                  a=rowmap(self.s * d, self.R0 * d, self.T2), c=rowmap(d, S * d, self.T2),
-                  r=rowmap(d, 0, self.T2), p=rowmap(d), bias=fp.p_ptr("temporal_conv.convs.1.bias"), act=L.ACT_RELU,
-                  drop1=(p01, SITE_CONV1), residual=ptr(w["pos"]) + self.off * d * es, out_pre=ptr(a["h1"]), tag="conv1_fwd")
-        # CLS rows (D:1157) + pos row 0
-        call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
-             0, 1, self.dtype, st)
-        self.model._extra_tokens_fwd(self, eeg1, eeg2, train)
+        self._front_end_fwd(eeg1, eeg2, train, p01, a["h1"])
         # encoder (A:292-295, 326-328), both streams batched (Siamese weights)
         for l in range(cfg.num_layers):
             pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
@@ -1011,10 +1002,7 @@ class Engine(EngineBase):
                          drop_c2=(p, sites["drop2"]), bits_out=ptr(a[f"gbits{l}"]),
                          ln=((pre + "ln2", a[f"x{l + 1}"], a[f"st2_{l}"]) if self.ln_fuse else None))
             else:
-                self.gemm(ptr(a[f"y1_{l}"]), ptr(w[f"w1{l}"]), ptr(a[f"hff{l}"]), M, F, d, bias=fp.p_ptr(pre + "ffn.linear1.bias"),
-                          act=L.ACT_RELU, drop1=(p, sites["ffn_a"]))
-                self.gemm(ptr(a[f"hff{l}"]), ptr(w[f"w2{l}"]), ptr(a[f"r2_{l}"]), M, d, F, bias=fp.p_ptr(pre + "ffn.linear2.bias"),
-                          drop1=(p, sites["ffn_b"]), drop2=(p, sites["drop2"]), residual=ptr(a[f"y1_{l}"]))
+                self.ffn_unfused_fwd(a[f"y1_{l}"], l, a[f"hff{l}"], a[f"r2_{l}"], p, sites)
             if not (self.fuse_ffn and self.ln_fuse):
                 self.ln_fwd(a[f"r2_{l}"], pre + "ln2", a[f"x{l + 1}"], a[f"st2_{l}"])
         Lr = cfg.num_layers
@@ -1025,6 +1013,44 @@ class Engine(EngineBase):
             self.attn_unfused_fwd(z, "x", B, _layer_sites(Lr), p)
             self.ln_fwd(a["rx"], "cross_attn.norm", a["zc"], a["stx"])
             z = a["zc"]
+        self._heads_fwd(z, labels, train, p)
+
+    def ffn_unfused_fwd(self, y1, l, hff, r2, p, sites):
+        """Layer l's feed-forward pair as two launches: linear1 + ReLU + dropout, linear2 + dropout x2 + residual (A:272, A:294)"""
+        M, d, F, w, fp, pre = self.M, self.cfg.d_model, self.cfg.d_ff, self.w, self.fp, f"encoder.layers.{l}."
+        self.gemm(ptr(y1), ptr(w[f"w1{l}"]), ptr(hff), M, F, d, bias=fp.p_ptr(pre + "ffn.linear1.bias"),
+                  act=L.ACT_RELU, drop1=(p, sites["ffn_a"]))
+        self.gemm(ptr(hff), ptr(w[f"w2{l}"]), ptr(r2), M, d, F, bias=fp.p_ptr(pre + "ffn.linear2.bias"),
+                  drop1=(p, sites["ffn_b"]), drop2=(p, sites["drop2"]), residual=ptr(y1))
+
+    def _front_end_fwd(self, eeg1, eeg2, train: bool, p01: float, h1):
+        """Input windows -> token rows a["x0"]: window pack, conv-0, conv-1 (+ positions), the CLS rows and the optional token
+        families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written)."""
+        cfg, d = self.cfg, self.cfg.d_model
+        B, NB, S, a, w, fp, es, st = self.B, self.NB, self.S, self.a, self.w, self.fp, self.es, self.stream
+        for i, x in enumerate((eeg1, eeg2)):
+            if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, self.C, self.T):
+                raise L.EgError(f"input windows must be contiguous f32 [{B},{self.C},{self.T}], got {tuple(x.shape)} {x.dtype}")
+            call("eg_window_pack", ptr(x), ptr(a["xt"]) + i * B * self.Tp * self.Cp * es, B, self.C, self.T, self.Cp,
+                 self.pad, self.Tp, self.dtype, st)
+        # K1: conv0 as a GEMM over overlapping channel-last rows (D:154,171)
+        self.gemm(ptr(a["xt"]), ptr(w["conv0"]), ptr(a["h0pad"]) + self.pad * d * es, NB * self.T1, d, self.K0,
+                  a=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1), c=rowmap(d, self.R0 * d, self.T1),
+                  bias=fp.p_ptr("temporal_conv.convs.0.bias"), act=L.ACT_RELU, drop1=(p01, SITE_CONV0))
+        # K2: conv1, epilogue writes token rows [off:] of the sequence with the positional rows added (D:158,171,174; A:120-126)
+        self.gemm(ptr(a["h0pad"]), ptr(w["conv1"]), ptr(a["x0"]) + self.off * d * es, NB * self.T2, d, self.k * d,
+                  a=rowmap(self.s * d, self.R0 * d, self.T2), c=rowmap(d, S * d, self.T2),
+                  r=rowmap(d, 0, self.T2), p=rowmap(d), bias=fp.p_ptr("temporal_conv.convs.1.bias"), act=L.ACT_RELU,
+                  drop1=(p01, SITE_CONV1), residual=ptr(w["pos"]) + self.off * d * es, out_pre=ptr(h1), tag="conv1_fwd")
+        # CLS rows (D:1157) + pos row 0
+        call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
+             0, 1, self.dtype, st)
+        self.model._extra_tokens_fwd(self, eeg1, eeg2, train)
+
+    def _heads_fwd(self, z, labels, train: bool, p: float):
+        """Pooling, symmetric fusion, classifier(s) and the losses on the final token rows z (D:1193-1213)"""
+        cfg, d = self.cfg, self.cfg.d_model
+        B, S, a, w, fp, st = self.B, self.S, self.a, self.w, self.fp, self.stream
         self.z_final = z
         # heads (D:1193-1213)
         call("eg_pool_fuse_fwd", ptr(z), ptr(a["cls1"]), ptr(a["cls2"]), ptr(a["comb"]), ptr(a["zf"]),
@@ -1316,3 +1342,205 @@ class Engine(EngineBase):
         if self.scaler_on:      # GradScaler.update(): back off after an overflow, grow after growth_interval clean steps
             c = self.scaler_cfg
             call("eg_scaler_update", self.st_ptr, c["growth"], c["backoff"], c["growth_interval"], self.stream)
+
+
+# ------------------------------------------------------------------------------------------------
+# forward-only route
+# ------------------------------------------------------------------------------------------------
+def _front_end_dims(cfg, T: int, dtype: int):
+    """(Cp, Tp, R0, T2) of the convolution front end at window length T: Engine.__init__'s arithmetic, device-free"""
+    k, s = cfg.conv_kernel_size, cfg.conv_stride
+    pad, bk = k // 2, (32 if dtype == EG_F32 else 64)
+    Cp = _align(cfg.in_channels, 8)
+    T1 = (T + 2 * pad - k) // s + 1
+    T2 = (T1 + 2 * pad - k) // s + 1
+    K0 = _align(k * Cp, bk)
+    Tp = _align(max(T + 2 * pad, s * (T1 - 1) + K0 // Cp + 1), 8)
+    return Cp, Tp, (T1 + 2 * pad + s - 1) // s * s, T2
+
+
+def _inference_tensors(cfg, B: int, T: int, dtype: int):
+    """The inference engine's own workspace, device-free: ({name: (shape, 16-bit-or-compute?)}, same for the shared scratch set).
+    An entry is (shape, is_f32); compute-dtype tensors have is_f32 False.  InferenceEngine allocates exactly these."""
+    d, F, H, nc = cfg.d_model, cfg.d_ff, cfg.num_heads, cfg.num_classes
+    NB, S = 2 * B, sequence_length(cfg, T)
+    M = NB * S
+    Cp, Tp, R0, _ = _front_end_dims(cfg, T, dtype)
+    a = {"xt": ((NB, Tp, Cp), False), "h0pad": ((NB, R0, d), False),
+         "xa": ((M, d), False), "xb": ((M, d), False), "y1": ((M, d), False),       # layer input / output ping-pong, normed mid-layer rows
+         "cls1": ((B, d), True), "cls2": ((B, d), True), "comb": ((B, 3 * d), False), "zf": ((B, 3 * d), False), "hcl": ((B, d), False),
+         "logits": ((B, nc), True), "sloss": ((B,), True), "loss": ((1,), True)}
+    if cfg.use_ibs:
+        a.update({"ibs_pool_f": ((B, d), True), "ibs_pool": ((B, d), False), "hib": ((B, d // 2), False),
+                  "ibs_logits": ((B, nc), True), "ibs_sloss": ((B,), True), "ibs_loss": ((1,), True)})
+    sc = {"qkv": ((M, 3 * d), False), "lse": ((NB, H, S), True), "ctx": ((M, d), False), "r": ((M, d), False),
+          "hff": ((M, F), False), "st": ((M, 2), True)}
+    return a, sc
+
+
+def inference_workspace_bytes(cfg, B: int, T: int, dtype: int) -> Tuple[int, int]:
+    """(with the shared scratch set, without it): bytes of the activations an InferenceEngine of this shape holds, device-free.
+    Independent of num_layers.  Not counted: the packed parameters `w`, the 4-byte counter of the fused heads, and the buffers of
+    the optional token families (tokens.py), which are the training engine's."""
+    es = 4 if dtype == EG_F32 else 2
+    a, sc = _inference_tensors(cfg, B, T, dtype)
+
+    def nbytes(tab):
+        total = 0
+        for shape, f32 in tab.values():
+            n = 1
+            for x in shape:
+                n *= x
+            total += n * (4 if f32 else es)
+        return total
+    lean = nbytes(a)
+    return lean + nbytes(sc), lean
+
+
+class InferenceEngine(Engine):
+    """Forward-only engine for a fixed (B, T): predicts without saving what a backward would read.  No per-layer activations (two
+    ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts, always p = 0, and
+    it neither reads nor writes the model's step state, forward counter or seeds.  Where a layer half has a lean launch
+    (eg_attn_block_fwd / eg_ffn_chain with only ln_out stored) it takes it; every other launch is the training engine's, writing
+    into ONE shared scratch set allocated on first need.  Same bits as Engine.forward(train=False)."""
+    inference = True
+
+    def _init_state(self, state_dev):
+        # a private all-zero state that no launch writes: at p = 0 no kernel reads a seed, and eg_set_step_state is never called
+        self.state_dev = torch.zeros(L.STATE_WORDS, dtype=torch.int32, device=self.device)
+
+    def _alloc(self):
+        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
+        f32 = torch.float32
+        w = {"conv0": self._t(d, self.K0), "conv1": self._t(d, self.k * d), "pos": self._t(cfg.max_len, d)}
+        for l in list(range(cfg.num_layers)) + (["x"] if cfg.use_cross_attention else []):
+            w[f"bqkv{l}"] = self._t(3 * d, dtype=f32)
+            if self.attn_block and l != "x":
+                w[f"wqkvb{l}"], w[f"wob{l}"] = self._t(3 * d * d), self._t(d * d)
+            else:
+                w[f"qkv{l}"], w[f"o{l}"] = self._t(3 * d, d), self._t(d, d)
+            if l != "x" and self.fuse_ffn:
+                w[f"w1f{l}"], w[f"w2f{l}"] = self._t(F * d), self._t(F * d)
+            elif l != "x":
+                w[f"w1{l}"], w[f"w2{l}"] = self._t(F, d), self._t(d, F)
+        w["sf"], w["c0"] = self._t(d, 3 * d), self._t(d, 3 * d)
+        if cfg.use_ibs:
+            w["i0"] = self._t(d // 2, d)
+        self.w = w
+        shapes, self._sc_shapes = _inference_tensors(cfg, self.B, self.T, self.dtype)
+        a = {n: self._t(*shape, dtype=(f32 if is32 else None)) for n, (shape, is32) in shapes.items()}
+        a["x0"] = a["xa"]                                  # the front end and the token families write the token rows here
+        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.a = a
+        self.sc = {}                                       # the shared scratch set: qkv, lse, ctx, r, hff, st -- see _scratch
+        self.routes_taken = []                             # (layer, "attn" | "ffn", "lean" | "scratch") of the last forward
+
+    def _scratch(self, name: str) -> torch.Tensor:
+        if name not in self.sc:
+            shape, is32 = self._sc_shapes[name]
+            self.sc[name] = self._t(*shape, dtype=(torch.float32 if is32 else None))
+        return self.sc[name]
+
+    def _attn_stage(self, l):
+        pre = "cross_attn.cross_attn." if l == "x" else f"encoder.layers.{l}.mha."
+        return pre, self._scratch("qkv"), self._scratch("lse"), self._scratch("ctx"), self._scratch("r")
+
+    def _pack_body(self):
+        """Only the layouts the forward reads (Engine._pack_body's forward half, by the same routes)"""
+        cfg, d, F, fp, w = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.fp, self.w
+        self.p_conv(fp.p_ptr("temporal_conv.convs.0.weight"), ptr(w["conv0"]), d, self.C, self.k, self.Cp, self.K0)
+        self.p_conv(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1"]), d, d, self.k, d, self.k * d)
+        self.p_cast(fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["pos"]), cfg.max_len * d)
+        for l in list(range(cfg.num_layers)) + (["x"] if cfg.use_cross_attention else []):
+            pre = "cross_attn.cross_attn." if l == "x" else f"encoder.layers.{l}.mha."
+            block = self.attn_block and l != "x"
+            for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
+                if block:
+                    self.p_frag(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"wqkvb{l}"]), d, d, 7, part=i)
+                else:
+                    self.p_cast(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkv{l}"]) + i * d * d * self.es, d * d)
+                self.p_copy(fp.p_ptr(f"{pre}{n}.bias"), ptr(w[f"bqkv{l}"]) + 4 * i * d, d)
+            if block:
+                self.p_frag(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"wob{l}"]), d, d, 8)
+            else:
+                self.p_cast(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"o{l}"]), d * d)
+            if l == "x":
+                continue
+            pre = f"encoder.layers.{l}.ffn."
+            if self.fuse_ffn:
+                self.p_frag(fp.p_ptr(pre + "linear1.weight"), ptr(w[f"w1f{l}"]), F, d, 3)
+                self.p_frag(fp.p_ptr(pre + "linear2.weight"), ptr(w[f"w2f{l}"]), d, F, 5)
+            else:
+                self.p_cast(fp.p_ptr(pre + "linear1.weight"), ptr(w[f"w1{l}"]), F * d)
+                self.p_cast(fp.p_ptr(pre + "linear2.weight"), ptr(w[f"w2{l}"]), d * F)
+        self.p_cast(fp.p_ptr("symmetric_fusion.proj.weight"), ptr(w["sf"]), 3 * d * d)
+        self.p_cast(fp.p_ptr("classifier.0.weight"), ptr(w["c0"]), 3 * d * d)
+        if cfg.use_ibs:
+            self.p_cast(fp.p_ptr("ibs_classifier.0.weight"), ptr(w["i0"]), (d // 2) * d)
+        self.model._pack_extra(self)
+
+    def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None, pack: bool = True):
+        """pack=False: the packed weights of an earlier call still hold (a caller walking many batches packs once)"""
+        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
+        B, M, a, w, fp = self.B, self.M, self.a, self.w, self.fp
+        self.stream = self._cur_stream()
+        self.train_flags = (0.0, 0.0, False)
+        self.routes_taken = []
+        if pack or self._plan_key is None:
+            self.pack_params()
+        self._front_end_fwd(eeg1, eeg2, False, 0.0, None)
+        xin, xout, y1 = a["xa"], a["xb"], a["y1"]
+        for l in range(cfg.num_layers):
+            pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
+            drop = self.model.encoder.layers[l].mha.dropout
+            lean_attn = self.attn_block and self.ln_fuse and not (drop._forward_hooks or drop._forward_pre_hooks)
+            if lean_attn:
+                self.attn_block_fwd(xin, l, 0.0, sites, ln=(pre + "ln1", y1, None), lean=True)
+            elif self.attn_block:
+                self.attn_block_fwd(xin, l, 0.0, sites, ln=((pre + "ln1", y1, self._scratch("st")) if self.ln_fuse else None))
+                self._probs_hook(drop, self._scratch("qkv"), self._scratch("lse"), 0)
+            else:
+                self.attn_unfused_fwd(xin, l, 0, sites, 0.0)
+            if not (self.attn_block and self.ln_fuse):
+                self.ln_fwd(self._scratch("r"), pre + "ln1", y1, self._scratch("st"))
+            self.routes_taken.append((l, "attn", "lean" if lean_attn else "scratch"))
+            b1, b2 = fp.p_ptr(pre + "ffn.linear1.bias"), fp.p_ptr(pre + "ffn.linear2.bias")
+            if self.fuse_ffn and self.ln_fuse:
+                self.ffn(ptr(y1), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), 0, 0, M, F, bias1=b1, bias2=b2, act1=L.ACT_RELU,
+                         residual=ptr(y1), ln=(pre + "ln2", xout, None))
+            elif self.fuse_ffn:
+                self.ffn(ptr(y1), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), ptr(self._scratch("hff")), ptr(self._scratch("r")), M, F,
+                         bias1=b1, bias2=b2, act1=L.ACT_RELU, residual=ptr(y1))
+            else:
+                self.ffn_unfused_fwd(y1, l, self._scratch("hff"), self._scratch("r"), 0.0, sites)
+            if not (self.fuse_ffn and self.ln_fuse):
+                self.ln_fwd(self._scratch("r"), pre + "ln2", xout, self._scratch("st"))
+            self.routes_taken.append((l, "ffn", "lean" if (self.fuse_ffn and self.ln_fuse) else "scratch"))
+            xin, xout = xout, xin
+        # the ping-pong pair also serves the final norm (zn) and the cross-attention stage's output (zc)
+        self.ln_fwd(xin, "encoder.norm", xout, self._scratch("st"))
+        z, free = xout, xin
+        if cfg.use_cross_attention:
+            self.attn_unfused_fwd(z, "x", B, _layer_sites(cfg.num_layers), 0.0)
+            self.ln_fwd(self._scratch("r"), "cross_attn.norm", free, self._scratch("st"))
+            z = free
+        self._heads_fwd(z, labels, False, 0.0)
+
+    def _refuse(self, what):
+        raise L.EgError(f"{what}() on an inference engine: it keeps no activations and has no backward workspace "
+                        "(use DualEEGTransformer.forward / Engine for training)")
+
+    def backward(self, *a, **k):
+        self._refuse("backward")
+
+    def accumulate(self, *a, **k):
+        self._refuse("accumulate")
+
+    def optimizer_step(self, *a, **k):
+        self._refuse("optimizer_step")
+
+    def set_state(self, *a, **k):
+        self._refuse("set_state")
+
+    def check_overflow_and_update_scaler(self):
+        self._refuse("check_overflow_and_update_scaler")

@@ -14,6 +14,10 @@ REGISTERED operators, visible to the dispatcher / profiler / torch.compile graph
       clip_grad_norm_(max_norm) + AdamW of train_art.py:221-222 on the flat buffers (mutates all but the gradients);
       flat_grads is the module's gradient buffer or, under gradient accumulation, its accumulator (Engine.accumulate)
 
+  eyegaze::dual_eeg_predict(Tensor eeg1, Tensor eeg2, Tensor? labels, Tensor[] params, int handle) -> Tensor[]
+      DualEEGTransformer.predict: the forward-only engine (engine.InferenceEngine), outputs in OUTPUT_KEYS order as above; no
+      autograd formula -- nothing is kept that a backward could read
+
 `handle` names the Python-side engine owner (a module instance): operators carry tensors and scalars only.
 Both operators are CUDA(HIP)-only: there is no CPU kernel behind them, calling them with host tensors raises.
 """
@@ -55,13 +59,28 @@ def dual_eeg_forward(eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[to
 
 @dual_eeg_forward.register_fake
 def _(eeg1, eeg2, labels, params, handle, train):
-    model = owner(handle)
+    return _fake_outputs(eeg1, labels, owner(handle))
+
+
+def _fake_outputs(eeg1, labels, model):
     B, d, nc = eeg1.shape[0], model.cfg.d_model, model.cfg.num_classes
     e = lambda: eeg1.new_empty(0)
     ibs, lab = model.cfg.use_ibs, labels is not None
     return [eeg1.new_empty(B, nc), eeg1.new_empty(B, d), eeg1.new_empty(B, d),
             eeg1.new_empty(B, nc) if ibs else e(), eeg1.new_empty(B, d) if ibs else e(),
             eeg1.new_empty(()) if lab else e(), eeg1.new_empty(()) if (lab and ibs) else e()]
+
+
+@torch.library.custom_op("eyegaze::dual_eeg_predict", mutates_args=(), device_types="cuda")
+def dual_eeg_predict(eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], params: Sequence[torch.Tensor],
+                     handle: int) -> List[torch.Tensor]:
+    out = owner(handle)._run_predict(eeg1, eeg2, labels)
+    return [out[k] if k in out else eeg1.new_empty(0) for k in OUTPUT_KEYS]
+
+
+@dual_eeg_predict.register_fake
+def _(eeg1, eeg2, labels, params, handle):
+    return _fake_outputs(eeg1, labels, owner(handle))
 
 
 def _setup(ctx, inputs, output):

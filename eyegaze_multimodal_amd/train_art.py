@@ -88,6 +88,24 @@ def macro_metrics(y_true: np.ndarray, y_pred: np.ndarray) -> Dict[str, float]:
             "eval/recall": float(np.mean(R)), "eval/f1": float(np.mean(F))}
 
 
+def macro_metrics_from_confusion(cm: np.ndarray) -> Dict[str, float]:
+    """macro_metrics from the confusion matrix cm[true][predicted] (what eg_eval_accumulate sums on the device): the classes that
+    occur in neither the labels nor the predictions are left out of the averages, as np.union1d leaves them out above."""
+    cm = np.asarray(cm, dtype=np.int64)
+    tp_all, row, col = np.diag(cm), cm.sum(1), cm.sum(0)
+    P, R, F = [], [], []
+    for c in np.nonzero(row + col)[0]:
+        tp, fp, fn = float(tp_all[c]), float(col[c] - tp_all[c]), float(row[c] - tp_all[c])
+        p = tp / (tp + fp) if tp + fp > 0 else 0.0
+        r = tp / (tp + fn) if tp + fn > 0 else 0.0
+        P.append(p)
+        R.append(r)
+        F.append(2 * p * r / (p + r) if p + r > 0 else 0.0)
+    # (np.mean of n exact 0 / 1 terms is this one division of two exact integers: the same float)
+    return {"eval/accuracy": float(tp_all.sum()) / float(cm.sum()), "eval/precision": float(np.mean(P)),
+            "eval/recall": float(np.mean(R)), "eval/f1": float(np.mean(F))}
+
+
 class Trainer:
     def __init__(self, config: Dict[str, Any], device: torch.device, rank: int = 0, world: int = 1, compute_dtype=None):
         self.config, self.device, self.rank, self.world = config, device, rank, world
@@ -101,6 +119,8 @@ class Trainer:
         self.step_no = 0                 # optimiser steps taken
         self.micro_no = 0                # micro-batches seen: the dropout seed counter (== step_no without accumulation)
         self.accum = accumulation_steps(config)
+        # training.inference_eval: evaluate() on the forward-only route (model.predict's engine + eg_eval_accumulate); absent = false
+        self.inference_eval = bool(t.get("inference_eval", False))
         self.pending = 0                 # micro-batches in the accumulator since the last optimiser step
         self.reducer = None              # data parallel, one batch per step: reduces the gradient buffer
         self.accred = None               # data parallel with accumulation: reduces the accumulator, once per optimiser step
@@ -239,6 +259,8 @@ class Trainer:
     @torch.no_grad()
     def evaluate(self, batches) -> Dict[str, float]:
         """evaluate() of train_art.py:258-314: eval forward, argmax, macro metrics."""
+        if self.inference_eval:
+            return self._evaluate_inference(batches)
         self.model.eval()
         preds, labs, tot, n = [], [], 0.0, 0
         for eeg1, eeg2, labels in batches:
@@ -257,6 +279,35 @@ class Trainer:
             tot, n = sum(g[2] for g in gathered), sum(g[3] for g in gathered)
         m = macro_metrics(yt, yp) if len(yt) else {"eval/accuracy": 0.0, "eval/precision": 0.0, "eval/recall": 0.0, "eval/f1": 0.0}
         return {"eval/loss": tot / max(n, 1), **m}
+
+    @torch.no_grad()
+    def _evaluate_inference(self, batches) -> Dict[str, float]:
+        """evaluate() on the forward-only route: no training workspace is built or evicted for the evaluation batch size, no step state
+        or dropout seed moves, and the host syncs ONCE, after the last batch -- argmax, confusion matrix and loss sum are kept on the
+        device by eg_eval_accumulate.  Data parallel: the matrix and the sums are all-reduced.  Same dict as evaluate(): equal metrics,
+        the loss to fp32 summation order.  (A label outside [0, num_classes) counts in no cell here.)"""
+        from ._lib import call, ptr
+        model, dev, ncls = self.model, self.device, self.model.cfg.num_classes
+        cm = torch.zeros(ncls, ncls, device=dev, dtype=torch.int32)
+        sums = torch.zeros(2, device=dev)                       # loss sum, batch count
+        packed = set()
+        for eeg1, eeg2, labels in batches:
+            eeg1, eeg2, labels = model._check_windows(eeg1, eeg2, labels)
+            B = eeg1.shape[0]
+            eng = model.inference_engine(B, eeg1.shape[2], eeg1.device)
+            eng.forward(eeg1, eeg2, labels, pack=id(eng) not in packed)       # the weights do not change inside an evaluation
+            packed.add(id(eng))
+            pred = torch.empty(B, device=dev, dtype=torch.int32)
+            call("eg_eval_accumulate", ptr(eng.a["logits"]), ptr(labels), ptr(eng.a["loss"]), ptr(pred), ptr(cm), ptr(sums), B, ncls,
+                 eng.stream)
+            sums[1] += 1
+        if self.world > 1:
+            dist.all_reduce(cm)
+            dist.all_reduce(sums)
+        cm_h, (tot, n) = cm.cpu().numpy(), sums.tolist()
+        m = macro_metrics_from_confusion(cm_h) if cm_h.sum() else {"eval/accuracy": 0.0, "eval/precision": 0.0, "eval/recall": 0.0,
+                                                                   "eval/f1": 0.0}
+        return {"eval/loss": tot / max(n, 1.0), **m}
 
 
 def split_items(items, test_size: float, seed: int):

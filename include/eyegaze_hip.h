@@ -192,13 +192,17 @@ int eg_gemm_nt_batch_route(const eg_gemm_desc* descs, int n);
  *   scaled by gate_scale), W2 = linear1^T, residual = the gradient arriving on the skip path.
  *   Bit-identical to the two eg_gemm_nt launches it replaces (same MFMA chains, epilogue order and dropout indices m*N + n);
  *   the hidden rows cross HBM once (the stored H) instead of three times.  16-bit dtypes, F % 128 == 0, strides in elements.
+ *   LEAN form (a forward that nobody differentiates): H and C both NULL.  Then nothing but ln_out is stored -- the hidden chunk
+ *   still passes through LDS rounded to 16 bit and C is still rounded before the LayerNorm, so ln_out has the bits of the keeping
+ *   form.  It needs the forward form (bias1, ReLU, no gate, no gate_bits_in), ln_out, and no gate_bits_out; ln_stats is not
+ *   written; ldh / ldc are not read.  One of H and C alone is refused, as is every other partial combination, before any launch.
  * ------------------------------------------------------------------------------------------- */
 typedef struct eg_ffn_desc {
   const void* A;        /* [M, 256], row stride lda */
   const void* W1;       /* [F, 256] in fragment order: eg_pack_table mode 3 (or 4 from the transposed parameter) */
   const void* W2;       /* [256, F] in fragment order: eg_pack_table mode 5 (or 6) */
-  void* H;              /* [M, F], row stride ldh */
-  void* C;              /* [M, 256], row stride ldc */
+  void* H;              /* [M, F], row stride ldh; NULL together with C: the lean form */
+  void* C;              /* [M, 256], row stride ldc; NULL together with H */
   const float* bias1;   /* [F] or NULL */
   const float* bias2;   /* [256] or NULL */
   const void* gate;     /* [M, F], row stride ldg, or NULL */
@@ -257,6 +261,9 @@ int eg_ln_bwd_proj_blocks(int M);   /* rows of `partial` a launch over M rows wr
  *   Bit-identical to eg_gemm_nt (q|k|v) -> eg_attention_fwd (kv_shift 0) -> eg_gemm_nt (out-proj, drop1 = out_drop, residual x).
  *   16-bit dtypes, d_model == 256, 8 heads; rows contiguous (stride 256 / 768).  Weights in fragment order: wqkv_frag by three
  *   eg_pack_table entries of mode 7 (ldd = 0, 1, 2 for q_proj, k_proj, v_proj, same dst), wo_frag by one entry of mode 8.
+ *   LEAN form (a forward that nobody differentiates): qkv, ctx, lse and r1 ALL NULL.  Then ln_out is required and is the launch's
+ *   only result (same bits as the keeping form's: r1 is still rounded to 16 bit before the LayerNorm); ln_stats may be NULL and
+ *   is not written.  Some but not all of the four NULL is refused before any launch.
  * ------------------------------------------------------------------------------------------- */
 typedef struct eg_attn_block_desc {
   const void* x;          /* [NB*S, 256] */
@@ -264,7 +271,7 @@ typedef struct eg_attn_block_desc {
   const void* wo_frag;    /* 256 x 256 elements, eg_pack_table mode 8 */
   const float* bqkv;      /* [768] = q_proj.bias | k_proj.bias | v_proj.bias */
   const float* bo;        /* [256] */
-  void* qkv;              /* out [NB*S, 768] */
+  void* qkv;              /* out [NB*S, 768]    -- these four: all given, or all NULL (the lean form) */
   void* ctx;              /* out [NB*S, 256] */
   float* lse;             /* out [NB, 8, S] */
   void* r1;               /* out [NB*S, 256] */
@@ -453,6 +460,15 @@ int eg_heads_bwd_pool(const void* z, const void* dcomb, const void* dzf, const f
                       int S, int D, int off, int n_ibs, int ibs_first, int dtype, void* stream);
 int eg_token_grad_tail(const void* dseq, const void* gate, void* dst, eg_rowmap dmap, float* pos_grad, float* cls_grad, int NB,
                        int S, int D, int R, int off, float gate_scale, int dtype, void* stream);
+
+/* eg_eval_accumulate — the per-batch tail of an evaluation loop (T:258-314) on the device, one launch of one workgroup:
+ *   pred[b] = argmax_c logits[b][c] (lowest index on ties, as torch.argmax on finite values);
+ *   confusion[labels[b]][pred[b]] += 1 (row-major [ncls][ncls]; NULL = no matrix; a label outside [0, ncls) counts nowhere);
+ *   *loss_sum += *loss (either NULL = no sum).
+ * confusion and loss_sum are read-modify-written with plain loads and stores: zero them once, then issue every batch's call on one
+ * stream and read them after the last.  1 <= ncls <= 16, B > 0; a confusion matrix needs labels. */
+int eg_eval_accumulate(const float* logits, const int64_t* labels, const float* loss, int32_t* pred, int32_t* confusion,
+                       float* loss_sum, int B, int ncls, void* stream);
 
 /* Batch-level auxiliary losses (3_Models/backbones/dual_eeg_transformer.py:1255-1371), fp32, each with the gradient of the
  * loss w.r.t. the [B, D] tokens it reads (upstream gradient 1; the caller scales).  B <= 1024.
