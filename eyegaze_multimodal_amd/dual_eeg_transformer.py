@@ -249,42 +249,39 @@ class DualEEGTransformer(nn.Module):
         self._op_handle = ops.register_owner(self)     # the registered operators (ops.py) find this module by handle
 
     # ------------------------------------------------------------------------------------------
-    def engine(self, B: int, T: int, device: torch.device) -> Engine:
+    def _pooled_engine(self, pool: dict, B: int, T: int, device, need_grad: bool, make):
+        """The engine of `pool` for this batch shape, keyed (B, T, device, dtype); make(device) builds a missing one.  A pool holds
+        at most four: the workspace of rarely used shapes is let go, oldest first."""
         L.lib()  # raises when the HIP library is missing
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:      # "cuda" and "cuda:0" must name ONE engine and ONE step state
             device = torch.device("cuda", torch.cuda.current_device())
-        self._flat.ensure(device)
+        self._flat.ensure(device, need_grad=need_grad)
         key = (B, T, str(device), self._dtype)
-        eng = self._engines.get(key)
+        eng = pool.get(key)
         if eng is None:
-            if len(self._engines) >= 4:  # bound the workspace held for rarely used shapes
-                self._engines.pop(next(iter(self._engines)))
+            if len(pool) >= 4:
+                pool.pop(next(iter(pool)))
+            eng = pool[key] = make(device)
+        return eng
+
+    def engine(self, B: int, T: int, device: torch.device) -> Engine:
+        def make(device):
             eng = Engine(self, B, T, device, self._dtype, state_dev=self._state_for(device))
             if not self._state_ready.get(str(device)):
                 # first engine on this device: it owns the initialisation of the shared step state (loss scaling on for fp16)
                 eng.set_state(seed=0, lr=0.0, step=1, grad_scale=1.0, reset_scaler=(1 if eng.scaler_on else 2),
                               init_scale=eng.scaler_cfg["init_scale"])
                 self._state_ready[str(device)] = True
-            self._engines[key] = eng
-        return eng
+            return eng
+        return self._pooled_engine(self._engines, B, T, device, True, make)
 
     def inference_engine(self, B: int, T: int, device: torch.device) -> InferenceEngine:
-        """The forward-only engine of predict() for this batch shape, from a pool of its own (bounded like the training pool, keyed
-        (B, T, device, dtype)).  It shares nothing with the training engines but the flat parameter buffer: no step state, no
-        gradient buffer, no forward counter."""
-        L.lib()
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self._flat.ensure(device, need_grad=False)
-        key = (B, T, str(device), self._dtype)
-        eng = self._infer_engines.get(key)
-        if eng is None:
-            if len(self._infer_engines) >= 4:
-                self._infer_engines.pop(next(iter(self._infer_engines)))
-            eng = self._infer_engines[key] = InferenceEngine(self, B, T, device, self._dtype)
-        return eng
+        """The forward-only engine of predict() for this batch shape, from a pool of its own (it never evicts a training engine).
+        It shares nothing with the training engines but the flat parameter buffer: no step state, no gradient buffer, no forward
+        counter."""
+        return self._pooled_engine(self._infer_engines, B, T, device, False,
+                                   lambda device: InferenceEngine(self, B, T, device, self._dtype))
 
     def _state_for(self, device: torch.device) -> torch.Tensor:
         """ONE eg_step_state per (model, device), shared by the engines of every batch shape: the tail batch of an epoch steps
@@ -298,13 +295,8 @@ class DualEEGTransformer(nn.Module):
             self._state_ready[key] = False
         return st
 
-    def _run_forward(self, eng: Engine, eeg1, eeg2, labels, train: Optional[bool] = None) -> Dict[str, torch.Tensor]:
-        train = self.training if train is None else train
-        self._fwd_count += 1
-        if train:
-            eng.set_state(seed=self._seed_base * 1000003 + self._fwd_count, lr=0.0, step=1)
-        eng.forward(eeg1, eeg2, labels, train=train)
-        a = eng.a
+    def _outputs(self, a: Dict[str, torch.Tensor], labels) -> Dict[str, torch.Tensor]:
+        """copies of an engine's results under the reference's keys (the losses only when labels were given)"""
         out = {"logits": a["logits"].clone(), "cls1": a["cls1"].clone(), "cls2": a["cls2"].clone()}
         if self.cfg.use_ibs:
             out["ibs_logits"] = a["ibs_logits"].clone()
@@ -314,6 +306,14 @@ class DualEEGTransformer(nn.Module):
             if self.cfg.use_ibs:
                 out["loss_ibs_cls"] = a["ibs_loss"].clone().reshape(())
         return out
+
+    def _run_forward(self, eng: Engine, eeg1, eeg2, labels, train: Optional[bool] = None) -> Dict[str, torch.Tensor]:
+        train = self.training if train is None else train
+        self._fwd_count += 1
+        if train:
+            eng.set_state(seed=self._seed_base * 1000003 + self._fwd_count, lr=0.0, step=1)
+        eng.forward(eeg1, eeg2, labels, train=train)
+        return self._outputs(eng.a, labels)
 
     def _check_windows(self, eeg1, eeg2, labels):
         if not eeg1.is_cuda:
@@ -329,16 +329,7 @@ class DualEEGTransformer(nn.Module):
         """predict()'s body behind eyegaze::dual_eeg_predict: the inference engine's forward and copies of its results"""
         eng = self.inference_engine(eeg1.shape[0], eeg1.shape[2], eeg1.device)
         eng.forward(eeg1, eeg2, labels, pack=pack)
-        a = eng.a
-        out = {"logits": a["logits"].clone(), "cls1": a["cls1"].clone(), "cls2": a["cls2"].clone()}
-        if self.cfg.use_ibs:
-            out["ibs_logits"] = a["ibs_logits"].clone()
-            out["ibs_token"] = a["ibs_pool_f"].clone()
-        if labels is not None:
-            out["loss_ce"] = a["loss"].clone().reshape(())
-            if self.cfg.use_ibs:
-                out["loss_ibs_cls"] = a["ibs_loss"].clone().reshape(())
-        return out
+        return self._outputs(eng.a, labels)
 
     @torch.no_grad()
     def predict(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None) -> dict:
@@ -384,15 +375,7 @@ class DualEEGTransformer(nn.Module):
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None) -> dict:
         """eeg1, eeg2: f32 [B, C, T] on a HIP device; labels: i64 [B] or None.  Returns the reference's dict
         (D:1232-1253): logits, cls1, cls2 (+ ibs_logits, ibs_token) (+ loss, loss_ce, loss_ibs_cls)."""
-        if not eeg1.is_cuda:
-            raise L.EgError("DualEEGTransformer (HIP) needs device tensors; there is no CPU fallback "
-                            "(the CPU restatement lives in oracle/ and is test infrastructure)")
-        if eeg1.shape != eeg2.shape or eeg1.dim() != 3 or eeg1.shape[1] != self.cfg.in_channels:
-            raise L.EgError(f"expected two [B, {self.cfg.in_channels}, T] windows, got {tuple(eeg1.shape)} / {tuple(eeg2.shape)}")
-        if labels is not None:
-            labels = labels.to(device=eeg1.device, dtype=torch.int64).contiguous()
-        eeg1, eeg2 = eeg1.contiguous().float(), eeg2.contiguous().float()
-        eng = self.engine(eeg1.shape[0], eeg1.shape[2], eeg1.device)
+        eeg1, eeg2, labels = self._check_windows(eeg1, eeg2, labels)
         # The whole forward is ONE registered operator, eyegaze::dual_eeg_forward (ops.py); its autograd formula is the HIP
         # backward.  Analysis code (Grad-CAM) freezes the parameters and marks the INPUTS instead: the HIP path has no gradient
         # w.r.t. the raw windows (the reference never trains through them either), their .grad stays None, but the backward

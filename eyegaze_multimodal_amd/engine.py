@@ -9,11 +9,22 @@ Data layout in HBM (NB = 2B windows: stream 1 = samples [0,B), stream 2 = [B,2B)
   qkv_l   [M, 3d]  ctx_l [M, d]  r1/r2 (pre-LN sums) [M, d]  hff_l [M, d_ff]                   compute dtype
   lse_l   [NB, H, S]  LN stats [M, 2]  logits / losses                                          fp32
   parameters, gradients, AdamW moments: ONE flat fp32 buffer each (16-B aligned segments, registration order)
+
+What is stated once here:
+  geometry()        the front end's and the sequence's row / column counts for (cfg, T, dtype), device-free
+  LAYOUTS           every packed weight layout: shape, pack operation, source, and the direction and route that read it
+  EngineBase        device / dtype fields, step state, timed launches, gemm / wgrad, the pack table (also ImageEngine's base)
+  ForwardEngine     the encoder forward: routes, allocation and pack recording from LAYOUTS, the launches, ONE forward body that
+                    asks the engine where each stage's rows go (_rows)
+  Engine            training: per-layer saved activations, the backward in stages, accumulation, the optimiser
+  InferenceEngine   forward only: a ping-pong pair + scratch on demand, the forward-reading layouts, the training calls refused
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+from collections import namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -43,6 +54,11 @@ def _layer_sites(l: int):
     return dict(attn=b, drop1=b + 1, ffn_a=b + 2, ffn_b=b + 3, drop2=b + 4)
 
 
+def _attn_prefix(l) -> str:
+    """parameter prefix of attention stage l: an encoder layer's index, or "x" for the cross-attention block"""
+    return "cross_attn.cross_attn." if l == "x" else f"encoder.layers.{l}.mha."
+
+
 def _align(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
@@ -51,17 +67,39 @@ ATTN_SHORT_MAX_S = 160      # eg_attention_fwd / _bwd / _probs: a whole window's
 ATTN_LONG_MAX_S = 2048      # eg_attention_long_*: flash-style tiles (csrc/attention_long.hip, EG_ATTN_LONG_MAX_S)
 
 
+# Row and column counts of the front end and the token sequence for one (cfg, T, dtype), from geometry():
+#   k, s, pad   convolution kernel, stride, padding          Cp      input channels, padded to 8
+#   T1, T2      conv-0 / conv-1 output rows per window       J       tap blocks per stride phase of conv-1's backward-data
+#   K0          conv-0 GEMM depth (zero-padded to the K-tile)  Tp    padded input rows per window
+#   U           backward-data rows per phase                 R0      padded conv-0 output rows per window (U * s)
+#   RY          padded dY rows per window (backward-data)    off     first temporal token row: 1 (CLS) + IBS + spectrogram tokens
+#   S           tokens per window
+Geometry = namedtuple("Geometry", "k s pad Cp T1 T2 J K0 Tp U R0 RY off S")
+
+
+def geometry(cfg, T: int, dtype: int = EG_BF16) -> Geometry:
+    """The one statement of the front end's arithmetic; needs no device and checks nothing (sequence_length does).  The dtype only
+    sets the GEMM K-tile behind K0 and Tp."""
+    k, s = cfg.conv_kernel_size, cfg.conv_stride
+    pad, Cp = k // 2, _align(cfg.in_channels, 8)
+    T1 = (T + 2 * pad - k) // s + 1
+    T2 = (T1 + 2 * pad - k) // s + 1
+    J = (k + s - 1) // s
+    K0 = _align(k * Cp, 32 if dtype == EG_F32 else 64)
+    U = (T1 + 2 * pad + s - 1) // s
+    off = 1 + cfg.num_ibs_tokens + (cfg.in_channels if cfg.use_spectrogram else 0)
+    return Geometry(k, s, pad, Cp, T1, T2, J, K0, _align(max(T + 2 * pad, s * (T1 - 1) + K0 // Cp + 1), 8), U, U * s,
+                    T2 + 2 * (J - 1), off, off + T2)
+
+
 def sequence_length(cfg, T: int) -> int:
     """Token count S = 1 (CLS) + IBS tokens + spectrogram tokens + T2 of a model config at window length T, after the checks
     that need no device: S within the positional table and the attention core's limit, and (with IBS) 64 <= T <= 2048, the
     synchrony kernels' range.  Raises EgError naming the limit that fails."""
-    k, s = cfg.conv_kernel_size, cfg.conv_stride
-    pad = k // 2
-    T1 = (T + 2 * pad - k) // s + 1
-    T2 = (T1 + 2 * pad - k) // s + 1
-    if T2 < 1:
+    geo = geometry(cfg, T)
+    s, S = geo.s, geo.S
+    if geo.T2 < 1:
         raise L.EgError(f"window length {T} is too short for the two stride-{s} convolutions")
-    S = 1 + cfg.num_ibs_tokens + (cfg.in_channels if cfg.use_spectrogram else 0) + T2
     if S > cfg.max_len:
         raise L.EgError(f"sequence length {S} exceeds max_len {cfg.max_len} of the positional table")
     if S > ATTN_LONG_MAX_S:
@@ -187,7 +225,7 @@ class EngineBase:
         # the recorded pack table (pack_params)
         self._recording, self._plan, self._plan_ex = False, [], False
         self._plan_key, self._plan_dev, self._plan_n, self._plan_blocks = None, None, 0, 0
-        # the routes pack_params keys its table on.  Off here: an engine that has them resolves them (Engine._resolve_routes)
+        # the routes pack_params keys its table on.  Off here: an engine that has them resolves them (_resolve_routes)
         self.fused_tail = self.pack_unused = False
         self.fuse_ffn = self.attn_block = self.ln_proj = False
 
@@ -478,57 +516,125 @@ class EngineBase:
              self.stream)
 
 
-class Engine(EngineBase):
-    """Workspace + kernel sequencing for a fixed (B, T) shape."""
-    LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
-    SQ_BLOCKS = 1024              # squared-norm partials of the flat gradient buffer (g["sqpart"]) that eg_clip_coef sums
-    GROUP_MIN_ROWS = 4096         # token rows below which the per-product weight-gradient launches (many splits) are the better shape
-    tn_cap = 24 * 1024 * 1024     # floats (96 MB) of TN split-K partials: sized for the largest product (conv-1 weights / FFN)
+# ------------------------------------------------------------------------------------------------
+# packed weight layouts of the EEG engines: the one declaration that allocation and pack recording are derived from
+# ------------------------------------------------------------------------------------------------
+# w[key + stage]: one packed form of a parameter (or, with several sources, of the parameters that share the buffer)
+#   shape   (d, F, engine) -> shape of the buffer; fp32 for "copy", else the compute dtype
+#   op      cast | copy | transpose | frag | conv | convT: the p_* operation that fills it
+#   args    (d, F, engine) -> that operation's arguments behind (src, dst), for one source
+#   src     parameter names under the stage's prefix; part i of the buffer comes from src[i]
+#   bwd     read by the backward; else by the forward
+#   route   the route attribute that decides whether anything reads it (None: always read) ...
+#   fused   ... namely when that route is on (True) or off (False)
+Layout = namedtuple("Layout", "key shape op args src bwd route fused", defaults=(False, None, False))
+
+
+def _lay(key, shape, op, args, *src, **kw):
+    return Layout(key, shape, op, args, src, **kw)
+
+
+_QKV = ("q_proj.weight", "k_proj.weight", "v_proj.weight")
+_BLOCK, _LNPROJ, _FFN = "attn_block", "ln_proj", "fuse_ffn"
+# stage -> groups in recording order; the layouts of one group are recorded source by source (q: each of them, k: each of them, ...).
+# "attn" is recorded per encoder layer and for the cross-attention block "x", which has no fused route; "ffn" per encoder layer.
+LAYOUTS = {
+    "front": [
+        (_lay("conv0", lambda d, F, e: (d, e.K0), "conv", lambda d, F, e: (d, e.C, e.k, e.Cp, e.K0), "temporal_conv.convs.0.weight"),),
+        (_lay("conv1", lambda d, F, e: (d, e.k * d), "conv", lambda d, F, e: (d, d, e.k, d, e.k * d), "temporal_conv.convs.1.weight"),),
+        (_lay("conv1T", lambda d, F, e: (e.s, d, e.J * d), "convT", lambda d, F, e: (d, d, e.k, e.s), "temporal_conv.convs.1.weight",
+              bwd=True),),
+        (_lay("pos", lambda d, F, e: (e.cfg.max_len, d), "cast", lambda d, F, e: (e.cfg.max_len * d,), "pos_embed.pos_embed.weight"),)],
+    "attn": [
+        (_lay("qkv", lambda d, F, e: (3 * d, d), "cast", lambda d, F, e: (d * d,), *_QKV, route=_BLOCK),
+         _lay("qkvT", lambda d, F, e: (d, 3 * d), "transpose", lambda d, F, e: (d, d), *_QKV, bwd=True),
+         _lay("bqkv", lambda d, F, e: (3 * d,), "copy", lambda d, F, e: (d,), "q_proj.bias", "k_proj.bias", "v_proj.bias")),
+        (_lay("o", lambda d, F, e: (d, d), "cast", lambda d, F, e: (d * d,), "out_proj.weight", route=_BLOCK),),
+        (_lay("oT", lambda d, F, e: (d, d), "transpose", lambda d, F, e: (d, d), "out_proj.weight", bwd=True, route=_LNPROJ),),
+        # out_proj^T in MFMA-fragment order (eg_pack_table mode 6) for eg_ln_bwd_proj
+        (_lay("oTf", lambda d, F, e: (d * d,), "frag", lambda d, F, e: (d, d, 6), "out_proj.weight", bwd=True, route=_LNPROJ, fused=True),),
+        # eg_attn_block_fwd's fragment-ordered q|k|v (mode 7, part = source index) and out-proj (mode 8) weights
+        (_lay("wqkvb", lambda d, F, e: (3 * d * d,), "frag", lambda d, F, e: (d, d, 7), *_QKV, route=_BLOCK, fused=True),),
+        (_lay("wob", lambda d, F, e: (d * d,), "frag", lambda d, F, e: (d, d, 8), "out_proj.weight", route=_BLOCK, fused=True),)],
+    "ffn": [
+        (_lay("w1", lambda d, F, e: (F, d), "cast", lambda d, F, e: (F * d,), "linear1.weight", route=_FFN),),
+        (_lay("w1T", lambda d, F, e: (d, F), "transpose", lambda d, F, e: (F, d), "linear1.weight", bwd=True, route=_FFN),),
+        (_lay("w2", lambda d, F, e: (d, F), "cast", lambda d, F, e: (d * F,), "linear2.weight", route=_FFN),),
+        (_lay("w2T", lambda d, F, e: (F, d), "transpose", lambda d, F, e: (d, F), "linear2.weight", bwd=True, route=_FFN),),
+        # the same four matrices in eg_ffn_chain's MFMA-fragment order (modes 3-6): forward products 1, 2; backward product
+        # 1 = linear2^T, 2 = linear1^T
+        (_lay("w1f", lambda d, F, e: (F * d,), "frag", lambda d, F, e: (F, d, 3), "linear1.weight", route=_FFN, fused=True),),
+        (_lay("w2f", lambda d, F, e: (F * d,), "frag", lambda d, F, e: (d, F, 5), "linear2.weight", route=_FFN, fused=True),),
+        (_lay("w2Tf", lambda d, F, e: (F * d,), "frag", lambda d, F, e: (d, F, 4), "linear2.weight", bwd=True, route=_FFN, fused=True),),
+        (_lay("w1Tf", lambda d, F, e: (F * d,), "frag", lambda d, F, e: (F, d, 6), "linear1.weight", bwd=True, route=_FFN, fused=True),)],
+    "heads": [
+        (_lay("sf", lambda d, F, e: (d, 3 * d), "cast", lambda d, F, e: (3 * d * d,), "symmetric_fusion.proj.weight"),),
+        (_lay("sfT", lambda d, F, e: (3 * d, d), "transpose", lambda d, F, e: (d, 3 * d), "symmetric_fusion.proj.weight", bwd=True),),
+        (_lay("c0", lambda d, F, e: (d, 3 * d), "cast", lambda d, F, e: (3 * d * d,), "classifier.0.weight"),),
+        (_lay("c0T", lambda d, F, e: (3 * d, d), "transpose", lambda d, F, e: (d, 3 * d), "classifier.0.weight", bwd=True),)],
+    "ibs": [
+        (_lay("i0", lambda d, F, e: (d // 2, d), "cast", lambda d, F, e: ((d // 2) * d,), "ibs_classifier.0.weight"),),
+        (_lay("i0T", lambda d, F, e: (d, _align(d // 2, e.bk)), "transpose", lambda d, F, e: (d // 2, d), "ibs_classifier.0.weight",
+              bwd=True),)],
+}
+_ALL_LAYOUTS = [lay for groups in LAYOUTS.values() for group in groups for lay in group]
+# forward layout of an unfused route -> the fragment-ordered layout of the same parameters that the fused route reads instead
+_FUSED_TWIN = {u.key: f for u in _ALL_LAYOUTS for f in _ALL_LAYOUTS
+               if u.route and not (u.bwd or f.bwd or u.fused) and (f.route, f.src, f.fused) == (u.route, u.src, True)}
+
+
+# Where one encoder stage's rows go, as the engine answers ForwardEngine._rows; None = not stored (the lean launches).
+#   qkv, lse, ctx   q|k|v rows, log-sum-exps, context rows          r1, st1, y1   pre-LN sum, statistics and output rows of norm1
+#   hff, gbits      hidden rows and their gate bits (an engine without them runs at p = 0)
+#   r2, st2         pre-LN sum and statistics of norm2              out           the stage's output rows
+# The cross-attention stage "x" fills the attention half and `out` (its normed rows); the final norm "norm" only st2 and out.
+Rows = namedtuple("Rows", "qkv lse ctx r1 st1 y1 hff gbits r2 st2 out", defaults=(None,) * 11)
+
+
+def _head_tensors(cfg, B: int):
+    """{name: (shape, is fp32)} of what the heads write (compute dtype unless fp32), device-free"""
+    d, nc = cfg.d_model, cfg.num_classes
+    t = {"cls1": ((B, d), True), "cls2": ((B, d), True), "comb": ((B, 3 * d), False), "zf": ((B, 3 * d), False), "hcl": ((B, d), False),
+         "logits": ((B, nc), True), "sloss": ((B,), True), "loss": ((1,), True)}
+    if cfg.use_ibs:
+        t.update({"ibs_pool_f": ((B, d), True), "ibs_pool": ((B, d), False), "hib": ((B, d // 2), False),
+                  "ibs_logits": ((B, nc), True), "ibs_sloss": ((B,), True), "ibs_loss": ((1,), True)})
+    return t
+
+
+class ForwardEngine(EngineBase):
+    """The encoder forward for a fixed (B, T), shared by the training and the inference engine: geometry, forward routes, the packed
+    layouts (LAYOUTS), the launches of the front end, an encoder layer, the cross-attention stage and the heads, and ONE forward
+    body.  A subclass allocates `a` (_alloc), says which layouts it holds (_held) and where each stage's rows go (_rows)."""
 
     def __init__(self, model, B: int, T: int, device: torch.device, dtype: int, state_dev: Optional[torch.Tensor] = None):
         """state_dev: the model's shared eg_step_state (see _init_state)"""
         super().__init__(model, B, device, dtype)
         cfg = model.cfg
         self.cfg, self.T = cfg, T
-        d = cfg.d_model
         self.head_dim = attention_head_dim(cfg)
         if cfg.conv_layers != 2:
             raise L.EgError("HIP path implements the reference's 2-layer temporal conv front-end (conv_layers=2)")
-        if d % 64 != 0 or cfg.d_ff % 64 != 0:
+        if cfg.d_model % 64 != 0 or cfg.d_ff % 64 != 0:
             raise L.EgError("d_model and d_ff must be multiples of 64")
-        k, s = cfg.conv_kernel_size, cfg.conv_stride
-        pad = k // 2
-        self.k, self.s, self.pad = k, s, pad
-        self.NB = 2 * B
-        self.C = cfg.in_channels
-        self.Cp = _align(self.C, 8)
-        self.T1 = (T + 2 * pad - k) // s + 1
-        self.T2 = (self.T1 + 2 * pad - k) // s + 1
-        self.J = (k + s - 1) // s
-        self.K0 = _align(k * self.Cp, self.bk)                    # conv-0 GEMM depth (zero-padded)
-        self.Tp = _align(max(T + 2 * pad, s * (self.T1 - 1) + self.K0 // self.Cp + 1), 8)
-        self.U = (self.T1 + 2 * pad + s - 1) // s                   # backward-data rows per phase
-        self.R0 = self.U * s                                        # padded conv-0 output rows per window
-        self.RY = self.T2 + 2 * (self.J - 1)                        # padded dY rows per window (backward-data)
+        self.NB, self.C = 2 * B, cfg.in_channels
+        self.geo = geometry(cfg, T, dtype)
+        for name, v in self.geo._asdict().items():      # k, s, pad, Cp, T1, T2, J, K0, Tp, U, R0, RY, off, S as plain attributes
+            setattr(self, name, v)
         self.n_ibs = cfg.num_ibs_tokens
         self.n_spec = self.C if cfg.use_spectrogram else 0
-        self.off = 1 + self.n_ibs + self.n_spec
-        self.S = sequence_length(cfg, T)
+        sequence_length(cfg, T)                         # its checks
         self.M = self.NB * self.S
         self._resolve_routes()
-        self._wg_key = self._wg_plan = None     # the grouped weight-gradient plan and the gradient buffer it was made for
-        self._wg_cross, self._ln_slot = False, {}
-        self._ranges_key = None
-        self._acc_norm_ready = False   # g["sqpart"] holds the norm partials of the whole accumulator (accumulate(norm=True))
         self._alloc()
         self._init_state(state_dev)
 
     def _resolve_routes(self):
-        """Every route of the step, decided once from the compute dtype, the shapes and the surviving switches; nothing else in
-        this module reads the environment (but _wgrad_pieces).  Tests assign the plain attributes on a live engine."""
+        """Every route of the forward, decided once from the compute dtype, the shapes and the surviving switches; nothing else in
+        this module reads the environment (but Engine._resolve_routes for the backward's, and _wgrad_pieces).  Tests assign the plain
+        attributes on a live engine."""
         cfg, dtype, env = self.cfg, self.dtype, os.environ
         half = dtype != EG_F32
-        self.scaler_on = dtype == EG_F16 and env.get("EYEGAZE_LOSS_SCALING", "1") != "0"
         # S > 160: the long-sequence attention core (eg_attention_long_*) at all four call sites; S <= 160 keeps the short one
         # 64-wide heads: the same core through eg_attention_dk_* at EVERY S (the short core and the fused block are 32 wide only)
         wide = self.head_dim != 32
@@ -541,201 +647,70 @@ class Engine(EngineBase):
                                and L.lib().eg_attn_block_ok(self.S, cfg.d_model, cfg.num_heads, dtype))
         # feed-forward pair as one launch (csrc/ffn.hip): 16-bit compute dtypes, d_model == 256, d_ff a multiple of 128
         self.fuse_ffn = half and cfg.d_model == 256 and cfg.d_ff % 128 == 0
-        # LayerNorm backward: a block walks 8 rows per trip with TWO trips in flight (112 registers: four 256-thread blocks per CU).
-        # All blocks must be resident at once -- a late block starts when an early one ends and doubles the launch -- so at most
-        # 4 blocks per CU: 33 280 rows = 1024 blocks x 4.06 trips (round 2: 1040 x 4 with one trip in flight)
-        env_nb = env.get("EYEGAZE_LN_BLOCKS")
-        trips = max(1, self.M // 8192)
-        self.LN_BLOCKS = int(env_nb) if env_nb else min(self.LN_PARTIAL_BLOCKS, 4 * self.cus,
-                                                        max(1, (self.M + 8 * trips - 1) // (8 * trips)))
-        if not 1 <= self.LN_BLOCKS <= self.LN_PARTIAL_BLOCKS:
-            # round 2: a sweep at 2080 blocks stored past the 2048-row partial buffer (GPU memory access fault); refuse, never clamp
-            raise L.EgError(f"EYEGAZE_LN_BLOCKS={env_nb} is outside [1, {self.LN_PARTIAL_BLOCKS}] (rows of the LayerNorm-backward "
-                            "partial buffer)")
-        self.ln_nblk_cap = max(self.LN_BLOCKS, (self.M + 63) // 64)
         # the two LayerNorms of an encoder layer as the tail of the launches that complete their input rows (eg_attn_block_fwd ->
         # norm1, eg_ffn_chain forward -> norm2) instead of two launches that re-read them; the statistics are summed in another order
         # than eg_layernorm_fwd's, so the step agrees with EYEGAZE_LN_FUSE=0 to rounding, not bit for bit
         self.ln_fuse = env.get("EYEGAZE_LN_FUSE", "1") != "0"
-        # norm1's backward and out_proj's backward-data product as one launch over 80-row tiles (eg_ln_bwd_proj): bit-identical to the
-        # two launches (the gain / bias partials are grouped by tile instead of by LayerNorm block: equal to fp32 rounding)
-        self.ln_proj = half and cfg.d_model == 256
-        self.ln_proj_blocks = L.lib().eg_ln_bwd_proj_blocks(self.M) if self.ln_proj else 0
         # the step's small-launch tail on its fused kernels (16-bit compute dtypes): the convolution weight layouts inside the
         # one table-driven pack launch, the heads' forward as pooling + ONE chained launch, their backward as three, and the
         # position / cls / conv-1 gradient rows from ONE pass over dseq.  Same bits as the separate launches, which remain the
         # route for fp32 and for the shapes the fused kernels do not cover (see _fused_heads); tests set this attribute to
         # False to compare the two routes.
         self.fused_tail = half
-        # False: pack_params skips the layouts that the routes chosen above never read (see _pack_body); True packs every one
+        # False: pack_params skips the layouts that the routes chosen above never read (see _held); True packs every one
         self.pack_unused = False
-        # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
-        # instead of eg_grad_sqnorm + eg_clip_coef.  Off by default: tests/test_gpu_accum.py counts the trainer's eg_grad_sqnorm calls
-        self.fused_norm_clip = False
-        # conv-1 backward-data as one batched launch over the real rows and the non-zero taps (conv1_bwd_data); False, or
-        # EYEGAZE_CONV1_BWD_BATCH=0, keeps one full launch per stride phase
-        self.conv1_bwd_batch = env.get("EYEGAZE_CONV1_BWD_BATCH", "1") != "0"
 
-    def _alloc(self):
-        cfg, d, F, L_ = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_layers
-        NB, M, S, H, B = self.NB, self.M, self.S, self.cfg.num_heads, self.B
-        f32 = torch.float32
-        w = {}
-        # packed parameters (compute dtype)
-        w["conv0"] = self._t(d, self.K0)
-        w["conv1"] = self._t(d, self.k * d)
-        w["conv1T"] = self._t(self.s, d, self.J * d)
-        w["pos"] = self._t(cfg.max_len, d)
-        for l in list(range(L_)) + (["x"] if cfg.use_cross_attention else []):
-            w[f"qkv{l}"] = self._t(3 * d, d)
-            w[f"qkvT{l}"] = self._t(d, 3 * d)
-            w[f"o{l}"] = self._t(d, d)
-            w[f"oT{l}"] = self._t(d, d)
-            w[f"bqkv{l}"] = self._t(3 * d, dtype=f32)
-            if self.ln_proj and l != "x":             # out_proj^T in MFMA-fragment order (eg_pack_table mode 6) for eg_ln_bwd_proj
-                w[f"oTf{l}"] = self._t(d * d)
-            if self.attn_block and l != "x":          # eg_attn_block_fwd's fragment-ordered q|k|v and out-proj weights
-                w[f"wqkvb{l}"] = self._t(3 * d * d)
-                w[f"wob{l}"] = self._t(d * d)
-            if l != "x":
-                w[f"w1{l}"] = self._t(F, d)
-                w[f"w1T{l}"] = self._t(d, F)
-                w[f"w2{l}"] = self._t(d, F)
-                w[f"w2T{l}"] = self._t(F, d)
-                if self.fuse_ffn:       # the same four matrices in eg_ffn_chain's MFMA-fragment order (eg_pack_table modes 3-6)
-                    for nm in ("w1f", "w2f", "w2Tf", "w1Tf"):
-                        w[f"{nm}{l}"] = self._t(F * d)
-        w["sf"] = self._t(d, 3 * d)
-        w["sfT"] = self._t(3 * d, d)
-        w["c0"] = self._t(d, 3 * d)
-        w["c0T"] = self._t(3 * d, d)
-        if cfg.use_ibs:
-            w["i0"] = self._t(d // 2, d)
-            w["i0T"] = self._t(d, _align(d // 2, self.bk))
-        self.w = w
-        a = {}
-        a["xt"] = self._t(NB, self.Tp, self.Cp)
-        a["h0pad"] = self._t(NB, self.R0, d)
-        a["h1"] = self._t(NB * self.T2, d)
-        a["x0"] = self._t(M, d)
-        for l in range(L_):
-            a[f"qkv{l}"] = self._t(M, 3 * d)
-            a[f"lse{l}"] = self._t(NB, H, S, dtype=f32)
-            a[f"ctx{l}"] = self._t(M, d)
-            a[f"r1_{l}"] = self._t(M, d)
-            a[f"st1_{l}"] = self._t(M, 2, dtype=f32)
-            a[f"y1_{l}"] = self._t(M, d)
-            a[f"hff{l}"] = self._t(M, F)
-            if self.fuse_ffn:           # ReLU / dropout gate of the hidden rows, one bit per element (forward -> backward)
-                a[f"gbits{l}"] = torch.zeros(L.gate_bits_bytes(M, F) // 8, device=self.device, dtype=torch.int64)
-            a[f"r2_{l}"] = self._t(M, d)
-            a[f"st2_{l}"] = self._t(M, 2, dtype=f32)
-            a[f"x{l + 1}"] = self._t(M, d)
-        a["stf"] = self._t(M, 2, dtype=f32)
-        a["zn"] = self._t(M, d)
-        if cfg.use_cross_attention:
-            a["qkvx"] = self._t(M, 3 * d)
-            a["lsex"] = self._t(NB, H, S, dtype=f32)
-            a["ctxx"] = self._t(M, d)
-            a["rx"] = self._t(M, d)
-            a["stx"] = self._t(M, 2, dtype=f32)
-            a["zc"] = self._t(M, d)
-        a["cls1"] = self._t(B, d, dtype=f32)
-        a["cls2"] = self._t(B, d, dtype=f32)
-        a["comb"] = self._t(B, 3 * d)
-        a["zf"] = self._t(B, 3 * d)
-        a["hcl"] = self._t(B, d)
-        a["logits"] = self._t(B, cfg.num_classes, dtype=f32)
-        a["sloss"] = self._t(B, dtype=f32)
-        a["loss"] = self._t(1, dtype=f32)
-        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)   # eg_heads_fwd's last-workgroup counter
-        if cfg.use_ibs:
-            a["ibs_pool_f"] = self._t(B, d, dtype=f32)
-            a["ibs_pool"] = self._t(B, d)
-            a["hib"] = self._t(B, d // 2)
-            a["ibs_logits"] = self._t(B, cfg.num_classes, dtype=f32)
-            a["ibs_sloss"] = self._t(B, dtype=f32)
-            a["ibs_loss"] = self._t(1, dtype=f32)
-        self.a = a
+    # ------------------------------------------------------------------------------------------
+    # packed weights: allocation and pack recording, both walks of LAYOUTS
+    # ------------------------------------------------------------------------------------------
+    def _reads(self, lay, l) -> bool:
+        """whether a route chosen NOW reads layout `lay` of stage l (the cross-attention block "x" has no fused route)"""
+        return lay.route is None or (bool(getattr(self, lay.route)) and l != "x") == lay.fused
 
-    def _alloc_bwd(self):
-        if self.g:
-            return
-        d, F, M, B, NB = self.cfg.d_model, self.cfg.d_ff, self.M, self.B, self.NB
-        g = {}
-        for n in ("dzA", "dzB", "dr", "drm", "dctx", "dy1"):
-            g[n] = self._t(M, d)
-        g["dqkv"] = self._t(M, 3 * d)
-        g["dh"] = self._t(M, F)
-        g["dzf"] = self._t(B, 3 * d)
-        g["dcomb"] = self._t(B, 3 * d)
-        g["dhcl"] = self._t(B, d)
-        g["dlogits"] = self._t(B, self.cfg.num_classes, dtype=torch.float32)
+    def _stages(self):
+        """(stage of LAYOUTS, parameter prefix, key suffix) in recording order"""
+        yield "front", "", ""
+        for l in range(self.cfg.num_layers):
+            yield "attn", f"encoder.layers.{l}.mha.", l
+            yield "ffn", f"encoder.layers.{l}.ffn.", l
+        if self.cfg.use_cross_attention:
+            yield "attn", "cross_attn.cross_attn.", "x"
+        yield "heads", "", ""
         if self.cfg.use_ibs:
-            g["dhib"] = self._t(B, d // 2)
-            g["dibs_pool"] = self._t(B, d)
-            g["dibs_logits"] = self._t(B, self.cfg.num_classes, dtype=torch.float32)
-        g["dy1pad"] = self._t(NB, self.RY, d)
-        g["dh0pad"] = self._t(NB, self.R0, d)
-        g["possum"] = self._t(self.S, d, dtype=torch.float32)
-        g["one"] = torch.ones(1, device=self.device, dtype=torch.float32)
-        g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
-        g["lnpart"] = self._t(self.LN_PARTIAL_BLOCKS * 2 * max(d, 8), dtype=torch.float32)
-        g["cspart"] = self._t(512 * max(3 * d, F), dtype=torch.float32)
-        if self.attn_long:          # delta = rowsum(dctx * ctx) of eg_attention_long_bwd, [NB, H, S]
-            g["attn_delta"] = self._t(NB * self.cfg.num_heads * self.S, dtype=torch.float32)
-        self.g = g
+            yield "ibs", "", ""
 
-    def check_overflow_and_update_scaler(self):
-        """autograd path at fp16: flags a non-finite gradient norm (eg_step_state.found_inf) and adapts the internal loss scale,
-        as the native optimiser step does between eg_clip_coef and eg_scaler_update -- without touching parameters."""
-        self._alloc_bwd()
-        self.stream = self._cur_stream()
-        nblk, sq = self.SQ_BLOCKS, ptr(self._sqpart())
-        self._acc_norm_ready = False
-        call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, sq, nblk, self.stream)
-        call("eg_clip_coef", sq, nblk, 0.0, self.st_ptr, self.stream)
-        c = self.scaler_cfg
-        call("eg_scaler_update", self.st_ptr, c["growth"], c["backoff"], c["growth_interval"], self.stream)
+    def _alloc_w(self) -> Dict[str, torch.Tensor]:
+        d, F = self.cfg.d_model, self.cfg.d_ff
+        return {f"{lay.key}{l}": self._t(*lay.shape(d, F, self), dtype=(torch.float32 if lay.op == "copy" else None))
+                for stage, _, l in self._stages() for group in LAYOUTS[stage] for lay in self._held(group, l, True)}
 
-    def conv1_bwd_data(self, sc01, batch=None):
-        """dh0 = conv-1's backward-data (gated by h0 > 0, scaled by sc01): stride phase ph gives rows t = u*s + ph of dh0pad
-        from J taps of dy1pad.
-        batch (default self.conv1_bwd_batch): the phases as ONE eg_gemm_nt_batch call that skips what the result does not
-        need -- the leading tap block of a phase whose tap s*(J-1) + ph lies beyond the kernel (zeros in conv1T) and the rows
-        that fall into dh0pad's pads, which nothing reads (conv-0's weight gradient starts at row `pad`; the buffer is zeroed
-        once, at allocation).  False: one full launch per phase.  The real rows of dh0 are the same bits either way."""
-        d, es, s, J, g, a, w = self.cfg.d_model, self.es, self.s, self.J, self.g, self.a, self.w
-        NB = self.NB
-        if not (self.conv1_bwd_batch if batch is None else batch):
-            for ph in range(s):
-                self.gemm(ptr(g["dy1pad"]), ptr(w["conv1T"]) + ph * d * J * d * es, ptr(g["dh0pad"]) + ph * d * es,
-                          NB * self.U, d, J * d, a=rowmap(d, self.RY * d, self.U), c=rowmap(s * d, self.R0 * d, self.U),
-                          gate=ptr(a["h0pad"]) + ph * d * es, gate_scale=sc01)
-            return
-        items = []
-        for ph, u0, n, j0 in conv_bwd_data_phases(self.k, s, self.pad, self.T1):
-            row = (u0 * s + ph) * d * es
-            items.append(dict(A=ptr(g["dy1pad"]) + (u0 + j0) * d * es, W=ptr(w["conv1T"]) + (ph * d * J * d + j0 * d) * es,
-                              C=ptr(g["dh0pad"]) + row, M=NB * n, N=d, K=(J - j0) * d, ldw=J * d,
-                              a=rowmap(d, self.RY * d, n), c=rowmap(s * d, self.R0 * d, n),
-                              gate=ptr(a["h0pad"]) + row, gate_scale=sc01))
-        for i in range(0, len(items), L.GEMM_BATCH_MAX):
-            self.gemm_batch(items[i:i + L.GEMM_BATCH_MAX])
+    def _pack_body(self):
+        if self._recording or not self._plan_ex:        # (a replayed table that carries the convolutions leaves nothing to do here)
+            d, F, fp = self.cfg.d_model, self.cfg.d_ff, self.fp
+            for stage, pre, l in self._stages():
+                for group in LAYOUTS[stage]:
+                    held = self._held(group, l, bool(self.pack_unused))
+                    for i in range(len(group[0].src)):
+                        for lay in held:
+                            t = self.w[f"{lay.key}{l}"]
+                            src, dst, args = fp.p_ptr(pre + lay.src[i]), ptr(t), lay.args(d, F, self)
+                            # source i: the next args[0] elements (cast, copy) or columns (transpose: ldd = the buffer's width)
+                            # of the buffer; a fragment layout takes the source index as its part
+                            off = 0 if lay.op == "frag" else i * args[0] * t.element_size()
+                            extra = (t.shape[1],) if lay.op == "transpose" else (i,) if lay.op == "frag" else ()
+                            getattr(self, "p_" + lay.op)(src, dst + off, *args, *extra)
+        self.model._pack_extra(self)
 
-    def _attn_stage(self, l):
-        """Attention stage l -- an encoder layer's index, or "x" for the cross-attention block, which is an unfused layer's
-        attention half under other names: (parameter prefix, q|k|v rows, log-sum-exps, context rows, pre-LN sum rows)"""
-        a = self.a
-        if l == "x":
-            return "cross_attn.cross_attn.", a["qkvx"], a["lsex"], a["ctxx"], a["rx"]
-        return f"encoder.layers.{l}.mha.", a[f"qkv{l}"], a[f"lse{l}"], a[f"ctx{l}"], a[f"r1_{l}"]
+    def _head_alloc(self) -> Dict[str, torch.Tensor]:
+        a = {n: self._t(*shape, dtype=(torch.float32 if is32 else None)) for n, (shape, is32) in _head_tensors(self.cfg, self.B).items()}
+        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)   # eg_heads_fwd's last-workgroup counter
+        return a
 
-    def attn_unfused_fwd(self, x, l, kv_shift, sites, p):
+    def attn_unfused_fwd(self, x, l, kv_shift, sites, p, R: Rows):
         """Stage l's forward as three launches: q|k|v = x W^T + b (A:203-205) fused over the three projections (the row-stream
         GEMM at K = 256), the attention core, out-proj + dropout + residual.  kv_shift = B pairs window b with b + B (D:966-974)."""
         M, d = self.M, self.cfg.d_model
-        pre, qkv, lse, ctx, r = self._attn_stage(l)
+        pre, qkv, lse, ctx, r = _attn_prefix(l), R.qkv, R.lse, R.ctx, R.r1
         self.gemm(ptr(x), ptr(self.w[f"qkv{l}"]), ptr(qkv), M, 3 * d, d, bias=ptr(self.w[f"bqkv{l}"]))
         call(self._attn_core + "_fwd", ptr(qkv), ptr(ctx), ptr(lse), self.NB, self.S, *self._attn_heads,
              kv_shift, self.dtype, p, sites["attn"], self.st_ptr, self.stream)
@@ -743,11 +718,11 @@ class Engine(EngineBase):
         self.gemm(ptr(ctx), ptr(self.w[f"o{l}"]), ptr(r), M, d, d, bias=self.fp.p_ptr(pre + "out_proj.bias"),
                   drop1=(p, sites["drop1"]), residual=ptr(x))
 
-    def attn_block_fwd(self, x, l, p, sites, ln=None, lean=False):
+    def attn_block_fwd(self, x, l, p, sites, R: Rows, ln=None):
         """eg_attn_block_fwd (csrc/attnblock.hip): A:202-213 + the residual of A:292-293 for encoder layer l in one launch.
-        lean: the forward-only form -- nothing but ln's rows is stored (no q|k|v, lse, ctx, r1, no statistics)"""
+        R without q|k|v rows: the lean, forward-only form -- nothing but ln's rows is stored (no q|k|v, lse, ctx, r1, no statistics)"""
         w, fp, d = self.w, self.fp, self.cfg.d_model
-        pre, qkv, lse, ctx, r1 = (f"encoder.layers.{l}.mha.", None, None, None, None) if lean else self._attn_stage(l)
+        pre, qkv, lse, ctx, r1, lean = _attn_prefix(l), R.qkv, R.lse, R.ctx, R.r1, R.qkv is None
         dsc = L.AttnBlockDesc()
         dsc.x, dsc.wqkv_frag, dsc.wo_frag = ptr(x), ptr(w[f"wqkvb{l}"]), ptr(w[f"wob{l}"])
         dsc.bqkv, dsc.bo = ptr(w[f"bqkv{l}"]), fp.p_ptr(pre + "out_proj.bias")
@@ -820,6 +795,299 @@ class Engine(EngineBase):
         finally:
             drop_module.training = was
 
+    def ln_fwd(self, x, gname, y, stats):
+        call("eg_layernorm_fwd", ptr(x), self.fp.p_ptr(gname + ".weight"), self.fp.p_ptr(gname + ".bias"), ptr(y),
+             ptr(stats), self.M, self.cfg.d_model, self.dtype, self.stream)
+
+    # ------------------------------------------------------------------------------------------
+    # forward
+    # ------------------------------------------------------------------------------------------
+    def _forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], train: bool, pack: bool = True):
+        """The forward of both engines: pack, front end, layers, final norm, cross stage, heads"""
+        cfg = self.cfg
+        self.stream = self._cur_stream()
+        p = cfg.dropout if train else 0.0
+        p01 = 0.1 if train else 0.0
+        self.train_flags = (p, p01, train)
+        if pack:
+            self.pack_params()
+        x = self._front_end_fwd(eeg1, eeg2, train, p01, self.a.get("h1"))
+        # encoder (A:292-295, 326-328), both streams batched (Siamese weights)
+        for l in range(cfg.num_layers):
+            x = self._layer_fwd(l, x, p)
+        R = self._rows("norm", x)
+        self.ln_fwd(x, "encoder.norm", R.out, R.st2)
+        z = R.out
+        if cfg.use_cross_attention:
+            # D:966-974: both directions in one launch each (kv_shift = B pairs window b with b+B)
+            R = self._rows("x", z)
+            self.attn_unfused_fwd(z, "x", self.B, _layer_sites(cfg.num_layers), p, R)
+            self.ln_fwd(R.r1, "cross_attn.norm", R.out, R.st1)
+            z = R.out
+        self._heads_fwd(z, labels, train, p)
+
+    def _layer_fwd(self, l: int, x, p: float):
+        """Encoder layer l on the rows x, by the routes: fused block or three launches, LayerNorm fused or separate, feed-forward
+        chain or two GEMMs.  Returns the layer's output rows."""
+        M, F, w, fp = self.M, self.cfg.d_ff, self.w, self.fp
+        pre, sites, R = f"encoder.layers.{l}.", _layer_sites(l), self._rows(l, x)
+        if self.attn_block:     # q|k|v projection + attention core + out-proj / dropout / residual: one launch, a workgroup per window
+            self.attn_block_fwd(x, l, p, sites, R, ln=((pre + "ln1", R.y1, R.st1) if self.ln_fuse else None))
+            if R.qkv is not None:
+                self._probs_hook(self.model.encoder.layers[l].mha.dropout, R.qkv, R.lse, 0)
+        else:
+            self.attn_unfused_fwd(x, l, 0, sites, p, R)
+        if not (self.attn_block and self.ln_fuse):
+            self.ln_fwd(R.r1, pre + "ln1", R.y1, R.st1)
+        if self.fuse_ffn:       # linear1 -> ReLU -> dropout -> linear2 -> dropout x2 -> + residual in one launch (A:272, A:294)
+            # an engine that keeps no gate bits runs at p = 0: its descriptor names no dropout site
+            drops = {} if R.gbits is None else dict(drop_h=(p, sites["ffn_a"]), drop_c1=(p, sites["ffn_b"]), drop_c2=(p, sites["drop2"]),
+                                                    bits_out=ptr(R.gbits))
+            self.ffn(ptr(R.y1), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), ptr(R.hff), ptr(R.r2), M, F,
+                     bias1=fp.p_ptr(pre + "ffn.linear1.bias"), bias2=fp.p_ptr(pre + "ffn.linear2.bias"), act1=L.ACT_RELU,
+                     residual=ptr(R.y1), ln=((pre + "ln2", R.out, R.st2) if self.ln_fuse else None), **drops)
+        else:
+            self.ffn_unfused_fwd(R.y1, l, R.hff, R.r2, p, sites)
+        if not (self.fuse_ffn and self.ln_fuse):
+            self.ln_fwd(R.r2, pre + "ln2", R.out, R.st2)
+        return R.out
+
+    def ffn_unfused_fwd(self, y1, l, hff, r2, p, sites):
+        """Layer l's feed-forward pair as two launches: linear1 + ReLU + dropout, linear2 + dropout x2 + residual (A:272, A:294)"""
+        M, d, F, w, fp, pre = self.M, self.cfg.d_model, self.cfg.d_ff, self.w, self.fp, f"encoder.layers.{l}."
+        self.gemm(ptr(y1), ptr(w[f"w1{l}"]), ptr(hff), M, F, d, bias=fp.p_ptr(pre + "ffn.linear1.bias"),
+                  act=L.ACT_RELU, drop1=(p, sites["ffn_a"]))
+        self.gemm(ptr(hff), ptr(w[f"w2{l}"]), ptr(r2), M, d, F, bias=fp.p_ptr(pre + "ffn.linear2.bias"),
+                  drop1=(p, sites["ffn_b"]), drop2=(p, sites["drop2"]), residual=ptr(y1))
+
+    def _front_end_fwd(self, eeg1, eeg2, train: bool, p01: float, h1):
+        """Input windows -> token rows a["x0"] (returned): window pack, conv-0, conv-1 (+ positions), the CLS rows and the optional
+        token families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written)."""
+        cfg, d = self.cfg, self.cfg.d_model
+        B, NB, S, a, w, fp, es, st = self.B, self.NB, self.S, self.a, self.w, self.fp, self.es, self.stream
+        for i, x in enumerate((eeg1, eeg2)):
+            if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, self.C, self.T):
+                raise L.EgError(f"input windows must be contiguous f32 [{B},{self.C},{self.T}], got {tuple(x.shape)} {x.dtype}")
+            call("eg_window_pack", ptr(x), ptr(a["xt"]) + i * B * self.Tp * self.Cp * es, B, self.C, self.T, self.Cp,
+                 self.pad, self.Tp, self.dtype, st)
+        # K1: conv0 as a GEMM over overlapping channel-last rows (D:154,171)
+        self.gemm(ptr(a["xt"]), ptr(w["conv0"]), ptr(a["h0pad"]) + self.pad * d * es, NB * self.T1, d, self.K0,
+                  a=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1), c=rowmap(d, self.R0 * d, self.T1),
+                  bias=fp.p_ptr("temporal_conv.convs.0.bias"), act=L.ACT_RELU, drop1=(p01, SITE_CONV0))
+        # K2: conv1, epilogue writes token rows [off:] of the sequence with the positional rows added (D:158,171,174; A:120-126)
+        self.gemm(ptr(a["h0pad"]), ptr(w["conv1"]), ptr(a["x0"]) + self.off * d * es, NB * self.T2, d, self.k * d,
+                  a=rowmap(self.s * d, self.R0 * d, self.T2), c=rowmap(d, S * d, self.T2),
+                  r=rowmap(d, 0, self.T2), p=rowmap(d), bias=fp.p_ptr("temporal_conv.convs.1.bias"), act=L.ACT_RELU,
+                  drop1=(p01, SITE_CONV1), residual=ptr(w["pos"]) + self.off * d * es, out_pre=ptr(h1), tag="conv1_fwd")
+        # CLS rows (D:1157) + pos row 0
+        call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
+             0, 1, self.dtype, st)
+        self.model._extra_tokens_fwd(self, eeg1, eeg2, train)
+        return a["x0"]
+
+    def _heads_fwd(self, z, labels, train: bool, p: float):
+        """Pooling, symmetric fusion, classifier(s) and the losses on the final token rows z (D:1193-1213)"""
+        cfg, d = self.cfg, self.cfg.d_model
+        B, S, a, w, fp, st = self.B, self.S, self.a, self.w, self.fp, self.stream
+        self.z_final = z
+        # heads (D:1193-1213)
+        call("eg_pool_fuse_fwd", ptr(z), ptr(a["cls1"]), ptr(a["cls2"]), ptr(a["comb"]), ptr(a["zf"]),
+             ptr(a.get("ibs_pool_f")), ptr(a.get("ibs_pool")), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
+        lab = ptr(labels) if labels is not None else 0
+        if self._fused_heads():     # both products, the class projection, the per-sample CE and its mean: one launch
+            call("eg_heads_fwd", ptr(a["comb"]), ptr(a["zf"]), ptr(a["hcl"]), ptr(w["sf"]), fp.p_ptr("symmetric_fusion.proj.bias"),
+                 ptr(w["c0"]), fp.p_ptr("classifier.0.bias"), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
+                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), ptr(a["heads_ctr"]), B, d, cfg.num_classes, p, SITE_CLS,
+                 self.st_ptr, self.dtype, st)
+        else:
+            self.gemm(ptr(a["comb"]), ptr(w["sf"]), ptr(a["zf"]), B, d, 3 * d, c=rowmap(3 * d),
+                      bias=fp.p_ptr("symmetric_fusion.proj.bias"))
+            self.gemm(ptr(a["zf"]), ptr(w["c0"]), ptr(a["hcl"]), B, d, 3 * d, bias=fp.p_ptr("classifier.0.bias"),
+                      act=L.ACT_RELU, drop1=(p, SITE_CLS))
+            call("eg_classifier_ce_fwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
+                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), B, d, cfg.num_classes, self.dtype, st)
+        if cfg.use_ibs:
+            p3 = 0.3 if train else 0.0
+            self.gemm(ptr(a["ibs_pool"]), ptr(w["i0"]), ptr(a["hib"]), B, d // 2, d, bias=fp.p_ptr("ibs_classifier.0.bias"),
+                      act=L.ACT_RELU, drop1=(p3, SITE_IBSCLS))
+            call("eg_classifier_ce_fwd", ptr(a["hib"]), fp.p_ptr("ibs_classifier.3.weight"), fp.p_ptr("ibs_classifier.3.bias"),
+                 lab, ptr(a["ibs_logits"]), ptr(a["ibs_sloss"]), ptr(a["ibs_loss"]), B, d // 2, cfg.num_classes, self.dtype, st)
+        self.labels = labels
+
+    def _fused_heads(self, backward: bool = False) -> bool:
+        """the fused head kernels cover 16-bit compute dtypes at d_model == 256 with at most 16 classes; their in-launch weight
+        gradients (backward) sum at most 256 samples, and need classifier.0 / symmetric_fusion.proj each laid out as weight then
+        bias in the flat gradient buffer (as eg_gemm_tn's fused-bias reduce does)"""
+        ok = bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model == 256 and self.cfg.num_classes <= 16
+        if ok and backward:
+            d = self.cfg.d_model
+            ok = self.B <= 256 and all(self._packed([n], d, 3 * d) for n in ("classifier.0", "symmetric_fusion.proj"))
+        return ok
+
+# What Engine.backward decides once, before its first launch, and every stage reads:
+#   p, train        dropout probability of the forward this backward belongs to, and whether that was a training forward
+#   sc, sc01        1 / (1 - p) of the encoder's and the heads' dropout, of the front end's
+#   seg             hears the name of each gradient segment as it completes (on_segment, or nobody)
+#   grouped         the encoder's weight gradients as one grouped launch ...
+#   pieced          ... cut in two pieces, the first launched after the plan's split layer
+#   defer_norms     the two norms outside the layers leave their gain / bias partials to the grouped reduce
+#   gx              the cross-attention block's weight gradients ride in the grouped launch
+#   fused_heads     the heads' backward as three launches (_fused_heads)
+#   fused_tokens    position / cls / conv-1 gradient rows from one pass over dseq
+#   dY1             ungrouped route: ONE buffer for the masked gradient that enters a branch
+BwdDecisions = namedtuple("BwdDecisions", "p train sc sc01 seg grouped pieced defer_norms gx has_drop fused_heads fused_tokens dY1")
+
+
+class Engine(ForwardEngine):
+    """Workspace + kernel sequencing of the training step for a fixed (B, T): the shared forward over per-layer saved
+    activations, the backward, gradient accumulation and the optimiser."""
+    LN_PARTIAL_BLOCKS = 2048      # rows of [2, d] the LayerNorm-backward scratch partial buffer holds (g["lnpart"])
+    SQ_BLOCKS = 1024              # squared-norm partials of the flat gradient buffer (g["sqpart"]) that eg_clip_coef sums
+    GROUP_MIN_ROWS = 4096         # token rows below which the per-product weight-gradient launches (many splits) are the better shape
+    tn_cap = 24 * 1024 * 1024     # floats (96 MB) of TN split-K partials: sized for the largest product (conv-1 weights / FFN)
+
+    def __init__(self, model, B: int, T: int, device: torch.device, dtype: int, state_dev: Optional[torch.Tensor] = None):
+        self._wg_key = self._wg_plan = None     # the grouped weight-gradient plan and the gradient buffer it was made for
+        self._wg_cross, self._ln_slot = False, {}
+        self._ranges_key = None
+        self._acc_norm_ready = False   # g["sqpart"] holds the norm partials of the whole accumulator (accumulate(norm=True))
+        super().__init__(model, B, T, device, dtype, state_dev)
+
+    def _resolve_routes(self):
+        """The forward's routes (ForwardEngine) and the backward's, from the same inputs"""
+        super()._resolve_routes()
+        cfg, dtype, env = self.cfg, self.dtype, os.environ
+        half = dtype != EG_F32
+        self.scaler_on = dtype == EG_F16 and env.get("EYEGAZE_LOSS_SCALING", "1") != "0"
+        # LayerNorm backward: a block walks 8 rows per trip with TWO trips in flight (112 registers: four 256-thread blocks per CU).
+        # All blocks must be resident at once -- a late block starts when an early one ends and doubles the launch -- so at most
+        # 4 blocks per CU: 33 280 rows = 1024 blocks x 4.06 trips (round 2: 1040 x 4 with one trip in flight)
+        env_nb = env.get("EYEGAZE_LN_BLOCKS")
+        trips = max(1, self.M // 8192)
+        self.LN_BLOCKS = int(env_nb) if env_nb else min(self.LN_PARTIAL_BLOCKS, 4 * self.cus,
+                                                        max(1, (self.M + 8 * trips - 1) // (8 * trips)))
+        if not 1 <= self.LN_BLOCKS <= self.LN_PARTIAL_BLOCKS:
+            # round 2: a sweep at 2080 blocks stored past the 2048-row partial buffer (GPU memory access fault); refuse, never clamp
+            raise L.EgError(f"EYEGAZE_LN_BLOCKS={env_nb} is outside [1, {self.LN_PARTIAL_BLOCKS}] (rows of the LayerNorm-backward "
+                            "partial buffer)")
+        self.ln_nblk_cap = max(self.LN_BLOCKS, (self.M + 63) // 64)
+        # norm1's backward and out_proj's backward-data product as one launch over 80-row tiles (eg_ln_bwd_proj): bit-identical to the
+        # two launches (the gain / bias partials are grouped by tile instead of by LayerNorm block: equal to fp32 rounding)
+        self.ln_proj = half and cfg.d_model == 256
+        self.ln_proj_blocks = L.lib().eg_ln_bwd_proj_blocks(self.M) if self.ln_proj else 0
+        # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
+        # instead of eg_grad_sqnorm + eg_clip_coef.  Off by default: tests/test_gpu_accum.py counts the trainer's eg_grad_sqnorm calls
+        self.fused_norm_clip = False
+        # conv-1 backward-data as one batched launch over the real rows and the non-zero taps (conv1_bwd_data); False, or
+        # EYEGAZE_CONV1_BWD_BATCH=0, keeps one full launch per stride phase
+        self.conv1_bwd_batch = env.get("EYEGAZE_CONV1_BWD_BATCH", "1") != "0"
+
+    def _held(self, group, l, every: bool):
+        """Every layout is allocated (tests flip routes on a live engine), but a fragment layout only where its route was on at
+        construction.  Recorded are the layouts that the routes chosen now read -- the row-major q|k|v and out_proj of an encoder
+        layer belong to the unfused attention route, out_proj^T to the separate backward-data product when eg_ln_bwd_proj is off,
+        the four row-major feed-forward matrices to the unfused feed-forward route -- and with pack_unused = True every row-major
+        one as well."""
+        return [lay for lay in group if self._reads(lay, l) or (every and not lay.fused)]
+
+    def _alloc(self):
+        cfg, d, F, L_ = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_layers
+        NB, M, S, H = self.NB, self.M, self.S, self.cfg.num_heads
+        f32 = torch.float32
+        self.w = self._alloc_w()
+        a = {"xt": self._t(NB, self.Tp, self.Cp), "h0pad": self._t(NB, self.R0, d), "h1": self._t(NB * self.T2, d), "x0": self._t(M, d)}
+        rows, stats = (lambda: self._t(M, d)), (lambda: self._t(M, 2, dtype=f32))
+        for l in range(L_):
+            a.update({f"qkv{l}": self._t(M, 3 * d), f"lse{l}": self._t(NB, H, S, dtype=f32), f"ctx{l}": rows(), f"r1_{l}": rows(),
+                      f"st1_{l}": stats(), f"y1_{l}": rows(), f"hff{l}": self._t(M, F), f"r2_{l}": rows(), f"st2_{l}": stats(),
+                      f"x{l + 1}": rows()})
+            if self.fuse_ffn:           # ReLU / dropout gate of the hidden rows, one bit per element (forward -> backward)
+                a[f"gbits{l}"] = torch.zeros(L.gate_bits_bytes(M, F) // 8, device=self.device, dtype=torch.int64)
+        a["stf"], a["zn"] = stats(), rows()
+        if cfg.use_cross_attention:
+            a.update(qkvx=self._t(M, 3 * d), lsex=self._t(NB, H, S, dtype=f32), ctxx=rows(), rx=rows(), stx=stats(), zc=rows())
+        a.update(self._head_alloc())
+        self.a = a
+
+    def _rows(self, l, x=None) -> Rows:
+        """Stage l's rows in the saved activations: an encoder layer's index, "norm" (the final norm) or "x" (the cross-attention
+        block, which is an unfused layer's attention half under other names)"""
+        a = self.a
+        if l == "norm":
+            return Rows(st2=a["stf"], out=a["zn"])
+        if l == "x":
+            return Rows(a["qkvx"], a["lsex"], a["ctxx"], a["rx"], a["stx"], out=a["zc"])
+        return Rows(a[f"qkv{l}"], a[f"lse{l}"], a[f"ctx{l}"], a[f"r1_{l}"], a[f"st1_{l}"], a[f"y1_{l}"], a[f"hff{l}"],
+                    a.get(f"gbits{l}"), a[f"r2_{l}"], a[f"st2_{l}"], a[f"x{l + 1}"])
+
+    def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], train: bool):
+        self._forward(eeg1, eeg2, labels, train)
+
+    def _alloc_bwd(self):
+        if self.g:
+            return
+        d, F, M, B, NB = self.cfg.d_model, self.cfg.d_ff, self.M, self.B, self.NB
+        g = {}
+        for n in ("dzA", "dzB", "dr", "drm", "dctx", "dy1"):
+            g[n] = self._t(M, d)
+        g["dqkv"] = self._t(M, 3 * d)
+        g["dh"] = self._t(M, F)
+        g["dzf"] = self._t(B, 3 * d)
+        g["dcomb"] = self._t(B, 3 * d)
+        g["dhcl"] = self._t(B, d)
+        g["dlogits"] = self._t(B, self.cfg.num_classes, dtype=torch.float32)
+        if self.cfg.use_ibs:
+            g["dhib"] = self._t(B, d // 2)
+            g["dibs_pool"] = self._t(B, d)
+            g["dibs_logits"] = self._t(B, self.cfg.num_classes, dtype=torch.float32)
+        g["dy1pad"] = self._t(NB, self.RY, d)
+        g["dh0pad"] = self._t(NB, self.R0, d)
+        g["possum"] = self._t(self.S, d, dtype=torch.float32)
+        g["one"] = torch.ones(1, device=self.device, dtype=torch.float32)
+        g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
+        g["lnpart"] = self._t(self.LN_PARTIAL_BLOCKS * 2 * max(d, 8), dtype=torch.float32)
+        g["cspart"] = self._t(512 * max(3 * d, F), dtype=torch.float32)
+        if self.attn_long:          # delta = rowsum(dctx * ctx) of eg_attention_long_bwd, [NB, H, S]
+            g["attn_delta"] = self._t(NB * self.cfg.num_heads * self.S, dtype=torch.float32)
+        self.g = g
+
+    def check_overflow_and_update_scaler(self):
+        """autograd path at fp16: flags a non-finite gradient norm (eg_step_state.found_inf) and adapts the internal loss scale,
+        as the native optimiser step does between eg_clip_coef and eg_scaler_update -- without touching parameters."""
+        self._alloc_bwd()
+        self.stream = self._cur_stream()
+        nblk, sq = self.SQ_BLOCKS, ptr(self._sqpart())
+        self._acc_norm_ready = False
+        call("eg_grad_sqnorm", ptr(self.fp.grad), self.fp.total, sq, nblk, self.stream)
+        call("eg_clip_coef", sq, nblk, 0.0, self.st_ptr, self.stream)
+        c = self.scaler_cfg
+        call("eg_scaler_update", self.st_ptr, c["growth"], c["backoff"], c["growth_interval"], self.stream)
+
+    def conv1_bwd_data(self, sc01, batch=None):
+        """dh0 = conv-1's backward-data (gated by h0 > 0, scaled by sc01): stride phase ph gives rows t = u*s + ph of dh0pad
+        from J taps of dy1pad.
+        batch (default self.conv1_bwd_batch): the phases as ONE eg_gemm_nt_batch call that skips what the result does not
+        need -- the leading tap block of a phase whose tap s*(J-1) + ph lies beyond the kernel (zeros in conv1T) and the rows
+        that fall into dh0pad's pads, which nothing reads (conv-0's weight gradient starts at row `pad`; the buffer is zeroed
+        once, at allocation).  False: one full launch per phase.  The real rows of dh0 are the same bits either way."""
+        d, es, s, J, g, a, w = self.cfg.d_model, self.es, self.s, self.J, self.g, self.a, self.w
+        NB = self.NB
+        if not (self.conv1_bwd_batch if batch is None else batch):
+            for ph in range(s):
+                self.gemm(ptr(g["dy1pad"]), ptr(w["conv1T"]) + ph * d * J * d * es, ptr(g["dh0pad"]) + ph * d * es,
+                          NB * self.U, d, J * d, a=rowmap(d, self.RY * d, self.U), c=rowmap(s * d, self.R0 * d, self.U),
+                          gate=ptr(a["h0pad"]) + ph * d * es, gate_scale=sc01)
+            return
+        items = []
+        for ph, u0, n, j0 in conv_bwd_data_phases(self.k, s, self.pad, self.T1):
+            row = (u0 * s + ph) * d * es
+            items.append(dict(A=ptr(g["dy1pad"]) + (u0 + j0) * d * es, W=ptr(w["conv1T"]) + (ph * d * J * d + j0 * d) * es,
+                              C=ptr(g["dh0pad"]) + row, M=NB * n, N=d, K=(J - j0) * d, ldw=J * d,
+                              a=rowmap(d, self.RY * d, n), c=rowmap(s * d, self.R0 * d, n),
+                              gate=ptr(a["h0pad"]) + row, gate_scale=sc01))
+        for i in range(0, len(items), L.GEMM_BATCH_MAX):
+            self.gemm_batch(items[i:i + L.GEMM_BATCH_MAX])
+
     # ------------------------------------------------------------------------------------------
     # grouped weight gradients of the encoder: ONE launch for all 4*L products, ONE reduce launch
     # ------------------------------------------------------------------------------------------
@@ -864,10 +1132,6 @@ class Engine(EngineBase):
             seg("cross")
         for l in reversed(pl["layers"]):
             seg(f"layer{l}")
-
-    def ln_fwd(self, x, gname, y, stats):
-        call("eg_layernorm_fwd", ptr(x), self.fp.p_ptr(gname + ".weight"), self.fp.p_ptr(gname + ".bias"), ptr(y),
-             ptr(stats), self.M, self.cfg.d_model, self.dtype, self.stream)
 
     def ln_bwd_proj(self, dy, x, stats, gname, wfrag, dx, dx_drop, dC, d1=(0.0, 0), slot=None):
         """eg_ln_bwd_proj: LayerNorm backward + the backward-data product dC = dx_drop W^T in one launch (csrc/lnproj.hip)"""
@@ -916,166 +1180,6 @@ class Engine(EngineBase):
         self.ln_bwd(dy, x, stats, gname, dmasked, None, slot=slot)
         return dmasked
 
-    def _pack_body(self):
-        cfg, d, F, fp, w, dt, st = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.fp, self.w, self.dtype, self.stream
-        self.p_conv(fp.p_ptr("temporal_conv.convs.0.weight"), ptr(w["conv0"]), d, self.C, self.k, self.Cp, self.K0)
-        self.p_conv(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1"]), d, d, self.k, d, self.k * d)
-        self.p_convT(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1T"]), d, d, self.k, self.s)
-        self.p_cast(fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["pos"]), cfg.max_len * d)
-
-        # Layouts that the chosen route never reads are not recorded (their buffers stay allocated): the row-major q|k|v and
-        # out_proj of an encoder layer belong to the unfused attention route, out_proj^T to the separate backward-data product
-        # when eg_ln_bwd_proj is off, the four row-major feed-forward matrices to the unfused feed-forward route.  The
-        # cross-attention block "x" has no fused route and keeps all of its layouts.  pack_unused = True records everything.
-        full = bool(self.pack_unused)
-
-        def attn_pack(pre, l):
-            enc = l != "x"
-            for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                if full or not (enc and self.attn_block):
-                    self.p_cast(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkv{l}"]) + i * d * d * self.es, d * d)
-                self.p_transpose(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkvT{l}"]) + i * d * self.es, d, d, 3 * d)
-                self.p_copy(fp.p_ptr(f"{pre}{n}.bias"), ptr(w[f"bqkv{l}"]) + 4 * i * d, d)
-            if full or not (enc and self.attn_block):
-                self.p_cast(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"o{l}"]), d * d)
-            if full or not (enc and self.ln_proj):
-                self.p_transpose(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"oT{l}"]), d, d, d)
-            if self.ln_proj and l != "x":
-                self.p_frag(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"oTf{l}"]), d, d, 6)
-            if self.attn_block and l != "x":
-                for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                    self.p_frag(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"wqkvb{l}"]), d, d, 7, part=i)
-                self.p_frag(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"wob{l}"]), d, d, 8)
-
-        for l in range(cfg.num_layers):
-            pre = f"encoder.layers.{l}."
-            attn_pack(pre + "mha.", l)
-            if full or not self.fuse_ffn:
-                self.p_cast(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1{l}"]), F * d)
-                self.p_transpose(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1T{l}"]), F, d, F)
-                self.p_cast(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2{l}"]), d * F)
-                self.p_transpose(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2T{l}"]), d, F, d)
-            if self.fuse_ffn:
-                self.p_frag(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1f{l}"]), F, d, 3)     # forward product 1
-                self.p_frag(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2f{l}"]), d, F, 5)     # forward product 2
-                self.p_frag(fp.p_ptr(pre + "ffn.linear2.weight"), ptr(w[f"w2Tf{l}"]), d, F, 4)    # backward product 1 = linear2^T
-                self.p_frag(fp.p_ptr(pre + "ffn.linear1.weight"), ptr(w[f"w1Tf{l}"]), F, d, 6)    # backward product 2 = linear1^T
-        if cfg.use_cross_attention:
-            attn_pack("cross_attn.cross_attn.", "x")
-        self.p_cast(fp.p_ptr("symmetric_fusion.proj.weight"), ptr(w["sf"]), 3 * d * d)
-        self.p_transpose(fp.p_ptr("symmetric_fusion.proj.weight"), ptr(w["sfT"]), d, 3 * d, d)
-        self.p_cast(fp.p_ptr("classifier.0.weight"), ptr(w["c0"]), 3 * d * d)
-        self.p_transpose(fp.p_ptr("classifier.0.weight"), ptr(w["c0T"]), d, 3 * d, d)
-        if cfg.use_ibs:
-            self.p_cast(fp.p_ptr("ibs_classifier.0.weight"), ptr(w["i0"]), (d // 2) * d)
-            self.p_transpose(fp.p_ptr("ibs_classifier.0.weight"), ptr(w["i0T"]), d // 2, d, w["i0T"].shape[1])
-        self.model._pack_extra(self)
-
-    # ------------------------------------------------------------------------------------------
-    # forward
-    # ------------------------------------------------------------------------------------------
-    def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor], train: bool):
-        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
-        B, NB, M, S, a, w, fp, es = self.B, self.NB, self.M, self.S, self.a, self.w, self.fp, self.es
-        self.stream = self._cur_stream()
-        st = self.stream
-        p = cfg.dropout if train else 0.0
-        p01 = 0.1 if train else 0.0
-        self.train_flags = (p, p01, train)
-        self.pack_params()
-        self._front_end_fwd(eeg1, eeg2, train, p01, a["h1"])
-        # encoder (A:292-295, 326-328), both streams batched (Siamese weights)
-        for l in range(cfg.num_layers):
-            pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
-            x = a[f"x{l}"]
-            if self.attn_block:     # q|k|v projection + attention core + out-proj / dropout / residual: one launch, a workgroup per window
-                self.attn_block_fwd(x, l, p, sites, ln=((pre + "ln1", a[f"y1_{l}"], a[f"st1_{l}"]) if self.ln_fuse else None))
-                self._probs_hook(self.model.encoder.layers[l].mha.dropout, a[f"qkv{l}"], a[f"lse{l}"], 0)
-            else:
-                self.attn_unfused_fwd(x, l, 0, sites, p)
-            if not (self.attn_block and self.ln_fuse):
-                self.ln_fwd(a[f"r1_{l}"], pre + "ln1", a[f"y1_{l}"], a[f"st1_{l}"])
-            if self.fuse_ffn:       # linear1 -> ReLU -> dropout -> linear2 -> dropout x2 -> + residual in one launch (A:272, A:294)
-                self.ffn(ptr(a[f"y1_{l}"]), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), ptr(a[f"hff{l}"]), ptr(a[f"r2_{l}"]), M, F,
-                         bias1=fp.p_ptr(pre + "ffn.linear1.bias"), bias2=fp.p_ptr(pre + "ffn.linear2.bias"), act1=L.ACT_RELU,
-                         residual=ptr(a[f"y1_{l}"]), drop_h=(p, sites["ffn_a"]), drop_c1=(p, sites["ffn_b"]),
-                         drop_c2=(p, sites["drop2"]), bits_out=ptr(a[f"gbits{l}"]),
-                         ln=((pre + "ln2", a[f"x{l + 1}"], a[f"st2_{l}"]) if self.ln_fuse else None))
-            else:
-                self.ffn_unfused_fwd(a[f"y1_{l}"], l, a[f"hff{l}"], a[f"r2_{l}"], p, sites)
-            if not (self.fuse_ffn and self.ln_fuse):
-                self.ln_fwd(a[f"r2_{l}"], pre + "ln2", a[f"x{l + 1}"], a[f"st2_{l}"])
-        Lr = cfg.num_layers
-        self.ln_fwd(a[f"x{Lr}"], "encoder.norm", a["zn"], a["stf"])
-        z = a["zn"]
-        if cfg.use_cross_attention:
-            # D:966-974: both directions in one launch each (kv_shift = B pairs window b with b+B)
-            self.attn_unfused_fwd(z, "x", B, _layer_sites(Lr), p)
-            self.ln_fwd(a["rx"], "cross_attn.norm", a["zc"], a["stx"])
-            z = a["zc"]
-        self._heads_fwd(z, labels, train, p)
-
-    def ffn_unfused_fwd(self, y1, l, hff, r2, p, sites):
-        """Layer l's feed-forward pair as two launches: linear1 + ReLU + dropout, linear2 + dropout x2 + residual (A:272, A:294)"""
-        M, d, F, w, fp, pre = self.M, self.cfg.d_model, self.cfg.d_ff, self.w, self.fp, f"encoder.layers.{l}."
-        self.gemm(ptr(y1), ptr(w[f"w1{l}"]), ptr(hff), M, F, d, bias=fp.p_ptr(pre + "ffn.linear1.bias"),
-                  act=L.ACT_RELU, drop1=(p, sites["ffn_a"]))
-        self.gemm(ptr(hff), ptr(w[f"w2{l}"]), ptr(r2), M, d, F, bias=fp.p_ptr(pre + "ffn.linear2.bias"),
-                  drop1=(p, sites["ffn_b"]), drop2=(p, sites["drop2"]), residual=ptr(y1))
-
-    def _front_end_fwd(self, eeg1, eeg2, train: bool, p01: float, h1):
-        """Input windows -> token rows a["x0"]: window pack, conv-0, conv-1 (+ positions), the CLS rows and the optional token
-        families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written)."""
-        cfg, d = self.cfg, self.cfg.d_model
-        B, NB, S, a, w, fp, es, st = self.B, self.NB, self.S, self.a, self.w, self.fp, self.es, self.stream
-        for i, x in enumerate((eeg1, eeg2)):
-            if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, self.C, self.T):
-                raise L.EgError(f"input windows must be contiguous f32 [{B},{self.C},{self.T}], got {tuple(x.shape)} {x.dtype}")
-            call("eg_window_pack", ptr(x), ptr(a["xt"]) + i * B * self.Tp * self.Cp * es, B, self.C, self.T, self.Cp,
-                 self.pad, self.Tp, self.dtype, st)
-        # K1: conv0 as a GEMM over overlapping channel-last rows (D:154,171)
-        self.gemm(ptr(a["xt"]), ptr(w["conv0"]), ptr(a["h0pad"]) + self.pad * d * es, NB * self.T1, d, self.K0,
-                  a=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1), c=rowmap(d, self.R0 * d, self.T1),
-                  bias=fp.p_ptr("temporal_conv.convs.0.bias"), act=L.ACT_RELU, drop1=(p01, SITE_CONV0))
-        # K2: conv1, epilogue writes token rows [off:] of the sequence with the positional rows added (D:158,171,174; A:120-126)
-        self.gemm(ptr(a["h0pad"]), ptr(w["conv1"]), ptr(a["x0"]) + self.off * d * es, NB * self.T2, d, self.k * d,
-                  a=rowmap(self.s * d, self.R0 * d, self.T2), c=rowmap(d, S * d, self.T2),
-                  r=rowmap(d, 0, self.T2), p=rowmap(d), bias=fp.p_ptr("temporal_conv.convs.1.bias"), act=L.ACT_RELU,
-                  drop1=(p01, SITE_CONV1), residual=ptr(w["pos"]) + self.off * d * es, out_pre=ptr(h1), tag="conv1_fwd")
-        # CLS rows (D:1157) + pos row 0
-        call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
-             0, 1, self.dtype, st)
-        self.model._extra_tokens_fwd(self, eeg1, eeg2, train)
-
-    def _heads_fwd(self, z, labels, train: bool, p: float):
-        """Pooling, symmetric fusion, classifier(s) and the losses on the final token rows z (D:1193-1213)"""
-        cfg, d = self.cfg, self.cfg.d_model
-        B, S, a, w, fp, st = self.B, self.S, self.a, self.w, self.fp, self.stream
-        self.z_final = z
-        # heads (D:1193-1213)
-        call("eg_pool_fuse_fwd", ptr(z), ptr(a["cls1"]), ptr(a["cls2"]), ptr(a["comb"]), ptr(a["zf"]),
-             ptr(a.get("ibs_pool_f")), ptr(a.get("ibs_pool")), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
-        lab = ptr(labels) if labels is not None else 0
-        if self._fused_heads():     # both products, the class projection, the per-sample CE and its mean: one launch
-            call("eg_heads_fwd", ptr(a["comb"]), ptr(a["zf"]), ptr(a["hcl"]), ptr(w["sf"]), fp.p_ptr("symmetric_fusion.proj.bias"),
-                 ptr(w["c0"]), fp.p_ptr("classifier.0.bias"), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
-                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), ptr(a["heads_ctr"]), B, d, cfg.num_classes, p, SITE_CLS,
-                 self.st_ptr, self.dtype, st)
-        else:
-            self.gemm(ptr(a["comb"]), ptr(w["sf"]), ptr(a["zf"]), B, d, 3 * d, c=rowmap(3 * d),
-                      bias=fp.p_ptr("symmetric_fusion.proj.bias"))
-            self.gemm(ptr(a["zf"]), ptr(w["c0"]), ptr(a["hcl"]), B, d, 3 * d, bias=fp.p_ptr("classifier.0.bias"),
-                      act=L.ACT_RELU, drop1=(p, SITE_CLS))
-            call("eg_classifier_ce_fwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"), fp.p_ptr("classifier.3.bias"), lab,
-                 ptr(a["logits"]), ptr(a["sloss"]), ptr(a["loss"]), B, d, cfg.num_classes, self.dtype, st)
-        if cfg.use_ibs:
-            p3 = 0.3 if train else 0.0
-            self.gemm(ptr(a["ibs_pool"]), ptr(w["i0"]), ptr(a["hib"]), B, d // 2, d, bias=fp.p_ptr("ibs_classifier.0.bias"),
-                      act=L.ACT_RELU, drop1=(p3, SITE_IBSCLS))
-            call("eg_classifier_ce_fwd", ptr(a["hib"]), fp.p_ptr("ibs_classifier.3.weight"), fp.p_ptr("ibs_classifier.3.bias"),
-                 lab, ptr(a["ibs_logits"]), ptr(a["ibs_sloss"]), ptr(a["ibs_loss"]), B, d // 2, cfg.num_classes, self.dtype, st)
-        self.labels = labels
-
     @staticmethod
     def _wgrad_pieces(listening: bool) -> bool:
         """Whether backward cuts the grouped weight-gradient launch in two pieces (see wgrad_plan.plan): with a gradient reducer
@@ -1084,16 +1188,6 @@ class Engine(EngineBase):
         pcs = os.environ.get("EYEGAZE_WGRAD_PIECES", "")
         return pcs != "0" and (listening or pcs == "1")
 
-    def _fused_heads(self, backward: bool = False) -> bool:
-        """the fused head kernels cover 16-bit compute dtypes at d_model == 256 with at most 16 classes; their in-launch weight
-        gradients (backward) sum at most 256 samples, and need classifier.0 / symmetric_fusion.proj each laid out as weight then
-        bias in the flat gradient buffer (as eg_gemm_tn's fused-bias reduce does)"""
-        ok = bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model == 256 and self.cfg.num_classes <= 16
-        if ok and backward:
-            d = self.cfg.d_model
-            ok = self.B <= 256 and all(self._packed([n], d, 3 * d) for n in ("classifier.0", "symmetric_fusion.proj"))
-        return ok
-
     # ------------------------------------------------------------------------------------------
     # backward.  g* arguments are optional fp32 device tensors (gradients of the module's outputs);
     # gloss / gloss_ibs are 1-element fp32 device tensors (d total / d loss_ce, d total / d loss_ibs_cls).
@@ -1101,31 +1195,55 @@ class Engine(EngineBase):
     # ------------------------------------------------------------------------------------------
     def backward(self, gloss=None, gloss_ibs=None, glogits=None, gcls1=None, gcls2=None, gibs_logits=None,
                  gibs_token=None, on_segment=None, prescaled: bool = False):
+        """Each stage takes the gradient rows and the free row buffer and returns that pair for the next stage"""
         self._alloc_bwd()
-        cfg, d, F, H = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.cfg.num_heads
-        B, NB, M, S, a, w, fp, g, es = self.B, self.NB, self.M, self.S, self.a, self.w, self.fp, self.g, self.es
         self.stream = self._cur_stream()
-        st = self.stream
+        b = self._bwd_decisions(on_segment)
+        gr = self._scale_incoming(prescaled, gloss=gloss, gloss_ibs=gloss_ibs, glogits=glogits, gcls1=gcls1, gcls2=gcls2,
+                                  gibs_logits=gibs_logits, gibs_token=gibs_token)
+        dz, free = self._heads_bwd(b, gr)
+        if self.cfg.use_cross_attention:
+            dz, free = self._cross_bwd(b, dz, free)
+        dz, free = self._final_norm_bwd(b, dz, free)
+        for l in reversed(range(self.cfg.num_layers)):
+            dz, free = self._layer_bwd(b, l, dz, free)
+        self._wgrad_group_bwd(b)
+        self._front_end_bwd(b, dz)
+
+    def _bwd_decisions(self, on_segment) -> BwdDecisions:
         p, p01, train = self.train_flags
-        sc = 1.0 / (1.0 - p) if p > 0 else 1.0
-        sc01 = 1.0 / (1.0 - p01) if p01 > 0 else 1.0
-        lab = ptr(self.labels) if self.labels is not None else 0
-        seg = on_segment or (lambda name: None)
+        plan = self._wgrad_group_plan()
+        grouped = plan is not None
+        pieced = grouped and len(plan["pieces"]) == 2 and self._wgrad_pieces(on_segment is not None)
+        return BwdDecisions(
+            p=p, train=train, sc=(1.0 / (1.0 - p) if p > 0 else 1.0), sc01=(1.0 / (1.0 - p01) if p01 > 0 else 1.0),
+            seg=on_segment or (lambda name: None), grouped=grouped, pieced=pieced,
+            # no reducer waits for the encoder.norm / cross buckets: the gain / bias partials of the two norms outside the layers
+            # are summed by the grouped reduce launch at the end of backward instead of a 16-workgroup launch each
+            defer_norms=grouped and not pieced and on_segment is None and plan["whole_norms"] is not None,
+            gx=self.cfg.use_cross_attention and grouped and self._wg_cross, has_drop=p > 0,
+            fused_heads=self._fused_heads(backward=True),
+            fused_tokens=bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model % 64 == 0,
+            dY1=self.g["drm"] if p > 0 else self.g["dr"])
+
+    def _scale_incoming(self, prescaled: bool, **grads):
+        """every gradient entering the backward is multiplied by the device-resident loss scale (no host sync); the optimiser
+        kernels divide it out again (eg_clip_coef / eg_adamw)"""
         if self.scaler_on and not prescaled:
-            # every gradient entering the backward is multiplied by the device-resident loss scale (no host sync); the
-            # optimiser kernels divide it out again (eg_clip_coef / eg_adamw)
             ls = self.loss_scale_dev
-            sc_ = lambda t_: None if t_ is None else t_ * ls
-            gloss, gloss_ibs, glogits, gcls1, gcls2 = sc_(gloss), sc_(gloss_ibs), sc_(glogits), sc_(gcls1), sc_(gcls2)
-            gibs_logits, gibs_token = sc_(gibs_logits), sc_(gibs_token)
-        # ---- heads ----
-        fused_heads = self._fused_heads(backward=True)
+            return {k: None if t is None else t * ls for k, t in grads.items()}
+        return grads
+
+    def _heads_bwd(self, b, gr):
+        """Heads and pooling: the incoming gradients -> the gradient of the final token rows, in g["dzA"]"""
+        cfg, d, B, S, a, w, fp, g, st = self.cfg, self.cfg.d_model, self.B, self.S, self.a, self.w, self.fp, self.g, self.stream
+        lab = ptr(self.labels) if self.labels is not None else 0
         # fused -- launch 1: CE backward rows + classifier.3's gradients; launch 2: both backward-data products chained per 16
         # samples + classifier.0's gradients; (launch 3, below: pool backward + symmetric_fusion.proj's gradients)
-        call("eg_classifier_ce_bwd_fused" if fused_heads else "eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"),
-             ptr(a["logits"]), lab, ptr(gloss), ptr(glogits), ptr(g["dlogits"]), ptr(g["dhcl"]), fp.g_ptr("classifier.3.weight"),
-             fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, sc, self.dtype, st)
-        if fused_heads:
+        call("eg_classifier_ce_bwd_fused" if b.fused_heads else "eg_classifier_ce_bwd", ptr(a["hcl"]), fp.p_ptr("classifier.3.weight"),
+             ptr(a["logits"]), lab, ptr(gr["gloss"]), ptr(gr["glogits"]), ptr(g["dlogits"]), ptr(g["dhcl"]),
+             fp.g_ptr("classifier.3.weight"), fp.g_ptr("classifier.3.bias"), B, d, cfg.num_classes, 1, b.sc, self.dtype, st)
+        if b.fused_heads:
             call("eg_heads_bwd_chain", ptr(g["dhcl"]), ptr(w["c0T"]), ptr(w["sfT"]), ptr(a["zf"]), ptr(g["dzf"]), ptr(g["dcomb"]),
                  fp.g_ptr("classifier.0.weight"), fp.g_ptr("classifier.0.bias"), B, d, self.dtype, st)
         else:
@@ -1135,136 +1253,135 @@ class Engine(EngineBase):
             self.wgrad(ptr(g["dzf"]), ptr(a["comb"]), 0, B, d, 3 * d, y=rowmap(3 * d), linear=["symmetric_fusion.proj"])
         dibs = None
         if cfg.use_ibs:
-            sc3 = 1.0 / 0.7 if train else 1.0
+            sc3 = 1.0 / 0.7 if b.train else 1.0
             call("eg_classifier_ce_bwd", ptr(a["hib"]), fp.p_ptr("ibs_classifier.3.weight"), ptr(a["ibs_logits"]), lab,
-                 ptr(gloss_ibs), ptr(gibs_logits), ptr(g["dibs_logits"]), ptr(g["dhib"]), fp.g_ptr("ibs_classifier.3.weight"),
-                 fp.g_ptr("ibs_classifier.3.bias"), B, d // 2, cfg.num_classes, 1, sc3, self.dtype, st)
-            Kp = w["i0T"].shape[1]
-            if Kp != d // 2:
+                 ptr(gr["gloss_ibs"]), ptr(gr["gibs_logits"]), ptr(g["dibs_logits"]), ptr(g["dhib"]),
+                 fp.g_ptr("ibs_classifier.3.weight"), fp.g_ptr("ibs_classifier.3.bias"), B, d // 2, cfg.num_classes, 1, sc3,
+                 self.dtype, st)
+            if w["i0T"].shape[1] != d // 2:
                 raise L.EgError("ibs_classifier hidden width must be a multiple of the GEMM K-tile")
             self.gemm(ptr(g["dhib"]), ptr(w["i0T"]), ptr(g["dibs_pool"]), B, d, d // 2)
             self.wgrad(ptr(g["dhib"]), ptr(a["ibs_pool"]), 0, B, d // 2, d, linear=["ibs_classifier.0"])
             dibs = g["dibs_pool"]
-        z = self.z_final
-        dz = g["dzA"]
-        if fused_heads:
-            call("eg_heads_bwd_pool", ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gcls1), ptr(gcls2), ptr(dibs), ptr(gibs_token),
-                 ptr(dz), ptr(a["comb"]), fp.g_ptr("symmetric_fusion.proj.weight"), fp.g_ptr("symmetric_fusion.proj.bias"),
-                 B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
+        z, dz = self.z_final, g["dzA"]
+        pool = (ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gr["gcls1"]), ptr(gr["gcls2"]), ptr(dibs), ptr(gr["gibs_token"]), ptr(dz))
+        if b.fused_heads:
+            call("eg_heads_bwd_pool", *pool, ptr(a["comb"]), fp.g_ptr("symmetric_fusion.proj.weight"),
+                 fp.g_ptr("symmetric_fusion.proj.bias"), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
         else:
-            call("eg_pool_fuse_bwd", ptr(z), ptr(g["dcomb"]), ptr(g["dzf"]), ptr(gcls1), ptr(gcls2), ptr(dibs), ptr(gibs_token),
-                 ptr(dz), B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
-        seg("heads")
-        Lr = cfg.num_layers
-        other = g["dzB"]
+            call("eg_pool_fuse_bwd", *pool, B, S, d, self.off, self.n_ibs, 1, self.dtype, st)
+        b.seg("heads")
+        return dz, g["dzB"]
 
-        grouped = self._wgrad_group_plan() is not None
-        pieced = grouped and len(self._wg_plan["pieces"]) == 2 and self._wgrad_pieces(on_segment is not None)
+    def _attn_stage_bwd(self, b, l, x_in, dr, drm, kv_shift, site_attn, dx_out, dqkv, defer, dctx_done=False):
+        """Attention stage l backward.  dr: grad of the pre-LN sum (residual path), drm: same, masked by the branch dropout;
+        defer: the stage's weight gradients ride in the grouped launch."""
+        M, d, NB, S, w, g = self.M, self.cfg.d_model, self.NB, self.S, self.w, self.g
+        pre, R = _attn_prefix(l), self._rows(l)
+        if not defer:
+            self.wgrad(ptr(drm), ptr(R.ctx), 0, M, d, d, linear=[pre + "out_proj"])
+        if not dctx_done:       # (eg_ln_bwd_proj has written dctx together with dr / drm)
+            self.gemm(ptr(drm), ptr(w[f"oT{l}"]), ptr(g["dctx"]), M, d, d)
+        delta = (ptr(g["attn_delta"]), g["attn_delta"].numel()) if self.attn_long else ()    # (the long core's scratch)
+        call(self._attn_core + "_bwd", ptr(R.qkv), ptr(R.ctx), ptr(g["dctx"]), ptr(R.lse),
+             ptr(dqkv), NB, S, *self._attn_heads, kv_shift, self.dtype, b.p, site_attn, self.st_ptr, *delta, self.stream)
+        if not defer:
+            self.wgrad(ptr(dqkv), ptr(x_in), 0, M, 3 * d, d, linear=[pre + n for n in ("q_proj", "k_proj", "v_proj")])
+        self.gemm(ptr(dqkv), ptr(w[f"qkvT{l}"]), ptr(dx_out), M, d, 3 * d, residual=ptr(dr))
 
-        def attn_block_bwd(l, x_in, dr, drm, kv_shift, site_attn, dx_out, dqkv, defer, dctx_done=False):
-            """dr: grad of the pre-LN sum (residual path), drm: same, masked by the branch dropout."""
-            pre, qkv, lse, ctx, _ = self._attn_stage(l)
-            names = [pre + n for n in ("q_proj", "k_proj", "v_proj")]
-            if not defer:
-                self.wgrad(ptr(drm), ptr(ctx), 0, M, d, d, linear=[pre + "out_proj"])
-            if not dctx_done:       # (eg_ln_bwd_proj has written dctx together with dr / drm)
-                self.gemm(ptr(drm), ptr(w[f"oT{l}"]), ptr(g["dctx"]), M, d, d)
-            delta = (ptr(g["attn_delta"]), g["attn_delta"].numel()) if self.attn_long else ()    # (the long core's scratch)
-            call(self._attn_core + "_bwd", ptr(qkv), ptr(ctx), ptr(g["dctx"]), ptr(lse),
-                 ptr(dqkv), NB, S, *self._attn_heads, kv_shift, self.dtype, p, site_attn, self.st_ptr, *delta, st)
-            if not defer:
-                self.wgrad(ptr(dqkv), ptr(x_in), 0, M, 3 * d, d, linear=names)
-            self.gemm(ptr(dqkv), ptr(w[f"qkvT{l}"]), ptr(dx_out), M, d, 3 * d, residual=ptr(dr))
+    def _norm_slot(self, b, name):
+        return self._ln_slot.get(name) if b.defer_norms else None
 
-        has_drop = p > 0
-        dY1 = g["drm"] if has_drop else g["dr"]     # ungrouped route: ONE buffer for the masked gradient that enters a branch
-        gx = False
-        # no reducer waits for the encoder.norm / cross buckets: the gain / bias partials of the two norms outside the layers
-        # are summed by the grouped reduce launch at the end of backward instead of a 16-workgroup launch each
-        defer_norms = grouped and not pieced and on_segment is None and self._wg_plan["whole_norms"] is not None
-        nslot = lambda n: self._ln_slot.get(n) if defer_norms else None
-        if cfg.use_cross_attention:
-            xs = _layer_sites(Lr)
-            gx = grouped and self._wg_cross                     # its weight gradients ride in the grouped launch
-            drm = g["dYo_x"] if gx else dY1
-            drx = self.ln_bwd_residual(dz, a["rx"], a["stx"], "cross_attn.norm", drm, (p, xs["drop1"]), slot=nslot("cross_attn.norm"))
-            attn_block_bwd("x", a["zn"], drx, drm, B, xs["attn"], other, g["dqkv_x"] if gx else g["dqkv"], gx)
-            dz, other = other, dz
-            if not gx:
-                seg("cross")
-        # final encoder norm (A:328)
-        self.ln_bwd(dz, a[f"x{Lr}"], a["stf"], "encoder.norm", other, slot=nslot("encoder.norm"))
-        dz, other = other, dz
-        seg("encoder.norm")
-        for l in reversed(range(Lr)):
-            pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
-            # with the grouped weight-gradient launch every layer keeps its own dY operands until the end of backward
-            dYf = g[f"dYf{l}"] if grouped else dY1
-            dYo = g[f"dYo{l}"] if grouped else dY1
-            dh = g[f"dh{l}"] if grouped else g["dh"]
-            dqkv = g[f"dqkv{l}"] if grouped else g["dqkv"]
-            s2 = self._ln_slot[pre + "ln2"] if grouped else None
-            s1 = self._ln_slot[pre + "ln1"] if grouped else None
-            dr = self.ln_bwd_residual(dz, a[f"r2_{l}"], a[f"st2_{l}"], pre + "ln2", dYf, (p, sites["ffn_b"]), (p, sites["drop2"]),
-                                      slot=s2)
-            if not grouped:
-                self.wgrad(ptr(dYf), ptr(a[f"hff{l}"]), 0, M, d, F, linear=[pre + "ffn.linear2"])
-            if self.fuse_ffn:
-                # dH = gate(dY W2) (stored: the weight gradients read it) and dy1 = dH W1 + dr in one launch; the gate is the
-                # bit image the forward launch of this layer left
-                self.ffn(ptr(dYf), ptr(w[f"w2Tf{l}"]), ptr(w[f"w1Tf{l}"]), ptr(dh), ptr(g["dy1"]), M, F, residual=ptr(dr),
-                         bits_in=ptr(a[f"gbits{l}"]), gate_scale=sc)
-            else:
-                self.gemm(ptr(dYf), ptr(w[f"w2T{l}"]), ptr(dh), M, F, d, gate=ptr(a[f"hff{l}"]), gate_scale=sc)
-            if not grouped:
-                self.wgrad(ptr(dh), ptr(a[f"y1_{l}"]), 0, M, F, d, linear=[pre + "ffn.linear1"])
-            if not self.fuse_ffn:
-                self.gemm(ptr(dh), ptr(w[f"w1T{l}"]), ptr(g["dy1"]), M, d, F, residual=ptr(dr))
-            if self.ln_proj:        # norm1 backward + out_proj backward-data in one launch
-                self.ln_bwd_proj(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", w[f"oTf{l}"], g["dr"], dYo, g["dctx"],
-                                 d1=(p, sites["drop1"]) if has_drop else (0.0, 0), slot=s1)
-                dr = g["dr"]
-            else:
-                dr = self.ln_bwd_residual(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", dYo, (p, sites["drop1"]), slot=s1)
-            attn_block_bwd(l, a[f"x{l}"], dr, dYo, 0, sites["attn"], other, dqkv, grouped, dctx_done=self.ln_proj)
-            dz, other = other, dz
-            if not grouped:
-                seg(f"layer{l}")
-            elif pieced and l == self._wg_plan["split_layer"]:
-                # upper half of the encoder: its weight gradients are complete -> reduce them now, hand the buckets to the
-                # all-reduce while the lower layers' backward-data chain keeps the compute stream busy
-                self._wgrad_group_launch(self._wg_plan["pieces"][0], seg, gx)
-        if grouped and pieced:
-            self._wgrad_group_launch(self._wg_plan["pieces"][1], seg)
-        elif grouped:
-            self._wgrad_group_launch(self._wg_plan["whole_norms"] if defer_norms else None, seg, gx)
-        dseq = dz
-        # positional table / cls token (A:120-126, D:1157)
+    def _cross_bwd(self, b, dz, free):
+        a, g, xs = self.a, self.g, _layer_sites(self.cfg.num_layers)
+        drm = g["dYo_x"] if b.gx else b.dY1      # gx: its weight gradients ride in the grouped launch
+        drx = self.ln_bwd_residual(dz, a["rx"], a["stx"], "cross_attn.norm", drm, (b.p, xs["drop1"]),
+                                   slot=self._norm_slot(b, "cross_attn.norm"))
+        self._attn_stage_bwd(b, "x", a["zn"], drx, drm, self.B, xs["attn"], free, g["dqkv_x"] if b.gx else g["dqkv"], b.gx)
+        if not b.gx:
+            b.seg("cross")
+        return free, dz
+
+    def _final_norm_bwd(self, b, dz, free):
+        """final encoder norm (A:328)"""
+        self.ln_bwd(dz, self.a[f"x{self.cfg.num_layers}"], self.a["stf"], "encoder.norm", free, slot=self._norm_slot(b, "encoder.norm"))
+        b.seg("encoder.norm")
+        return free, dz
+
+    def _layer_bwd(self, b, l, dz, free):
+        M, d, F, a, w, g, p, grouped = self.M, self.cfg.d_model, self.cfg.d_ff, self.a, self.w, self.g, b.p, b.grouped
+        pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
+        # with the grouped weight-gradient launch every layer keeps its own dY operands until the end of backward
+        dYf = g[f"dYf{l}"] if grouped else b.dY1
+        dYo = g[f"dYo{l}"] if grouped else b.dY1
+        dh = g[f"dh{l}"] if grouped else g["dh"]
+        dqkv = g[f"dqkv{l}"] if grouped else g["dqkv"]
+        s2 = self._ln_slot[pre + "ln2"] if grouped else None
+        s1 = self._ln_slot[pre + "ln1"] if grouped else None
+        dr = self.ln_bwd_residual(dz, a[f"r2_{l}"], a[f"st2_{l}"], pre + "ln2", dYf, (p, sites["ffn_b"]), (p, sites["drop2"]),
+                                  slot=s2)
+        if not grouped:
+            self.wgrad(ptr(dYf), ptr(a[f"hff{l}"]), 0, M, d, F, linear=[pre + "ffn.linear2"])
+        if self.fuse_ffn:
+            # dH = gate(dY W2) (stored: the weight gradients read it) and dy1 = dH W1 + dr in one launch; the gate is the
+            # bit image the forward launch of this layer left
+            self.ffn(ptr(dYf), ptr(w[f"w2Tf{l}"]), ptr(w[f"w1Tf{l}"]), ptr(dh), ptr(g["dy1"]), M, F, residual=ptr(dr),
+                     bits_in=ptr(a[f"gbits{l}"]), gate_scale=b.sc)
+        else:
+            self.gemm(ptr(dYf), ptr(w[f"w2T{l}"]), ptr(dh), M, F, d, gate=ptr(a[f"hff{l}"]), gate_scale=b.sc)
+        if not grouped:
+            self.wgrad(ptr(dh), ptr(a[f"y1_{l}"]), 0, M, F, d, linear=[pre + "ffn.linear1"])
+        if not self.fuse_ffn:
+            self.gemm(ptr(dh), ptr(w[f"w1T{l}"]), ptr(g["dy1"]), M, d, F, residual=ptr(dr))
+        if self.ln_proj:        # norm1 backward + out_proj backward-data in one launch
+            self.ln_bwd_proj(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", w[f"oTf{l}"], g["dr"], dYo, g["dctx"],
+                             d1=(p, sites["drop1"]) if b.has_drop else (0.0, 0), slot=s1)
+            dr = g["dr"]
+        else:
+            dr = self.ln_bwd_residual(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", dYo, (p, sites["drop1"]), slot=s1)
+        self._attn_stage_bwd(b, l, a[f"x{l}"], dr, dYo, 0, sites["attn"], free, dqkv, grouped, dctx_done=self.ln_proj)
+        if not grouped:
+            b.seg(f"layer{l}")
+        elif b.pieced and l == self._wg_plan["split_layer"]:
+            # upper half of the encoder: its weight gradients are complete -> reduce them now, hand the buckets to the
+            # all-reduce while the lower layers' backward-data chain keeps the compute stream busy
+            self._wgrad_group_launch(self._wg_plan["pieces"][0], b.seg, b.gx)
+        return free, dz
+
+    def _wgrad_group_bwd(self, b):
+        """the grouped weight-gradient launch, or the second of its two pieces, once every layer's operands are complete"""
+        if b.grouped and b.pieced:
+            self._wgrad_group_launch(self._wg_plan["pieces"][1], b.seg)
+        elif b.grouped:
+            self._wgrad_group_launch(self._wg_plan["whole_norms"] if b.defer_norms else None, b.seg, b.gx)
+
+    def _front_end_bwd(self, b, dseq):
+        """The gradient of the token rows -> positional table / cls token (A:120-126, D:1157), the token families, conv-1, conv-0"""
+        d, NB, S, a, g, fp, es, st, sc01 = self.cfg.d_model, self.NB, self.S, self.a, self.g, self.fp, self.es, self.stream, b.sc01
         # conv1 backward: dY = dseq[:, off:, :] * relu/dropout gate
         ymap = rowmap(d, self.RY * d, self.T2)
-        fused_tokens = bool(self.fused_tail) and self.dtype != EG_F32 and d % 64 == 0
-        if fused_tokens:        # ONE pass over dseq: position sums, the cls_token copy and conv-1's gated dY rows
-            call("eg_token_grad_tail", ptr(dseq), ptr(a["h1"]), ptr(g["dy1pad"]) + (self.J - 1) * d * es, ymap,
+        dy1 = ptr(g["dy1pad"]) + (self.J - 1) * d * es
+        if b.fused_tokens:      # ONE pass over dseq: position sums, the cls_token copy and conv-1's gated dY rows
+            call("eg_token_grad_tail", ptr(dseq), ptr(a["h1"]), dy1, ymap,
                  fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), NB, S, d, self.T2, self.off, sc01, self.dtype, st)
         else:
             call("eg_batch_rowsum", ptr(dseq), fp.g_ptr("pos_embed.pos_embed.weight"), NB, S, d, S, self.dtype, st)
             call("eg_cast", fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), d, EG_F32, st)
         self.model._extra_tokens_bwd(self, dseq)
-        seg("tokens")           # positions, token generators, the extra heads: everything registered between conv-1 and the encoder
-        if not fused_tokens:
-            call("eg_rows_gather_gate", ptr(dseq), ptr(a["h1"]), ptr(g["dy1pad"]) + (self.J - 1) * d * es, ymap, NB, S, d,
+        b.seg("tokens")         # positions, token generators, the extra heads: everything registered between conv-1 and the encoder
+        if not b.fused_tokens:
+            call("eg_rows_gather_gate", ptr(dseq), ptr(a["h1"]), dy1, ymap, NB, S, d,
                  self.T2, self.off, 0, sc01, self.dtype, st)
-        dy1 = ptr(g["dy1pad"]) + (self.J - 1) * d * es
         self.wgrad(dy1, ptr(a["h0pad"]), fp.g_ptr("temporal_conv.convs.1.weight"), NB * self.T2, d, self.k * d, y=ymap,
                    x=rowmap(self.s * d, self.R0 * d, self.T2), out_b=fp.g_ptr("temporal_conv.convs.1.bias"),
                    conv=(d, self.k, d))
-        seg("conv1")            # 6.5 MB of the front end's 7 MB: reduces under the backward-data phases and conv-0's gradient
+        b.seg("conv1")          # 6.5 MB of the front end's 7 MB: reduces under the backward-data phases and conv-0's gradient
         self.conv1_bwd_data(sc01)
         h0map = rowmap(d, self.R0 * d, self.T1)
         self.wgrad(ptr(g["dh0pad"]) + self.pad * d * es, ptr(a["xt"]), fp.g_ptr("temporal_conv.convs.0.weight"),
                    NB * self.T1, d, self.K0, y=h0map, x=rowmap(self.s * self.Cp, self.Tp * self.Cp, self.T1),
                    out_b=fp.g_ptr("temporal_conv.convs.0.bias"), conv=(self.C, self.k, self.Cp))
-        seg("frontend")
+        b.seg("frontend")
 
     # ------------------------------------------------------------------------------------------
     # gradient accumulation: one optimiser step from several micro-batches (no reference counterpart: T is one batch per step)
@@ -1347,32 +1464,16 @@ class Engine(EngineBase):
 # ------------------------------------------------------------------------------------------------
 # forward-only route
 # ------------------------------------------------------------------------------------------------
-def _front_end_dims(cfg, T: int, dtype: int):
-    """(Cp, Tp, R0, T2) of the convolution front end at window length T: Engine.__init__'s arithmetic, device-free"""
-    k, s = cfg.conv_kernel_size, cfg.conv_stride
-    pad, bk = k // 2, (32 if dtype == EG_F32 else 64)
-    Cp = _align(cfg.in_channels, 8)
-    T1 = (T + 2 * pad - k) // s + 1
-    T2 = (T1 + 2 * pad - k) // s + 1
-    K0 = _align(k * Cp, bk)
-    Tp = _align(max(T + 2 * pad, s * (T1 - 1) + K0 // Cp + 1), 8)
-    return Cp, Tp, (T1 + 2 * pad + s - 1) // s * s, T2
-
-
 def _inference_tensors(cfg, B: int, T: int, dtype: int):
-    """The inference engine's own workspace, device-free: ({name: (shape, 16-bit-or-compute?)}, same for the shared scratch set).
-    An entry is (shape, is_f32); compute-dtype tensors have is_f32 False.  InferenceEngine allocates exactly these."""
-    d, F, H, nc = cfg.d_model, cfg.d_ff, cfg.num_heads, cfg.num_classes
+    """The inference engine's own workspace, device-free: ({name: (shape, is fp32)}, same for the shared scratch set);
+    compute-dtype tensors have is fp32 False.  InferenceEngine allocates exactly these."""
+    d, F, H = cfg.d_model, cfg.d_ff, cfg.num_heads
+    geo = geometry(cfg, T, dtype)
     NB, S = 2 * B, sequence_length(cfg, T)
     M = NB * S
-    Cp, Tp, R0, _ = _front_end_dims(cfg, T, dtype)
-    a = {"xt": ((NB, Tp, Cp), False), "h0pad": ((NB, R0, d), False),
+    a = {"xt": ((NB, geo.Tp, geo.Cp), False), "h0pad": ((NB, geo.R0, d), False),
          "xa": ((M, d), False), "xb": ((M, d), False), "y1": ((M, d), False),       # layer input / output ping-pong, normed mid-layer rows
-         "cls1": ((B, d), True), "cls2": ((B, d), True), "comb": ((B, 3 * d), False), "zf": ((B, 3 * d), False), "hcl": ((B, d), False),
-         "logits": ((B, nc), True), "sloss": ((B,), True), "loss": ((1,), True)}
-    if cfg.use_ibs:
-        a.update({"ibs_pool_f": ((B, d), True), "ibs_pool": ((B, d), False), "hib": ((B, d // 2), False),
-                  "ibs_logits": ((B, nc), True), "ibs_sloss": ((B,), True), "ibs_loss": ((1,), True)})
+         **_head_tensors(cfg, B)}
     sc = {"qkv": ((M, 3 * d), False), "lse": ((NB, H, S), True), "ctx": ((M, d), False), "r": ((M, d), False),
           "hff": ((M, F), False), "st": ((M, 2), True)}
     return a, sc
@@ -1385,50 +1486,30 @@ def inference_workspace_bytes(cfg, B: int, T: int, dtype: int) -> Tuple[int, int
     es = 4 if dtype == EG_F32 else 2
     a, sc = _inference_tensors(cfg, B, T, dtype)
 
-    def nbytes(tab):
-        total = 0
-        for shape, f32 in tab.values():
-            n = 1
-            for x in shape:
-                n *= x
-            total += n * (4 if f32 else es)
-        return total
-    lean = nbytes(a)
-    return lean + nbytes(sc), lean
+    lean, scratch = (sum(math.prod(shape) * (4 if f32 else es) for shape, f32 in tab.values()) for tab in (a, sc))
+    return lean + scratch, lean
 
 
-class InferenceEngine(Engine):
+class InferenceEngine(ForwardEngine):
     """Forward-only engine for a fixed (B, T): predicts without saving what a backward would read.  No per-layer activations (two
     ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts, always p = 0, and
     it neither reads nor writes the model's step state, forward counter or seeds.  Where a layer half has a lean launch
     (eg_attn_block_fwd / eg_ffn_chain with only ln_out stored) it takes it; every other launch is the training engine's, writing
     into ONE shared scratch set allocated on first need.  Same bits as Engine.forward(train=False)."""
-    inference = True
+    TRAINING_CALLS = ("backward", "accumulate", "optimizer_step", "set_state", "check_overflow_and_update_scaler")
 
     def _init_state(self, state_dev):
         # a private all-zero state that no launch writes: at p = 0 no kernel reads a seed, and eg_set_step_state is never called
         self.state_dev = torch.zeros(L.STATE_WORDS, dtype=torch.int32, device=self.device)
 
+    def _held(self, group, l, every: bool):
+        """Only what the forward reads: each forward layout, or in its place the fragment layout that the fused route reads instead"""
+        return [lay if self._reads(lay, l) else _FUSED_TWIN[lay.key] for lay in group if not (lay.bwd or lay.fused)]
+
     def _alloc(self):
-        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
-        f32 = torch.float32
-        w = {"conv0": self._t(d, self.K0), "conv1": self._t(d, self.k * d), "pos": self._t(cfg.max_len, d)}
-        for l in list(range(cfg.num_layers)) + (["x"] if cfg.use_cross_attention else []):
-            w[f"bqkv{l}"] = self._t(3 * d, dtype=f32)
-            if self.attn_block and l != "x":
-                w[f"wqkvb{l}"], w[f"wob{l}"] = self._t(3 * d * d), self._t(d * d)
-            else:
-                w[f"qkv{l}"], w[f"o{l}"] = self._t(3 * d, d), self._t(d, d)
-            if l != "x" and self.fuse_ffn:
-                w[f"w1f{l}"], w[f"w2f{l}"] = self._t(F * d), self._t(F * d)
-            elif l != "x":
-                w[f"w1{l}"], w[f"w2{l}"] = self._t(F, d), self._t(d, F)
-        w["sf"], w["c0"] = self._t(d, 3 * d), self._t(d, 3 * d)
-        if cfg.use_ibs:
-            w["i0"] = self._t(d // 2, d)
-        self.w = w
-        shapes, self._sc_shapes = _inference_tensors(cfg, self.B, self.T, self.dtype)
-        a = {n: self._t(*shape, dtype=(f32 if is32 else None)) for n, (shape, is32) in shapes.items()}
+        self.w = self._alloc_w()
+        shapes, self._sc_shapes = _inference_tensors(self.cfg, self.B, self.T, self.dtype)
+        a = {n: self._t(*shape, dtype=(torch.float32 if is32 else None)) for n, (shape, is32) in shapes.items()}
         a["x0"] = a["xa"]                                  # the front end and the token families write the token rows here
         a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)
         self.a = a
@@ -1441,106 +1522,36 @@ class InferenceEngine(Engine):
             self.sc[name] = self._t(*shape, dtype=(torch.float32 if is32 else None))
         return self.sc[name]
 
-    def _attn_stage(self, l):
-        pre = "cross_attn.cross_attn." if l == "x" else f"encoder.layers.{l}.mha."
-        return pre, self._scratch("qkv"), self._scratch("lse"), self._scratch("ctx"), self._scratch("r")
-
-    def _pack_body(self):
-        """Only the layouts the forward reads (Engine._pack_body's forward half, by the same routes)"""
-        cfg, d, F, fp, w = self.cfg, self.cfg.d_model, self.cfg.d_ff, self.fp, self.w
-        self.p_conv(fp.p_ptr("temporal_conv.convs.0.weight"), ptr(w["conv0"]), d, self.C, self.k, self.Cp, self.K0)
-        self.p_conv(fp.p_ptr("temporal_conv.convs.1.weight"), ptr(w["conv1"]), d, d, self.k, d, self.k * d)
-        self.p_cast(fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["pos"]), cfg.max_len * d)
-        for l in list(range(cfg.num_layers)) + (["x"] if cfg.use_cross_attention else []):
-            pre = "cross_attn.cross_attn." if l == "x" else f"encoder.layers.{l}.mha."
-            block = self.attn_block and l != "x"
-            for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                if block:
-                    self.p_frag(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"wqkvb{l}"]), d, d, 7, part=i)
-                else:
-                    self.p_cast(fp.p_ptr(f"{pre}{n}.weight"), ptr(w[f"qkv{l}"]) + i * d * d * self.es, d * d)
-                self.p_copy(fp.p_ptr(f"{pre}{n}.bias"), ptr(w[f"bqkv{l}"]) + 4 * i * d, d)
-            if block:
-                self.p_frag(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"wob{l}"]), d, d, 8)
-            else:
-                self.p_cast(fp.p_ptr(f"{pre}out_proj.weight"), ptr(w[f"o{l}"]), d * d)
-            if l == "x":
-                continue
-            pre = f"encoder.layers.{l}.ffn."
-            if self.fuse_ffn:
-                self.p_frag(fp.p_ptr(pre + "linear1.weight"), ptr(w[f"w1f{l}"]), F, d, 3)
-                self.p_frag(fp.p_ptr(pre + "linear2.weight"), ptr(w[f"w2f{l}"]), d, F, 5)
-            else:
-                self.p_cast(fp.p_ptr(pre + "linear1.weight"), ptr(w[f"w1{l}"]), F * d)
-                self.p_cast(fp.p_ptr(pre + "linear2.weight"), ptr(w[f"w2{l}"]), d * F)
-        self.p_cast(fp.p_ptr("symmetric_fusion.proj.weight"), ptr(w["sf"]), 3 * d * d)
-        self.p_cast(fp.p_ptr("classifier.0.weight"), ptr(w["c0"]), 3 * d * d)
-        if cfg.use_ibs:
-            self.p_cast(fp.p_ptr("ibs_classifier.0.weight"), ptr(w["i0"]), (d // 2) * d)
-        self.model._pack_extra(self)
+    def _rows(self, l, x) -> Rows:
+        """Stage l's rows: the output goes to the one of the ping-pong pair that x is not (the pair also serves the final norm and
+        the cross-attention stage), the normed mid-layer rows to y1, and everything else either nowhere -- the lean launch: fused
+        block, LayerNorm fused, no hook on that layer / feed-forward chain, LayerNorm fused -- or into the shared scratch set."""
+        a, s = self.a, self._scratch
+        out = a["xb"] if x is a["xa"] else a["xa"]
+        if l == "norm":
+            return Rows(st2=s("st"), out=out)
+        if l == "x":
+            return Rows(s("qkv"), s("lse"), s("ctx"), s("r"), s("st"), out=out)
+        drop = self.model.encoder.layers[l].mha.dropout
+        lean_attn = self.attn_block and self.ln_fuse and not (drop._forward_hooks or drop._forward_pre_hooks)
+        lean_ffn = self.fuse_ffn and self.ln_fuse
+        self.routes_taken += [(l, "attn", "lean" if lean_attn else "scratch"), (l, "ffn", "lean" if lean_ffn else "scratch")]
+        attn = (None,) * 5 if lean_attn else (s("qkv"), s("lse"), s("ctx"), s("r"), s("st"))
+        ffn = (None,) * 4 if lean_ffn else (s("hff"), None, s("r"), s("st"))
+        return Rows(*attn, a["y1"], *ffn, out)
 
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None, pack: bool = True):
         """pack=False: the packed weights of an earlier call still hold (a caller walking many batches packs once)"""
-        cfg, d, F = self.cfg, self.cfg.d_model, self.cfg.d_ff
-        B, M, a, w, fp = self.B, self.M, self.a, self.w, self.fp
-        self.stream = self._cur_stream()
-        self.train_flags = (0.0, 0.0, False)
         self.routes_taken = []
-        if pack or self._plan_key is None:
-            self.pack_params()
-        self._front_end_fwd(eeg1, eeg2, False, 0.0, None)
-        xin, xout, y1 = a["xa"], a["xb"], a["y1"]
-        for l in range(cfg.num_layers):
-            pre, sites = f"encoder.layers.{l}.", _layer_sites(l)
-            drop = self.model.encoder.layers[l].mha.dropout
-            lean_attn = self.attn_block and self.ln_fuse and not (drop._forward_hooks or drop._forward_pre_hooks)
-            if lean_attn:
-                self.attn_block_fwd(xin, l, 0.0, sites, ln=(pre + "ln1", y1, None), lean=True)
-            elif self.attn_block:
-                self.attn_block_fwd(xin, l, 0.0, sites, ln=((pre + "ln1", y1, self._scratch("st")) if self.ln_fuse else None))
-                self._probs_hook(drop, self._scratch("qkv"), self._scratch("lse"), 0)
-            else:
-                self.attn_unfused_fwd(xin, l, 0, sites, 0.0)
-            if not (self.attn_block and self.ln_fuse):
-                self.ln_fwd(self._scratch("r"), pre + "ln1", y1, self._scratch("st"))
-            self.routes_taken.append((l, "attn", "lean" if lean_attn else "scratch"))
-            b1, b2 = fp.p_ptr(pre + "ffn.linear1.bias"), fp.p_ptr(pre + "ffn.linear2.bias")
-            if self.fuse_ffn and self.ln_fuse:
-                self.ffn(ptr(y1), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), 0, 0, M, F, bias1=b1, bias2=b2, act1=L.ACT_RELU,
-                         residual=ptr(y1), ln=(pre + "ln2", xout, None))
-            elif self.fuse_ffn:
-                self.ffn(ptr(y1), ptr(w[f"w1f{l}"]), ptr(w[f"w2f{l}"]), ptr(self._scratch("hff")), ptr(self._scratch("r")), M, F,
-                         bias1=b1, bias2=b2, act1=L.ACT_RELU, residual=ptr(y1))
-            else:
-                self.ffn_unfused_fwd(y1, l, self._scratch("hff"), self._scratch("r"), 0.0, sites)
-            if not (self.fuse_ffn and self.ln_fuse):
-                self.ln_fwd(self._scratch("r"), pre + "ln2", xout, self._scratch("st"))
-            self.routes_taken.append((l, "ffn", "lean" if (self.fuse_ffn and self.ln_fuse) else "scratch"))
-            xin, xout = xout, xin
-        # the ping-pong pair also serves the final norm (zn) and the cross-attention stage's output (zc)
-        self.ln_fwd(xin, "encoder.norm", xout, self._scratch("st"))
-        z, free = xout, xin
-        if cfg.use_cross_attention:
-            self.attn_unfused_fwd(z, "x", B, _layer_sites(cfg.num_layers), 0.0)
-            self.ln_fwd(self._scratch("r"), "cross_attn.norm", free, self._scratch("st"))
-            z = free
-        self._heads_fwd(z, labels, False, 0.0)
+        self._forward(eeg1, eeg2, labels, False, pack=pack or self._plan_key is None)
 
-    def _refuse(self, what):
-        raise L.EgError(f"{what}() on an inference engine: it keeps no activations and has no backward workspace "
+
+def _refused(name: str):
+    def method(self, *a, **k):
+        raise L.EgError(f"{name}() on an inference engine: it keeps no activations and has no backward workspace "
                         "(use DualEEGTransformer.forward / Engine for training)")
+    return method
 
-    def backward(self, *a, **k):
-        self._refuse("backward")
 
-    def accumulate(self, *a, **k):
-        self._refuse("accumulate")
-
-    def optimizer_step(self, *a, **k):
-        self._refuse("optimizer_step")
-
-    def set_state(self, *a, **k):
-        self._refuse("set_state")
-
-    def check_overflow_and_update_scaler(self):
-        self._refuse("check_overflow_and_update_scaler")
+for _name in InferenceEngine.TRAINING_CALLS:
+    setattr(InferenceEngine, _name, _refused(_name))

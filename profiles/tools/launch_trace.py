@@ -24,8 +24,8 @@ class Recorder:
         """(lo, hi, name, tensor) of every workspace / parameter / table tensor alive now (backward allocates lazily)"""
         out = {}
         for tag, e in self.engines:
-            for kind in ("a", "w", "g"):
-                out.update({f"{tag}{kind}.{k}": v for k, v in getattr(e, kind).items()})
+            for kind in ("a", "w", "g", "sc"):          # sc: the inference engine's shared scratch set
+                out.update({f"{tag}{kind}.{k}": v for k, v in getattr(e, kind, {}).items()})
             out.update({tag + "flat": e.fp.flat, tag + "grad": e.fp.grad, tag + "acc": e.fp.acc, tag + "state": e.state_dev,
                         tag + "plan_dev": getattr(e, "_plan_dev", None)})
             plan = getattr(e, "_wg_plan", None)
@@ -84,7 +84,7 @@ def main():
         if not m.name.startswith(("lib", "build")):     # (the shared library itself is listed as a module)
             importlib.import_module(f"{pkg.__name__}.{m.name}")
     from eyegaze_multimodal_amd import DualEEGTransformer
-    from eyegaze_multimodal_amd.engine import Engine
+    from eyegaze_multimodal_amd.engine import Engine, InferenceEngine
     from eyegaze_multimodal_amd.fuzzy_gating_fusion import FuzzyGatingFusion
     from eyegaze_multimodal_amd.image_encoder import GazeCNNEncoder, ImageEngine
     from eyegaze_multimodal_amd.train_multimodal_fuzzy_fusion import MultimodalFusionModel, MultimodalTrainer
@@ -132,6 +132,24 @@ def main():
                 eng.optimizer_step(m, v, **(dict(accumulated=True, norm_ready=True) if mode == "accum" else {}))
         return run
 
+    def infer(dt, B=4, T=1024, kw=None, golden=None, hook=False):
+        """two forwards of the forward-only engine, the second with pack=False; hook: a forward hook on layer 0's attention dropout"""
+        def run():
+            if golden:
+                from tests.helpers import load_golden
+                model = DualEEGTransformer(**load_golden(golden)[1])
+            else:
+                model = DualEEGTransformer(**{**dict(in_channels=8, max_len=256), **(kw or {})})
+            model._flat.ensure(cpu, need_grad=False)
+            eng = InferenceEngine(model, B, T, cpu, DT[dt])
+            x, y = torch.zeros(B, model.cfg.in_channels, T), torch.zeros(B, dtype=torch.long)
+            rec.engines, rec.extra = [("", eng)], [lambda: dict(x=x, labels=y)]
+            if hook:
+                model.encoder.layers[0].mha.dropout.register_forward_hook(lambda mod, inp, out: None)
+            eng.forward(x, x, y)
+            eng.forward(x, x, y, pack=False)
+        return run
+
     def image(dt):
         def run():
             model = GazeCNNEncoder(compute_dtype=dt)
@@ -176,6 +194,19 @@ def main():
     case("h_accum", eeg("bf16", mode="accum"))
     case("h_fp16_overflow", eeg("fp16", mode="overflow"))
     case("j_multimodal_trainer", trainer)
+    # the forward-only engine: the four shapes of tests/test_infer_host.py::INFER_CASES, the switches, a hooked layer
+    case("k_infer_cfg3", infer("bf16", golden="cfg3_xattn"))
+    case("k_infer_a5_full", infer("bf16", golden="a5_full"))
+    case("k_infer_long_S257", infer("bf16", B=2, T=4096, kw=LONG))
+    case("k_infer_f32", infer("f32", golden="cfg3_xattn"))
+    for k in ("EYEGAZE_LN_FUSE", "EYEGAZE_ATTN_BLOCK"):
+        case(f"k_infer_{k}=0", infer("bf16", kw=SMALL), env={k: "0"})
+    case("k_infer_hook", infer("bf16", kw=SMALL, hook=True))
+    # 64-wide heads: a training step and an inference forward (the grouped weight-gradient launch, with and without a listener,
+    # is already in a_* / f_*: M = 64 * 115 rows is above GROUP_MIN_ROWS)
+    WIDE = dict(SMALL, d_model=256, num_heads=4)
+    case("l_wide_step", eeg("bf16", **WIDE))
+    case("l_wide_infer", infer("bf16", kw=WIDE))
     with open(args.out, "w") as f:
         json.dump(cases, f, indent=0)
     print(json.dumps({"cases": len(cases), "rows": sum(len(r) for r in cases.values()),

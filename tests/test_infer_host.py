@@ -126,6 +126,13 @@ def test_macro_metrics_from_the_confusion_matrix_reference_known_answer():
 BACKWARD_LAYOUTS = ("qkvT", "oT", "oTf", "w1T", "w2T", "w1Tf", "w2Tf", "conv1T", "sfT", "c0T", "i0T")
 
 
+def test_the_layout_table_marks_exactly_these_layouts_as_the_backward_s():
+    from eyegaze_multimodal_amd import engine as E
+    rows = [lay for groups in E.LAYOUTS.values() for group in groups for lay in group]
+    assert sorted(lay.key for lay in rows if lay.bwd) == sorted(BACKWARD_LAYOUTS)
+    assert len({lay.key for lay in rows}) == len(rows)
+
+
 def golden_kwargs(name):
     from tests.helpers import load_golden
     return load_golden(name)[1]
@@ -198,6 +205,34 @@ def test_inference_engine_launches_stay_inside_what_it_holds(case):
         assert eng.S == 257 and eng.attn_long
     if case == "cfg3":
         assert {how for _, _, how in eng.routes_taken} == {"lean"} and "hff" not in eng.sc
+
+
+SMALL_LN_UNFUSED = (lambda: dict(in_channels=8, max_len=256, use_spectrogram=False, use_ibs=False), L.EG_BF16, 4, 1024)
+
+
+@pytest.mark.parametrize("case", sorted(INFER_CASES) + ["small_ln_unfused"])
+def test_inference_forward_issues_the_entry_points_of_an_eval_forward(case, monkeypatch):
+    """Engine.forward(train=False) and InferenceEngine.forward call the same entry points in the same order once the pack launches
+    (eg_pack*: the inference engine packs fewer layouts, through the same table launch) are set aside"""
+    from eyegaze_multimodal_amd import DualEEGTransformer, engine as E, tokens
+    if case == "small_ln_unfused":
+        monkeypatch.setenv("EYEGAZE_LN_FUSE", "0")
+    kw, dtype, B, T = SMALL_LN_UNFUSED if case == "small_ln_unfused" else INFER_CASES[case]
+    names = []
+    for m in (E, tokens):
+        monkeypatch.setattr(m, "call", lambda name, *args: names.append(name) if name != "eg_pack_table_ex_check" else L.call(name, *args))
+    issued = {}
+    for cls in (E.Engine, E.InferenceEngine):
+        model = DualEEGTransformer(**kw())
+        cpu = torch.device("cpu")
+        model._flat.ensure(cpu, need_grad=cls is E.Engine)
+        eng = cls(model, B, T, cpu, dtype)
+        assert eng.ln_fuse == (case != "small_ln_unfused")
+        x, y = torch.zeros(B, model.cfg.in_channels, T), torch.zeros(B, dtype=torch.long)
+        del names[:]
+        eng.forward(x, x, y, train=False) if cls is E.Engine else eng.forward(x, x, y)
+        issued[cls] = [n for n in names if not n.startswith("eg_pack")]
+    assert len(issued[E.Engine]) > 20 and issued[E.InferenceEngine] == issued[E.Engine]
 
 
 def test_inference_engine_pointers_lie_inside_tensors_it_holds():
