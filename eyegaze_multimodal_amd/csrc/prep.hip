@@ -3,6 +3,9 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <algorithm>
+#include <cmath>
+
 #include "rowtile.h"      // rt_frag_elem: the fragment order that modes 3-8 write
 
 thread_local char eg_err_buf[512] = {0};
@@ -580,5 +583,155 @@ extern "C" int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, i
   hipLaunchKernelGGL(window_normalize_kernel, dim3(2 * N), dim3(256), mode ? (size_t)T * 4 : 0, (hipStream_t)stream, raw, eeg1,
                      eeg2, C, T, mode);
   EG_LAUNCH_CHECK("window_normalize");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Window augmentation of the training forward (include/eyegaze_hip.h: eg_window_augment states the index formulas): Gaussian
+// noise, channel dropout, time masks, all drawn from eg_hash -- the seed comes from eg_step_state, so a captured launch draws
+// anew at every replay.  Streaming: one WAVE takes AUG_SPAN consecutive samples of one row (player, window, channel), so the
+// row's drop decision and the window's at most 8 mask intervals are wave-uniform (scalar registers), computed once per unit.
+// A dropped row is written without being read; a 16-byte chunk that lies inside a mask is neither read nor given noise.
+// Every element is read and written by the same lane, so out may alias in.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t AUG_SPAN = 1024;   // samples per unit: 4 rounds of 16 bytes per lane (VEC), 16 rounds of 4 bytes otherwise
+
+struct AugMasks {
+  uint32_t start[8], len[8];          // len 0: unused
+};
+__device__ __forceinline__ bool aug_masked(const AugMasks& m, uint32_t t) {
+  bool z = false;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z |= (t - m.start[j]) < m.len[j];
+  return z;
+}
+// Box-Muller on pair q of the flat element index: n0 for the even element, n1 for the odd one
+__device__ __forceinline__ void aug_noise_pair(uint32_t lo, uint32_t hi, uint32_t q, float& n0, float& n1) {
+  const float u1 = ((float)(eg_hash(lo, hi, EG_SITE_AUG_NOISE_R, q) >> 9) + 0.5f) * 0x1p-23f;
+  const float u2 = (float)(eg_hash(lo, hi, EG_SITE_AUG_NOISE_T, q) >> 8) * 0x1p-24f;
+  const float r = sqrtf(-2.0f * logf(u1));
+  float s, c;
+  sincospif(2.0f * u2, &s, &c);
+  n0 = __fmul_rn(r, c);
+  n1 = __fmul_rn(r, s);
+}
+
+// VEC: T % 4 == 0 and 16-byte aligned buffers, so every row starts on a 16-byte boundary and on an even flat index
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_augment_kernel(const float* in1, const float* in2, float* out1, float* out2, int N,
+                                                             int C, int T, float noise_std, uint32_t chan_thresh, int n_masks,
+                                                             int mask_max_len, const eg_step_state* __restrict__ state) {
+  const uint32_t lo = state->seed_lo, hi = state->seed_hi;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const uint32_t NC = (uint32_t)N * (uint32_t)C;                  // rows per player; 2 NC T < 2^32 (host check)
+  const uint32_t Tn = (uint32_t)T, segs = (Tn + AUG_SPAN - 1) / AUG_SPAN;
+  const uint64_t units = 2ull * NC * segs;                        // <= 2 NC T
+  const uint32_t Lm = min((uint32_t)mask_max_len, Tn);
+  for (uint64_t u = (uint64_t)blockIdx.x * 4 + wave; u < units; u += (uint64_t)gridDim.x * 4) {
+    const uint32_t row = (uint32_t)u / segs, seg = (uint32_t)u % segs;
+    const uint32_t pl = row >= NC ? 1u : 0u, rp = row - pl * NC, w = rp / (uint32_t)C;
+    const float* src = (pl ? in2 : in1) + (size_t)rp * Tn;
+    float* dst = (pl ? out2 : out1) + (size_t)rp * Tn;
+    const uint32_t e0 = row * Tn;                                 // flat index of the row's first sample
+    const uint32_t t0 = seg * AUG_SPAN, t1 = min(t0 + AUG_SPAN, Tn);
+    bool dropped = false;
+    if (chan_thresh) {
+      const uint32_t h = eg_hash(lo, hi, EG_SITE_AUG_CHAN, row >> 1);
+      dropped = ((row & 1u) ? (h >> 16) : (h & 0xFFFFu)) < chan_thresh;
+    }
+    if (dropped) {
+      if (VEC) {
+        for (uint32_t t = t0 + lane * 4; t < t1; t += 256) *(f32x4*)(dst + t) = (f32x4){0.f, 0.f, 0.f, 0.f};
+      } else {
+        for (uint32_t t = t0 + lane; t < t1; t += 64) dst[t] = 0.f;
+      }
+      continue;
+    }
+    AugMasks m;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      m.start[j] = m.len[j] = 0;
+      if (j < n_masks) {
+        const uint32_t h = eg_hash(lo, hi, EG_SITE_AUG_TIME, w * 8u + j);
+        m.len[j] = 1u + (uint32_t)(((uint64_t)(h & 0xFFFFu) * Lm) >> 16);
+        m.start[j] = (uint32_t)(((uint64_t)(h >> 16) * (Tn - m.len[j] + 1u)) >> 16);
+      }
+    }
+    if (VEC) {
+      for (uint32_t t = t0 + lane * 4; t < t1; t += 256) {
+        bool z[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[i] = aug_masked(m, t + i);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (!(z[0] && z[1] && z[2] && z[3])) {
+          v = *(const f32x4*)(src + t);
+          if (noise_std > 0.f) {
+            const uint32_t q = (e0 + t) >> 1;
+            float n[4];
+            aug_noise_pair(lo, hi, q, n[0], n[1]);
+            aug_noise_pair(lo, hi, q + 1, n[2], n[3]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = __fmaf_rn(noise_std, n[i], v[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (z[i]) v[i] = 0.f;
+        }
+        *(f32x4*)(dst + t) = v;
+      }
+    } else {
+      for (uint32_t t = t0 + lane; t < t1; t += 64) {
+        float v = 0.f;
+        if (!aug_masked(m, t)) {
+          v = src[t];
+          if (noise_std > 0.f) {
+            const uint32_t e = e0 + t;
+            float n0, n1;
+            aug_noise_pair(lo, hi, e >> 1, n0, n1);
+            v = __fmaf_rn(noise_std, (e & 1u) ? n1 : n0, v);
+          }
+        }
+        dst[t] = v;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int eg_window_augment(const float* in1, const float* in2, float* out1, float* out2, int N, int C, int T, float noise_std,
+                                 float chan_drop_p, int n_masks, int mask_max_len, const eg_step_state* state, void* stream) {
+  EG_CHECK(in1 && in2 && out1 && out2, "eg_window_augment: null pointer (in1=%p in2=%p out1=%p out2=%p)", (const void*)in1,
+           (const void*)in2, (void*)out1, (void*)out2);
+  EG_CHECK(state, "eg_window_augment: null state (the seed is read from eg_step_state)");
+  EG_CHECK(N > 0 && C > 0 && T > 0, "eg_window_augment: bad shape N=%d C=%d T=%d", N, C, T);
+  EG_CHECK(std::isfinite(noise_std) && noise_std >= 0.f, "eg_window_augment: noise_std=%g must be finite and >= 0", (double)noise_std);
+  EG_CHECK(chan_drop_p >= 0.f && chan_drop_p < 1.f, "eg_window_augment: chan_drop_p=%g outside [0, 1)", (double)chan_drop_p);
+  EG_CHECK(n_masks >= 0 && n_masks <= 8, "eg_window_augment: n_masks=%d outside [0, 8]", n_masks);
+  EG_CHECK(n_masks == 0 || mask_max_len >= 1, "eg_window_augment: mask_max_len=%d must be >= 1 when n_masks > 0", mask_max_len);
+  const long long nc = (long long)N * C;
+  EG_CHECK(nc < (1ll << 31) && 2 * nc * T < (1ll << 32), "eg_window_augment: 2*N*C*T = 2*%d*%d*%d does not fit 32-bit element indices",
+           N, C, T);
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    const bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
+    cus = ok && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  // memory-bound: 8 blocks (32 waves) per CU cover the chip, the unit-stride loop takes the rest
+  const long long units = 2 * nc * ((T + (long long)AUG_SPAN - 1) / AUG_SPAN);
+  const dim3 gd((unsigned)std::min<long long>((units + 3) / 4, 8ll * cus)), bd(256);
+  const uint32_t thresh = make_drop(chan_drop_p, EG_SITE_AUG_CHAN).thresh;
+  const bool vec = T % 4 == 0 && ((uintptr_t)in1 | (uintptr_t)in2 | (uintptr_t)out1 | (uintptr_t)out2) % 16 == 0;
+  if (vec)
+    hipLaunchKernelGGL(window_augment_kernel<true>, gd, bd, 0, (hipStream_t)stream, in1, in2, out1, out2, N, C, T, noise_std, thresh,
+                       n_masks, mask_max_len, state);
+  else
+    hipLaunchKernelGGL(window_augment_kernel<false>, gd, bd, 0, (hipStream_t)stream, in1, in2, out1, out2, N, C, T, noise_std, thresh,
+                       n_masks, mask_max_len, state);
+  EG_LAUNCH_CHECK("window_augment");
   return 0;
 }

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import Engine, FlatParams, InferenceEngine
+from .engine import Engine, FlatParams, InferenceEngine, WindowAugmentation
 
 
 class _Holder(nn.Module):
@@ -245,6 +245,9 @@ class DualEEGTransformer(nn.Module):
         self._state_ready: Dict[str, bool] = {}
         self._fwd_count = 0
         self._seed_base = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
+        # training-time window augmentation (engine.WindowAugmentation or None): a plain attribute -- not a constructor argument, a
+        # parameter or a buffer -- read at the top of every TRAIN forward; eval forwards and predict() never look at it
+        self.augmentation: Optional[WindowAugmentation] = None
         from . import ops
         self._op_handle = ops.register_owner(self)     # the registered operators (ops.py) find this module by handle
 

@@ -22,6 +22,7 @@ What is stated once here:
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import os
 from collections import namedtuple
@@ -35,6 +36,43 @@ from ._lib import EG_BF16, EG_F16, EG_F32, GemmDesc, GemmTNDesc, StepState, call
 
 # dropout site ids (any fixed numbering works: the mask depends on (seed, site, element index))
 SITE_CONV0, SITE_CONV1, SITE_SPEC, SITE_IBSTOK, SITE_IBSGEN, SITE_CLS, SITE_IBSCLS = 1, 2, 3, 4, 5, 6, 7
+# eg_window_augment's own sites (EG_SITE_AUG_* of include/eyegaze_hip.h; the kernel names them, no call passes them)
+SITE_AUG_NOISE_R, SITE_AUG_NOISE_T, SITE_AUG_CHAN, SITE_AUG_TIME = 8, 9, 10, 11
+
+
+@dataclasses.dataclass(frozen=True)
+class WindowAugmentation:
+    """Training-time augmentation of the input windows (eg_window_augment): additive Gaussian noise, whole
+    channels zeroed without rescaling, `time_mask_num` zeroed intervals of 1 .. time_mask_max_length samples per window, the
+    same for both players.  Refuses what the C entry point refuses.  An instance with everything off is `not enabled`:
+    DualEEGTransformer.augmentation treats it as None."""
+    gaussian_noise_std: float = 0.0
+    channel_dropout_prob: float = 0.0
+    time_mask_max_length: int = 0
+    time_mask_num: int = 0
+
+    def __post_init__(self):
+        for name in ("gaussian_noise_std", "channel_dropout_prob"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{name} must be a number (got {v!r})")
+        for name in ("time_mask_max_length", "time_mask_num"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer (got {v!r})")
+        if not (math.isfinite(self.gaussian_noise_std) and self.gaussian_noise_std >= 0.0):
+            raise ValueError(f"gaussian_noise_std must be finite and >= 0 (got {self.gaussian_noise_std!r})")
+        if not 0.0 <= self.channel_dropout_prob < 1.0:
+            raise ValueError(f"channel_dropout_prob must lie in [0, 1) (got {self.channel_dropout_prob!r})")
+        if not 0 <= self.time_mask_num <= 8:
+            raise ValueError(f"time_mask_num must lie in [0, 8] (got {self.time_mask_num!r})")
+        if self.time_mask_max_length < (1 if self.time_mask_num > 0 else 0):
+            raise ValueError(f"time_mask_max_length must be >= 1 when time_mask_num > 0, and never negative "
+                             f"(got {self.time_mask_max_length!r})")
+
+    @property
+    def enabled(self) -> bool:
+        return self.gaussian_noise_std > 0.0 or self.channel_dropout_prob > 0.0 or self.time_mask_num > 0
 
 
 def scramble_seed(seed: int) -> int:
@@ -865,9 +903,23 @@ class ForwardEngine(EngineBase):
         token families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written)."""
         cfg, d = self.cfg, self.cfg.d_model
         B, NB, S, a, w, fp, es, st = self.B, self.NB, self.S, self.a, self.w, self.fp, self.es, self.stream
-        for i, x in enumerate((eeg1, eeg2)):
+        for x in (eeg1, eeg2):
             if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, self.C, self.T):
                 raise L.EgError(f"input windows must be contiguous f32 [{B},{self.C},{self.T}], got {tuple(x.shape)} {x.dtype}")
+        aug = getattr(self.model, "augmentation", None) if train else None
+        if aug is not None:
+            if not isinstance(aug, WindowAugmentation):
+                raise L.EgError(f"model.augmentation must be a WindowAugmentation or None, got {type(aug).__name__}")
+            if aug.enabled:
+                # one launch into the engine's own copy; everything below -- the pack, the token families -- reads the copy, the
+                # caller's tensors are never written.  The seed is this step's (eg_step_state), so a replayed graph draws anew.
+                if "aug" not in a:
+                    a["aug"] = torch.empty(2, B, self.C, self.T, device=self.device, dtype=torch.float32)
+                call("eg_window_augment", ptr(eeg1), ptr(eeg2), ptr(a["aug"][0]), ptr(a["aug"][1]), B, self.C, self.T,
+                     float(aug.gaussian_noise_std), float(aug.channel_dropout_prob), int(aug.time_mask_num),
+                     int(aug.time_mask_max_length), self.st_ptr, st)
+                eeg1, eeg2 = a["aug"][0], a["aug"][1]
+        for i, x in enumerate((eeg1, eeg2)):
             call("eg_window_pack", ptr(x), ptr(a["xt"]) + i * B * self.Tp * self.Cp * es, B, self.C, self.T, self.Cp,
                  self.pad, self.Tp, self.dtype, st)
         # K1: conv0 as a GEMM over overlapping channel-last rows (D:154,171)

@@ -23,7 +23,7 @@ import math
 import os
 import sys
 from pathlib import Path
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
@@ -36,6 +36,7 @@ if __package__ in (None, ""):
 
 from . import DualEEGTransformer, HipAdamW  # noqa: E402
 from .data import WindowShards, build_window_shards, synth_windows  # noqa: E402
+from .engine import WindowAugmentation  # noqa: E402
 from .ddp import AccumulatingReducer, GradAllReducer, broadcast_params, bucket_ranges, shard_indices  # noqa: E402
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
@@ -69,6 +70,24 @@ def accumulation_steps(config: Dict[str, Any]) -> int:
     if isinstance(k, bool) or not isinstance(k, int) or k < 1:
         raise ValueError(f"training.gradient_accumulation_steps must be an integer >= 1 (got {k!r})")
     return k
+
+
+AUGMENTATION_KEYS = ("gaussian_noise_std", "channel_dropout_prob", "time_mask_max_length", "time_mask_num")
+
+
+def augmentation_from_config(config: Dict[str, Any]) -> Optional[WindowAugmentation]:
+    """training.augmentation: a mapping with exactly the four keys of WindowAugmentation (absent ones are off); absent, or
+    everything off, means None.  An unknown key is an error that names it; the values are validated by WindowAugmentation."""
+    m = (config.get("training") or {}).get("augmentation")
+    if m is None:
+        return None
+    if not isinstance(m, dict):
+        raise ValueError(f"training.augmentation must be a mapping with the keys {list(AUGMENTATION_KEYS)} (got {m!r})")
+    unknown = [k for k in m if k not in AUGMENTATION_KEYS]
+    if unknown:
+        raise ValueError(f"training.augmentation: unknown key {unknown[0]!r} (known: {', '.join(AUGMENTATION_KEYS)})")
+    aug = WindowAugmentation(**m)
+    return aug if aug.enabled else None
 
 
 def macro_metrics(y_true: np.ndarray, y_pred: np.ndarray) -> Dict[str, float]:
@@ -113,6 +132,7 @@ class Trainer:
         torch.manual_seed(seed)
         np.random.seed(seed)
         self.model = build_model(config, compute_dtype).to(device)
+        self.model.augmentation = augmentation_from_config(config)     # train forwards only; evaluate() never augments
         t = config["training"]
         self.opt = HipAdamW(self.model, lr=t["learning_rate"], weight_decay=t["weight_decay"])
         self.epochs = t["num_train_epochs"]

@@ -92,6 +92,32 @@ int eg_window_pack(const float* x, void* xt, int NB, int C, int T, int Cp, int p
  *   mode 1: common-average reference, then per-channel z-score, population std + 1e-8 */
 int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, int N, int C, int T, int mode, void* stream);
 
+/* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
+ * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
+ * pl = 0 for buffer 1 and 1 for buffer 2.  Every draw is counter-based: H(site, i) = eg_hash(state->seed_lo, state->seed_hi,
+ * site, i), the full 32-bit word of csrc/common.h; half(site, e) = the 16-bit half of H(site, e >> 1) that eg_dropout uses for
+ * element e (low half for even e, high half for odd e).  The seed is read from *state on the device, so a captured launch
+ * draws anew at every replay; *state is only read.  Applied in this order:
+ *   noise (noise_std > 0): element e = ((pl N + w) C + c) T + t, pair q = e >> 1 (pairs run over the flat index: with odd T a
+ *     pair straddles two rows);  u1 = ((H(NOISE_R, q) >> 9) + 0.5f) 2^-23  (exact in fp32, inside (0, 1));
+ *     u2 = (H(NOISE_T, q) >> 8) 2^-24;  r = sqrtf(-2 logf(u1));  (s, c) = sincospif(2 u2);  n = r c for even e, r s for odd e;
+ *     y = fmaf(noise_std, n, x)
+ *   channel dropout (chan_drop_p > 0): row e = (pl N + w) C + c is kept iff half(CHAN, e) >= round(chan_drop_p 65536); a dropped
+ *     row is exact 0.0f, a kept row is NOT rescaled (a dead electrode); the two players draw independently
+ *   time masks (n_masks in [0, 8]): mask j of window w: h = H(TIME, 8 w + j), L = min(mask_max_len, T),
+ *     len = 1 + (((h & 0xFFFF) L) >> 16), start = ((h >> 16) (T - len + 1)) >> 16; samples [start, start + len) are exact 0.0f in
+ *     every channel of BOTH players (their windows stay aligned)
+ * Zeros win over noise; with noise_std == 0 every element that is not zeroed is copied bit for bit.  Refused on the host:
+ * null pointers, N / C / T <= 0, noise_std negative or not finite, chan_drop_p outside [0, 1), n_masks outside [0, 8],
+ * mask_max_len < 1 with n_masks > 0, 2 N C T >= 2^32. */
+#define EG_SITE_AUG_NOISE_R 8   /* sites 1-7 and >= 16 are taken (engine.py: SITE_*, _layer_sites) */
+#define EG_SITE_AUG_NOISE_T 9
+#define EG_SITE_AUG_CHAN    10
+#define EG_SITE_AUG_TIME    11
+int eg_window_augment(const float* in1, const float* in2, float* out1, float* out2, int N, int C, int T,
+                      float noise_std, float chan_drop_p, int n_masks, int mask_max_len,
+                      const eg_step_state* state, void* stream);
+
 /* Parameter staging (fp32 master -> compute dtype copies), run once per optimiser step.
  *   eg_cast:             n contiguous elements
  *   eg_transpose_cast:   src [R, Cc] f32 -> dst[c*ldd + r]         (weights for backward-data GEMMs)
