@@ -149,6 +149,8 @@ SIGNATURES = {
     "eg_attention_dk_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _U, _P, _P],
     "eg_attention_dk_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _U, _P, _P, _L, _P],
     "eg_attention_dk_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "eg_attention_stats_scratch_elems": [_I, _I, _I],          # returns int64_t: attn_stats_scratch_elems() below
+    "eg_attention_stats": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
     "eg_rows_bcast_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_rows_copy": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "eg_pool_fuse_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -228,6 +230,13 @@ def gate_bits_bytes(M: int, F: int) -> int:
     l.eg_ffn_gate_bits_bytes.restype = C.c_int64
     l.eg_ffn_gate_bits_bytes.argtypes = [C.c_int, C.c_int]
     return int(l.eg_ffn_gate_bits_bytes(M, F))
+
+
+def attn_stats_scratch_elems(NB: int, S: int, H: int) -> int:
+    """Floats of scratch eg_attention_stats needs for this shape (host only; 0: none, -1: bad shape)"""
+    l = lib()
+    l.eg_attention_stats_scratch_elems.restype = C.c_int64
+    return int(l.eg_attention_stats_scratch_elems(NB, S, H))
 
 
 def exported_symbols():

@@ -753,6 +753,7 @@ class ForwardEngine(EngineBase):
         call(self._attn_core + "_fwd", ptr(qkv), ptr(ctx), ptr(lse), self.NB, self.S, *self._attn_heads,
              kv_shift, self.dtype, p, sites["attn"], self.st_ptr, self.stream)
         self._probs_hook(self.model.get_submodule(pre + "dropout"), qkv, lse, kv_shift)
+        self._attn_stats(l, qkv, lse, kv_shift)
         self.gemm(ptr(ctx), ptr(self.w[f"o{l}"]), ptr(r), M, d, d, bias=self.fp.p_ptr(pre + "out_proj.bias"),
                   drop1=(p, sites["drop1"]), residual=ptr(x))
 
@@ -833,6 +834,9 @@ class ForwardEngine(EngineBase):
         finally:
             drop_module.training = was
 
+    def _attn_stats(self, l, qkv, lse, kv_shift):
+        """Where a stage's q|k|v rows and lse are complete.  Only the inference engine reduces them (InferenceEngine.attn_stats)."""
+
     def ln_fwd(self, x, gname, y, stats):
         call("eg_layernorm_fwd", ptr(x), self.fp.p_ptr(gname + ".weight"), self.fp.p_ptr(gname + ".bias"), ptr(y),
              ptr(stats), self.M, self.cfg.d_model, self.dtype, self.stream)
@@ -873,6 +877,7 @@ class ForwardEngine(EngineBase):
             self.attn_block_fwd(x, l, p, sites, R, ln=((pre + "ln1", R.y1, R.st1) if self.ln_fuse else None))
             if R.qkv is not None:
                 self._probs_hook(self.model.encoder.layers[l].mha.dropout, R.qkv, R.lse, 0)
+                self._attn_stats(l, R.qkv, R.lse, 0)
         else:
             self.attn_unfused_fwd(x, l, 0, sites, p, R)
         if not (self.attn_block and self.ln_fuse):
@@ -1542,6 +1547,16 @@ def inference_workspace_bytes(cfg, B: int, T: int, dtype: int) -> Tuple[int, int
     return lean + scratch, lean
 
 
+class AttnStats:
+    """A request to InferenceEngine.attn_stats.  stage: "cross" or an encoder layer index; map_sum [S, S] f32 is added to, diag
+    [B, S] f32 -- the current batch's rows of a caller's buffer -- is written, scratch holds at least
+    _lib.attn_stats_scratch_elems(2 B, S, H) floats."""
+
+    def __init__(self, where, map_sum: torch.Tensor, diag: torch.Tensor, scratch: torch.Tensor):
+        self.stage = "x" if where == "cross" else int(where)
+        self.map_sum, self.diag, self.scratch = map_sum, diag, scratch
+
+
 class InferenceEngine(ForwardEngine):
     """Forward-only engine for a fixed (B, T): predicts without saving what a backward would read.  No per-layer activations (two
     ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts, always p = 0, and
@@ -1567,6 +1582,7 @@ class InferenceEngine(ForwardEngine):
         self.a = a
         self.sc = {}                                       # the shared scratch set: qkv, lse, ctx, r, hff, st -- see _scratch
         self.routes_taken = []                             # (layer, "attn" | "ffn", "lean" | "scratch") of the last forward
+        self.attn_stats: Optional[AttnStats] = None        # a plain attribute: the stage whose probabilities the next forwards reduce
 
     def _scratch(self, name: str) -> torch.Tensor:
         if name not in self.sc:
@@ -1585,12 +1601,25 @@ class InferenceEngine(ForwardEngine):
         if l == "x":
             return Rows(s("qkv"), s("lse"), s("ctx"), s("r"), s("st"), out=out)
         drop = self.model.encoder.layers[l].mha.dropout
-        lean_attn = self.attn_block and self.ln_fuse and not (drop._forward_hooks or drop._forward_pre_hooks)
+        wanted = drop._forward_hooks or drop._forward_pre_hooks or (self.attn_stats is not None and self.attn_stats.stage == l)
+        lean_attn = self.attn_block and self.ln_fuse and not wanted
         lean_ffn = self.fuse_ffn and self.ln_fuse
         self.routes_taken += [(l, "attn", "lean" if lean_attn else "scratch"), (l, "ffn", "lean" if lean_ffn else "scratch")]
         attn = (None,) * 5 if lean_attn else (s("qkv"), s("lse"), s("ctx"), s("r"), s("st"))
         ffn = (None,) * 4 if lean_ffn else (s("hff"), None, s("r"), s("st"))
         return Rows(*attn, a["y1"], *ffn, out)
+
+    def _attn_stats(self, l, qkv, lse, kv_shift):
+        """eg_attention_stats on the requested stage: the batch's mean-over-heads-and-directions map added into map_sum, its
+        per-sample diagonals written to diag -- from q|k|v and lse, no [NB, H, S, S] tensor (predict.attention_statistics)"""
+        st = self.attn_stats
+        if st is None or st.stage != l:
+            return
+        for name, t, shape in (("map_sum", st.map_sum, (self.S, self.S)), ("diag", st.diag, (self.B, self.S))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != qkv.device:
+                raise L.EgError(f"attn_stats.{name} must be a contiguous f32 {list(shape)} tensor on {qkv.device}")
+        call("eg_attention_stats", ptr(qkv), ptr(lse), ptr(st.map_sum), ptr(st.diag), ptr(st.scratch), st.scratch.numel(),
+             self.NB, self.S, self.cfg.num_heads, self.head_dim, kv_shift, self.dtype, self.stream)
 
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None, pack: bool = True):
         """pack=False: the packed weights of an earlier call still hold (a caller walking many batches packs once)"""

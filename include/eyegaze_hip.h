@@ -431,6 +431,19 @@ int eg_attention_dk_bwd(const void* qkv, const void* ctx, const void* dctx, cons
 int eg_attention_dk_probs(const void* qkv, const float* lse, float* probs, int NB, int S, int H, int head_dim, int kv_shift,
                           int dtype, void* stream);
 
+/* Statistics of the attention probabilities P[w,h,q,k] = exp(q.k/sqrt(head_dim) - lse[w,h,q]) of one attention stage, from the
+ * stage's q|k|v rows and lse (layouts and kv_shift pairing of eg_attention_dk_*), without storing P.  NB is even; sample b < NB/2
+ * owns windows b and b + NB/2 (stream 1 / stream 2 of a Siamese layer, the two directions of the cross stage).
+ *   diag[b, q]     = 1/(2H) sum_h (P[b,h,q,q] + P[b+NB/2,h,q,q])                  written, [NB/2, S] fp32
+ *   map_sum[q, k] += sum_b 1/(2H) sum_h (P[b,h,q,k] + P[b+NB/2,h,q,k])            read-modify-write, [S, S] fp32: zero it once,
+ *                    issue every batch's call on one stream, read after the last (as eg_eval_accumulate's outputs)
+ * head_dim 32 or 64, 1 <= S <= EG_ATTN_LONG_MAX_S, dtype bf16 / fp16 / f32.  scratch: at least
+ * eg_attention_stats_scratch_elems(NB, S, H) floats, contents irrelevant on entry (0 floats: the tiles alone fill the GPU and
+ * scratch may be NULL; -1: bad shape).  Deterministic, no atomics. */
+int64_t eg_attention_stats_scratch_elems(int NB, int S, int H);            /* host only, no device needed */
+int eg_attention_stats(const void* qkv, const float* lse, float* map_sum, float* diag, float* scratch, int64_t scratch_elems,
+                       int NB, int S, int H, int head_dim, int kv_shift, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sequence assembly and heads (all [B, d]-sized, latency-bound single launches)
  *   eg_rows_bcast_f32  seq[b, off+r, :] = src[b % src_nb, r, :] + pos[off+r, :]   (cls_token expand + pos, D:1157,1178)
