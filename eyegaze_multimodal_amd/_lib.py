@@ -77,6 +77,12 @@ class AttnBlockDesc(C.Structure):
                 ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_out", C.c_void_p), ("ln_stats", C.c_void_p)]
 
 
+class WindowGatherDesc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("pair_off", C.c_void_p), ("pair_len", C.c_void_p), ("win_pair", C.c_void_p),
+                ("win_start", C.c_void_p), ("win_label", C.c_void_p),
+                ("n_pairs", C.c_int32), ("n_windows", C.c_int32), ("C", C.c_int32), ("T", C.c_int32)]
+
+
 class PackEntry(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("rows", C.c_int32), ("cols", C.c_int32), ("ldd", C.c_int32),
                 ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32)]
@@ -141,6 +147,7 @@ SIGNATURES = {
     "eg_attention_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
     "eg_attention_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
     "eg_window_normalize": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "eg_window_gather": [C.POINTER(WindowGatherDesc), _P, _I, _I, _I, _P, _P, _P, _I, _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],

@@ -527,38 +527,66 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
   return s;
 }
 
-__global__ __launch_bounds__(256) void window_normalize_kernel(const float* __restrict__ raw, float* __restrict__ eeg1,
-                                                               float* __restrict__ eeg2, int C, int T, int mode) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ double red[4];
-  float* car = (float*)smem;  // [T] (mode 1)
-  const int n = blockIdx.x >> 1, who = blockIdx.x & 1;
+// How a (window, player)'s C channel rows of T floats are addressed.  window_normalize_rows below is written once against
+// this interface, so the two launches share every load order, accumulator and reduction (bit-equal outputs).
+//   flat element e = c * T + t of the window; a cursor walks e = threadIdx.x, threadIdx.x + blockDim.x, ...
+struct ContiguousRows {            // rows back to back: the shards' [C, T] window
+  const float* x;
+  int T;
+  struct Cursor { long long e; };
+  __device__ __forceinline__ Cursor begin() const { return {(long long)threadIdx.x}; }
+  __device__ __forceinline__ void next(Cursor& p) const { p.e += blockDim.x; }
+  __device__ __forceinline__ float at(const Cursor& p) const { return x[p.e]; }
+  __device__ __forceinline__ const float* row(int c) const { return x + (long long)c * T; }
+};
+struct StridedRows {               // rows `ld` floats apart: a window inside a recording of the resident store
+  const float* x;
+  long long ld;
+  int T;
+  struct Cursor { long long e; long long off; int t; };   // off = c * ld + t for e = c * T + t
+  __device__ __forceinline__ Cursor begin() const {
+    Cursor p = {(long long)threadIdx.x, 0, (int)threadIdx.x};
+    while (p.t >= T) p.t -= T, p.off += ld;
+    p.off += p.t;
+    return p;
+  }
+  __device__ __forceinline__ void next(Cursor& p) const {
+    p.e += blockDim.x;
+    p.off += blockDim.x;
+    p.t += blockDim.x;
+    while (p.t >= T) p.t -= T, p.off += ld - T;
+  }
+  __device__ __forceinline__ float at(const Cursor& p) const { return x[p.off]; }
+  __device__ __forceinline__ const float* row(int c) const { return x + (long long)c * ld; }
+};
+
+template <class Rows>
+__device__ __forceinline__ void window_normalize_rows(const Rows in, float* __restrict__ y, int C, int T, int mode, float* car,
+                                                      double* red) {
   const long long CT = (long long)C * T;
-  const float* x = raw + ((long long)n * 2 + who) * CT;
-  float* y = (who ? eeg2 : eeg1) + (long long)n * CT;
   if (mode == 0) {
     double s = 0.0;
-    for (long long i = threadIdx.x; i < CT; i += blockDim.x) s += (double)x[i];
+    for (auto p = in.begin(); p.e < CT; in.next(p)) s += (double)in.at(p);
     const double mean = block_sum_d(s, red) / (double)CT;
     const float meanf = (float)mean;
     double q = 0.0;
-    for (long long i = threadIdx.x; i < CT; i += blockDim.x) {
-      const double d = (double)x[i] - mean;
+    for (auto p = in.begin(); p.e < CT; in.next(p)) {
+      const double d = (double)in.at(p) - mean;
       q += d * d;
     }
     const float stdf = (float)sqrt(block_sum_d(q, red) / (double)CT);
     const float den = stdf + 1e-8f;
-    for (long long i = threadIdx.x; i < CT; i += blockDim.x) y[i] = (x[i] - meanf) / den;
+    for (auto p = in.begin(); p.e < CT; in.next(p)) y[p.e] = (in.at(p) - meanf) / den;
     return;
   }
   for (int t = threadIdx.x; t < T; t += blockDim.x) {
     float s = 0.f;
-    for (int c = 0; c < C; ++c) s += x[(long long)c * T + t];
+    for (int c = 0; c < C; ++c) s += in.row(c)[t];
     car[t] = s / (float)C;
   }
   __syncthreads();
   for (int c = 0; c < C; ++c) {
-    const float* xc = x + (long long)c * T;
+    const float* xc = in.row(c);
     double s = 0.0;
     for (int t = threadIdx.x; t < T; t += blockDim.x) s += (double)(xc[t] - car[t]);
     const double mean = block_sum_d(s, red) / (double)T;
@@ -573,6 +601,33 @@ __global__ __launch_bounds__(256) void window_normalize_kernel(const float* __re
   }
 }
 
+__global__ __launch_bounds__(256) void window_normalize_kernel(const float* __restrict__ raw, float* __restrict__ eeg1,
+                                                               float* __restrict__ eeg2, int C, int T, int mode) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double red[4];
+  const int n = blockIdx.x >> 1, who = blockIdx.x & 1;
+  const long long CT = (long long)C * T;
+  const ContiguousRows in = {raw + ((long long)n * 2 + who) * CT, T};
+  window_normalize_rows(in, (who ? eeg2 : eeg1) + (long long)n * CT, C, T, mode, (float*)smem /* [T] (mode 1) */, red);
+}
+
+// The same arithmetic on windows cut out of device-resident recordings (include/eyegaze_hip.h: eg_window_gather).  One block
+// per (batch window, player); the tables are trusted (data.validate_store checks them once, on the host); every offset is 64-bit
+// and every access a 4-byte one, since a row may start at any float of the store.
+__global__ __launch_bounds__(256) void window_gather_kernel(const eg_window_gather_desc d, const int32_t* __restrict__ order,
+                                                            int first, float* __restrict__ eeg1, float* __restrict__ eeg2,
+                                                            int64_t* __restrict__ labels, int mode) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double red[4];
+  const int j = blockIdx.x >> 1, who = blockIdx.x & 1;
+  const int w = order[(long long)first + j];
+  const int p = d.win_pair[w];
+  const long long len = d.pair_len[p];
+  const StridedRows in = {d.data + d.pair_off[p] + (long long)who * d.C * len + d.win_start[w], len, d.T};
+  if (labels && who == 0 && threadIdx.x == 0) labels[j] = d.win_label[w];
+  window_normalize_rows(in, (who ? eeg2 : eeg1) + (long long)j * d.C * d.T, d.C, d.T, mode, (float*)smem, red);
+}
+
 }  // namespace
 
 extern "C" int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, int N, int C, int T, int mode, void* stream) {
@@ -583,6 +638,23 @@ extern "C" int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, i
   hipLaunchKernelGGL(window_normalize_kernel, dim3(2 * N), dim3(256), mode ? (size_t)T * 4 : 0, (hipStream_t)stream, raw, eeg1,
                      eeg2, C, T, mode);
   EG_LAUNCH_CHECK("window_normalize");
+  return 0;
+}
+
+extern "C" int eg_window_gather(const eg_window_gather_desc* d, const int32_t* order, int order_len, int first, int n, float* eeg1,
+                                float* eeg2, int64_t* labels, int mode, void* stream) {
+  EG_CHECK(d && d->data && d->pair_off && d->pair_len && d->win_pair && d->win_start && order && eeg1 && eeg2,
+           "eg_window_gather: null pointer");
+  EG_CHECK(n > 0 && d->C > 0 && d->T > 0, "eg_window_gather: bad shape n=%d C=%d T=%d", n, d->C, d->T);
+  EG_CHECK(d->n_pairs > 0 && d->n_windows > 0, "eg_window_gather: empty tables (n_pairs=%d n_windows=%d)", d->n_pairs, d->n_windows);
+  EG_CHECK(mode == 0 || mode == 1, "eg_window_gather: mode %d (0 = window z-score, 1 = CAR + channel z-score)", mode);
+  EG_CHECK(d->T <= 16384, "eg_window_gather: T=%d exceeds the 16384-sample staging row", d->T);
+  EG_CHECK(first >= 0 && (long long)first + n <= (long long)order_len, "eg_window_gather: windows [%d, %d + %d) outside the order of %d",
+           first, first, n, order_len);
+  EG_CHECK(!labels || d->win_label, "eg_window_gather: labels requested but the descriptor has no win_label");
+  hipLaunchKernelGGL(window_gather_kernel, dim3(2 * n), dim3(256), mode ? (size_t)d->T * 4 : 0, (hipStream_t)stream, *d, order, first,
+                     eeg1, eeg2, labels, mode);
+  EG_LAUNCH_CHECK("window_gather");
   return 0;
 }
 

@@ -82,16 +82,13 @@ def load_recording(path):
     return orient_recording(pd.read_csv(path, header=None).values)
 
 
-def build_window_shards(items: Sequence[Dict], eeg_base_path, label2id: Dict[str, int], out_dir, window_size: int = 1024,
-                        stride: int = 256, shard_windows: int = 4096, recordings: Optional[Dict[str, np.ndarray]] = None) -> Dict:
-    """Cut every (player1, player2) pair of `items` into sliding windows and write shards + index.
-
-    items        sequence of {'player1': name, 'player2': name, 'class': label} (the reference's metadata rows)
-    recordings   optional name -> 2-D array holding a file's contents, instead of `<eeg_base_path>/<name>.csv`
-    Window enumeration = the reference's: per item in order, `(min_len - W) // stride + 1` windows starting at
-    `i * stride`, items with a missing file or `min_len < W` skipped; channels truncated to the pair's minimum."""
-    out = Path(out_dir)
-    out.mkdir(parents=True, exist_ok=True)
+def kept_pairs(items: Sequence[Dict], eeg_base_path, window_size: int, stride: int,
+               recordings: Optional[Dict[str, np.ndarray]] = None):
+    """The reference's window enumeration (`_prepare_windows`, dual_eeg_dataset.py:62-120), pair by pair: yields
+    (idx, item, a, b, nwin) for every item of `items` that has windows -- a, b the two (C, len) recordings with the channels
+    truncated to the pair's minimum, nwin = (min_len - W) // stride + 1 windows starting at i * stride.  Items with a missing
+    file or `min_len < W` are skipped (min_len from the column counts as stored, see orient_recording); a pair whose channel
+    count differs from the earlier ones raises ValueError.  Both the shard builder and the recording store walk this."""
     base = Path(eeg_base_path) if eeg_base_path is not None else None
     cache: Dict[str, np.ndarray] = {}
 
@@ -103,6 +100,39 @@ def build_window_shards(items: Sequence[Dict], eeg_base_path, label2id: Dict[str
             cache[name] = load_recording(p) if p.exists() else None
         return cache[name]
 
+    C_all = None
+    for idx, item in enumerate(items):
+        ra, rb = get(item["player1"]), get(item["player2"])
+        if ra is None or rb is None:
+            continue
+        (a, na), (b, nb_) = ra, rb
+        min_len = min(na, nb_)
+        if min_len < window_size:
+            continue
+        C = min(a.shape[0], b.shape[0])
+        if C_all is None:
+            C_all = C
+        elif C != C_all:
+            raise ValueError(f"item {idx}: {C} channels, earlier items have {C_all}")
+        yield idx, item, a[:C], b[:C], (min_len - window_size) // stride + 1
+        if recordings is None:
+            cache.clear()
+
+
+def _window_meta(idx: int, item: Dict, s: int, e: int) -> Dict:
+    return {"dataset_idx": idx, "start": s, "end": e, "player1": item["player1"], "player2": item["player2"], "class": item["class"]}
+
+
+def build_window_shards(items: Sequence[Dict], eeg_base_path, label2id: Dict[str, int], out_dir, window_size: int = 1024,
+                        stride: int = 256, shard_windows: int = 4096, recordings: Optional[Dict[str, np.ndarray]] = None) -> Dict:
+    """Cut every (player1, player2) pair of `items` into sliding windows and write shards + index.
+
+    items        sequence of {'player1': name, 'player2': name, 'class': label} (the reference's metadata rows)
+    recordings   optional name -> 2-D array holding a file's contents, instead of `<eeg_base_path>/<name>.csv`
+    Window enumeration = the reference's (kept_pairs): per item in order, `(min_len - W) // stride + 1` windows starting at
+    `i * stride`, items with a missing file or `min_len < W` skipped; channels truncated to the pair's minimum."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
     meta: List[Dict] = []
     labels: List[int] = []
     shards: List[Dict] = []
@@ -118,29 +148,15 @@ def build_window_shards(items: Sequence[Dict], eeg_base_path, label2id: Dict[str
         shards.append({"file": name, "count": int(arr.shape[0])})
         buf.clear()
 
-    for idx, item in enumerate(items):
-        ra, rb = get(item["player1"]), get(item["player2"])
-        if ra is None or rb is None:
-            continue
-        (a, na), (b, nb_) = ra, rb
-        min_len = min(na, nb_)
-        if min_len < window_size:
-            continue
-        C = min(a.shape[0], b.shape[0])
-        if C_all is None:
-            C_all = C
-        elif C != C_all:
-            raise ValueError(f"item {idx}: {C} channels, earlier items have {C_all}")
-        for w in range((min_len - window_size) // stride + 1):
+    for idx, item, a, b, nwin in kept_pairs(items, eeg_base_path, window_size, stride, recordings):
+        C_all = a.shape[0]
+        for w in range(nwin):
             s, e = w * stride, w * stride + window_size
-            buf.append(np.stack([a[:C, s:e], b[:C, s:e]]))
-            meta.append({"dataset_idx": idx, "start": s, "end": e, "player1": item["player1"], "player2": item["player2"],
-                         "class": item["class"]})
+            buf.append(np.stack([a[:, s:e], b[:, s:e]]))
+            meta.append(_window_meta(idx, item, s, e))
             labels.append(int(label2id[item["class"]]))
             if len(buf) == shard_windows:
                 flush()
-        if recordings is None:
-            cache.clear()
     flush()
     np.save(out / "labels.npy", np.asarray(labels, dtype=np.int64))
     index = {"window_size": window_size, "stride": stride, "channels": C_all, "count": len(meta), "shards": shards,
@@ -182,10 +198,7 @@ class WindowShards:
         self.epoch = epoch
 
     def _order(self) -> np.ndarray:
-        idx = np.arange(self.n)
-        if self.shuffle:
-            idx = np.random.default_rng(self.seed + self.epoch).permutation(self.n)
-        return idx[self.rank::self.world]
+        return epoch_order(self.n, self.shuffle, self.seed, self.epoch, self.rank, self.world)
 
     def __len__(self):
         if self.drop_last:      # the same count on every rank (a DDP step needs all of them)
@@ -227,3 +240,187 @@ class WindowShards:
             self.consumed[slot].record(cur)
             yield {"eeg1": eeg1, "eeg2": eeg2, "labels": self.labels[ids].to(self.device, non_blocking=True),
                    "dataset_idx": [self.index["windows"][int(i)]["dataset_idx"] for i in ids]}
+
+
+# ------------------------------------------------------------------------------------------------------
+# Device-resident recordings.  The shards above store every sample window_size / stride times and every batch
+# crosses the host.  The recording store keeps each kept pair ONCE -- only the samples its windows cover, `[2][C][len]` f32 at a
+# float offset of one flat `store.npy` -- plus a window table (pair, start).  ResidentWindows uploads store and tables once and
+# cuts + normalises every batch on the device with one `eg_window_gather` launch: nothing of a batch crosses the host.
+# ------------------------------------------------------------------------------------------------------
+def build_recording_store(items: Sequence[Dict], eeg_base_path, label2id: Dict[str, int], out_dir, window_size: int = 1024,
+                          stride: int = 256, recordings: Optional[Dict[str, np.ndarray]] = None) -> Dict:
+    """`build_window_shards`' arguments, skipping rules and window order (kept_pairs), written as a recording store:
+      store.npy   flat f32; pair p at float offset off[p] as [2][C][len[p]], len[p] = (nwin - 1) * stride + window_size
+      labels.npy  i64 per window, as the shards'
+      index.json  the shard index's keys (without `shards`) + `pairs` [{offset, length, dataset_idx}] + `window_pair` [count]"""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    meta: List[Dict] = []
+    labels: List[int] = []
+    pairs: List[Dict] = []
+    window_pair: List[int] = []
+    C_all, total = None, 0
+    tmp = out / "store.f32.partial"                     # the total is known only after the walk: raw first, .npy after
+    with open(tmp, "wb") as f:
+        for idx, item, a, b, nwin in kept_pairs(items, eeg_base_path, window_size, stride, recordings):
+            C_all = a.shape[0]
+            length = (nwin - 1) * stride + window_size
+            np.stack([a[:, :length], b[:, :length]]).astype(np.float32, copy=False).tofile(f)
+            for w in range(nwin):
+                meta.append(_window_meta(idx, item, w * stride, w * stride + window_size))
+                labels.append(int(label2id[item["class"]]))
+                window_pair.append(len(pairs))
+            pairs.append({"offset": total, "length": length, "dataset_idx": idx})
+            total += 2 * C_all * length
+    store = np.lib.format.open_memmap(out / "store.npy", mode="w+", dtype=np.float32, shape=(total,))
+    if total:
+        raw = np.memmap(tmp, dtype=np.float32, mode="r", shape=(total,))
+        for i in range(0, total, 1 << 24):
+            store[i:i + (1 << 24)] = raw[i:i + (1 << 24)]
+        del raw
+    store.flush()
+    del store
+    tmp.unlink()
+    np.save(out / "labels.npy", np.asarray(labels, dtype=np.int64))
+    index = {"window_size": window_size, "stride": stride, "channels": C_all, "count": len(meta), "windows": meta,
+             "label2id": label2id, "pairs": pairs, "window_pair": window_pair}
+    (out / "index.json").write_text(json.dumps(index))
+    return index
+
+
+def store_tables(index: Dict):
+    """index -> (pair_off [P], pair_len [P], win_pair [N], win_start [N]), int64 host arrays in eg_window_gather's table order"""
+    return (np.asarray([p["offset"] for p in index["pairs"]], dtype=np.int64),
+            np.asarray([p["length"] for p in index["pairs"]], dtype=np.int64),
+            np.asarray(index["window_pair"], dtype=np.int64),
+            np.asarray([w["start"] for w in index["windows"]], dtype=np.int64))
+
+
+def validate_store(index: Dict, store_floats: int) -> None:
+    """Raises ValueError unless every window lies inside its pair (0 <= start, start + T <= len[pair]), every pair inside the
+    store's `store_floats` floats, and the pairs' offsets are non-decreasing without overlap.  This is the only bounds check the
+    gather gets: the kernel trusts its tables."""
+    C, T = int(index["channels"] or 0), int(index["window_size"])
+    off, ln, wp, ws = store_tables(index)
+    if C < 1 or T < 1:
+        raise ValueError(f"recording store: channels={C} window_size={T}")
+    if not (len(wp) == len(ws) == int(index["count"])):
+        raise ValueError(f"recording store: {len(ws)} windows, {len(wp)} pair numbers, count {index['count']}")
+    if len(ln) and (ln.min() < 0 or ln.max() >= 2 ** 31):
+        raise ValueError("recording store: a pair's length does not fit int32")
+    end = off + 2 * C * ln
+    if len(off) and (off[0] < 0 or end[-1] > store_floats or (end > store_floats).any()):
+        p = int(np.argmax((end > store_floats) | (off < 0)))
+        raise ValueError(f"recording store: pair {p} covers floats [{off[p]}, {end[p]}) of a store of {store_floats}")
+    if (off[1:] < end[:-1]).any():
+        p = int(np.argmax(off[1:] < end[:-1]))
+        raise ValueError(f"recording store: pair {p + 1} at float {off[p + 1]} overlaps pair {p}, which ends at {end[p]}")
+    if len(wp) and (wp.min() < 0 or wp.max() >= len(ln)):
+        raise ValueError(f"recording store: a window names a pair outside [0, {len(ln)})")
+    bad = (ws < 0) | (ws + T > ln[wp]) if len(wp) else np.zeros(0, bool)
+    if bad.any():
+        w = int(np.argmax(bad))
+        raise ValueError(f"recording store: window {w} covers samples [{ws[w]}, {ws[w] + T}) of pair {wp[w]}, which has {ln[wp[w]]}")
+
+
+def epoch_order(n: int, shuffle: bool, seed: int, epoch: int, rank: int, world: int) -> np.ndarray:
+    """Both loaders' `_order`: the epoch's (optionally shuffled) window order, rank r of world taking r::world"""
+    idx = np.arange(n)
+    if shuffle:
+        idx = np.random.default_rng(seed + epoch).permutation(n)
+    return idx[rank::world]
+
+
+class DeviceRecordings:
+    """A recording store in device memory with its window tables, and the launch that cuts batches out of it.
+    data: flat f32 device tensor; the tables are host arrays (store_tables' order), validated by the caller."""
+
+    def __init__(self, data: torch.Tensor, pair_off, pair_len, win_pair, win_start, win_label, C: int, T: int):
+        from . import _lib as L
+        L.lib()
+        dev = data.device
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        self.data, self.C, self.T, self.device = data, int(C), int(T), dev
+        self.pair_off, self.pair_len = up(pair_off, np.int64), up(pair_len, np.int32)
+        self.win_pair, self.win_start = up(win_pair, np.int32), up(win_start, np.int32)
+        self.win_label = up(win_label, np.int64) if win_label is not None else None
+        self.n_windows = int(self.win_pair.numel())
+        self.desc = L.WindowGatherDesc(L.ptr(data), L.ptr(self.pair_off), L.ptr(self.pair_len), L.ptr(self.win_pair),
+                                       L.ptr(self.win_start), L.ptr(self.win_label), int(self.pair_off.numel()), self.n_windows,
+                                       self.C, self.T)
+
+    def gather(self, order: torch.Tensor, first: int, n: int, mode: int):
+        """windows order[first : first + n] (order: i32 device tensor of window numbers) -> eeg1, eeg2 [n, C, T] f32 normalised in
+        `mode`, labels [n] i64 or None: one launch on the current stream, no copy, no sync"""
+        import ctypes
+        from ._lib import call, ptr
+        eeg1 = torch.empty(n, self.C, self.T, dtype=torch.float32, device=self.device)
+        eeg2 = torch.empty_like(eeg1)
+        labels = torch.empty(n, dtype=torch.int64, device=self.device) if self.win_label is not None else None
+        call("eg_window_gather", ctypes.byref(self.desc), ptr(order), int(order.numel()), int(first), int(n), ptr(eeg1), ptr(eeg2),
+             ptr(labels), int(mode), torch.cuda.current_stream(self.device).cuda_stream)
+        return eeg1, eeg2, labels
+
+
+class ResidentWindows:
+    """WindowShards' interface over a recording store that lives in device memory: same constructor, same batches (bit for
+    bit), same order, `__len__` and `set_epoch`.  Construction validates the index, uploads the store (in bounded chunks) and
+    the tables once; an epoch uploads this rank's order (int32) once; a batch is ONE eg_window_gather launch on the current
+    stream -- no host gather, no H2D copy, no event, no sync.  Build it once per run and iterate it every epoch.  With
+    world > 1 every rank holds the whole store and takes its rank::world share.  There is no fallback: a store that does not
+    fit raises EgError."""
+    UPLOAD_CHUNK = 1 << 24      # floats per staged upload (64 MiB)
+
+    def __init__(self, root, batch_size: int, device, rank: int = 0, world: int = 1, shuffle: bool = False, seed: int = 0,
+                 preprocessing: bool = False, drop_last: bool = False):
+        from ._lib import EgError
+        self.root = Path(root)
+        self.index = json.loads((self.root / "index.json").read_text())
+        labels = np.load(self.root / "labels.npy")
+        host = np.load(self.root / "store.npy", mmap_mode="r")
+        validate_store(self.index, int(host.shape[0]))
+        self.n, self.C, self.T = int(self.index["count"]), int(self.index["channels"]), int(self.index["window_size"])
+        if labels.shape[0] != self.n:
+            raise ValueError(f"{self.root}: {labels.shape[0]} labels for {self.n} windows")
+        self.B, self.device, self.rank, self.world = batch_size, torch.device(device), rank, world
+        self.shuffle, self.seed, self.mode, self.drop_last = shuffle, seed, 1 if preprocessing else 0, drop_last
+        self.epoch = 0
+        self.dataset_idx = np.asarray([w["dataset_idx"] for w in self.index["windows"]], dtype=np.int64)
+        need = 4 * int(host.shape[0])
+        try:
+            data = torch.empty(int(host.shape[0]), dtype=torch.float32, device=self.device)
+        except torch.OutOfMemoryError as e:
+            free = torch.cuda.mem_get_info(self.device)[0]
+            raise EgError(f"ResidentWindows: the recording store needs {need} bytes of device memory, {free} are free "
+                          "(there is no fallback: use WindowShards)") from e
+        stage = torch.empty(min(self.UPLOAD_CHUNK, max(1, int(host.shape[0]))), dtype=torch.float32).pin_memory()
+        for i in range(0, int(host.shape[0]), self.UPLOAD_CHUNK):
+            m = min(self.UPLOAD_CHUNK, int(host.shape[0]) - i)
+            stage.numpy()[:m] = host[i:i + m]
+            data[i:i + m].copy_(stage[:m])              # synchronous: `stage` is free again when it returns
+        off, ln, wp, ws = store_tables(self.index)
+        self.store = DeviceRecordings(data, off, ln, wp, ws, labels, self.C, self.T)
+        self._order_dev = None
+
+    def set_epoch(self, epoch: int):
+        self.epoch = epoch
+
+    def _order(self) -> np.ndarray:
+        return epoch_order(self.n, self.shuffle, self.seed, self.epoch, self.rank, self.world)
+
+    __len__ = WindowShards.__len__
+
+    def __iter__(self):
+        order = self._order()
+        nb = len(self)
+        if nb == 0:
+            return
+        # the epoch's one upload; kept on the object so that the last launch's table outlives the generator
+        self._order_dev = order_dev = torch.from_numpy(order.astype(np.int32)).to(self.device)
+        didx = self.dataset_idx[order].tolist()
+        for k in range(nb):
+            first = k * self.B
+            n = min(self.B, len(order) - first)
+            eeg1, eeg2, labels = self.store.gather(order_dev, first, n, self.mode)
+            yield {"eeg1": eeg1, "eeg2": eeg2, "labels": labels, "dataset_idx": didx[first:first + n]}

@@ -4,7 +4,11 @@ argmax, confusion matrix, loss sum -- kept on the device (eg_eval_accumulate), s
 attention_statistics is eeg_metrics.py's extract_attention_weights (:465-594) over the same walk: the mean attention map and the
 per-sample diagonals reduced on the device from each batch's q|k|v rows (eg_attention_stats), never a [B, H, S, S] tensor.
 
-    python -m eyegaze_multimodal_amd.predict --config CONFIG.yaml --checkpoint best_model.pt --out FILE.npz [--attention-stats [cross|LAYER]]
+predict_loader walks a data.ResidentWindows store instead (--resident: gather launch -> engine, no window visits the host), and
+predict_recording classifies one whole recording pair at any stride.
+
+    python -m eyegaze_multimodal_amd.predict --config CONFIG.yaml --checkpoint best_model.pt --out FILE.npz [--resident]
+                                             [--attention-stats [cross|LAYER]]
 """
 from __future__ import annotations
 
@@ -18,6 +22,43 @@ import torch
 from ._lib import EgError, attn_stats_scratch_elems, call, ptr
 
 
+class _PredictWalk:
+    """The per-batch body and the result of a prediction walk, whichever way its batches arrive: forward on the inference engine
+    (weights packed once per engine), logits kept, argmax / confusion matrix / loss sum on the device (eg_eval_accumulate)."""
+
+    def __init__(self, model, N: int, with_labels: bool):
+        self.model, self.N, ncls = model, N, model.cfg.num_classes
+        self.dev = dev = next(model.parameters()).device
+        self.logits = torch.empty(N, ncls, device=dev)
+        self.pred = torch.empty(N, device=dev, dtype=torch.int32)
+        self.cm = torch.zeros(ncls, ncls, device=dev, dtype=torch.int32) if with_labels else None
+        self.loss_sum = torch.zeros(1, device=dev) if with_labels else None
+        self.packed, self.nb, self.i = set(), 0, 0
+
+    def batch(self, eeg1, eeg2, labels):
+        """the next batch: device tensors [B, C, T], labels [B] or None; fills rows [i, i + B) of the walk"""
+        model, i = self.model, self.i
+        x1, x2, y = model._check_windows(eeg1, eeg2, labels)
+        B, ncls = x1.shape[0], model.cfg.num_classes
+        eng = model.inference_engine(B, x1.shape[2], self.dev)
+        eng.forward(x1, x2, y, pack=id(eng) not in self.packed)
+        self.packed.add(id(eng))
+        self.logits[i:i + B].copy_(eng.a["logits"])
+        call("eg_eval_accumulate", ptr(eng.a["logits"]), ptr(y), ptr(eng.a["loss"]) if y is not None else 0,
+             self.pred.data_ptr() + 4 * i, ptr(self.cm), ptr(self.loss_sum), B, ncls, eng.stream)
+        self.nb += 1
+        self.i += B
+
+    def result(self) -> Dict[str, Any]:
+        from .train_art import macro_metrics_from_confusion
+        out = {"logits": self.logits, "predictions": self.pred.long()}
+        if self.cm is not None:
+            out["confusion"] = self.cm.cpu().numpy()                 # the one host sync
+            out["loss"] = float(self.loss_sum) / self.nb
+            out["metrics"] = macro_metrics_from_confusion(out["confusion"])
+        return out
+
+
 @torch.no_grad()
 def predict_windows(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None,
                     batch_size: int = 256) -> Dict[str, Any]:
@@ -26,33 +67,76 @@ def predict_windows(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optio
       logits [N, ncls] f32 and predictions [N] i64 (device tensors), and with labels also
       confusion [ncls, ncls] (numpy, [true][predicted]), loss (mean of the batches' cross-entropy means, as Trainer.evaluate
       reports it) and metrics (train_art.macro_metrics_from_confusion)."""
-    from .train_art import macro_metrics_from_confusion
-    N, ncls = eeg1.shape[0], model.cfg.num_classes
-    dev = next(model.parameters()).device
+    N = eeg1.shape[0]
     if batch_size < 1 or N < 1:
         raise ValueError(f"predict_windows needs N >= 1 windows and batch_size >= 1 (got {N}, {batch_size})")
-    logits = torch.empty(N, ncls, device=dev)
-    pred = torch.empty(N, device=dev, dtype=torch.int32)
-    cm = torch.zeros(ncls, ncls, device=dev, dtype=torch.int32) if labels is not None else None
-    loss_sum = torch.zeros(1, device=dev) if labels is not None else None
-    packed, nb = set(), 0
+    walk = _PredictWalk(model, N, labels is not None)
     for i in range(0, N, batch_size):
-        up = lambda t: None if t is None else t[i:i + batch_size].to(dev, non_blocking=True)
-        x1, x2, y = model._check_windows(up(eeg1), up(eeg2), up(labels))
-        B = x1.shape[0]
-        eng = model.inference_engine(B, x1.shape[2], dev)
-        eng.forward(x1, x2, y, pack=id(eng) not in packed)
-        packed.add(id(eng))
-        logits[i:i + B].copy_(eng.a["logits"])
-        call("eg_eval_accumulate", ptr(eng.a["logits"]), ptr(y), ptr(eng.a["loss"]) if y is not None else 0,
-             pred.data_ptr() + 4 * i, ptr(cm), ptr(loss_sum), B, ncls, eng.stream)
-        nb += 1
-    out = {"logits": logits, "predictions": pred.long()}
-    if labels is not None:
-        out["confusion"] = cm.cpu().numpy()                      # the one host sync
-        out["loss"] = float(loss_sum) / nb
-        out["metrics"] = macro_metrics_from_confusion(out["confusion"])
-    return out
+        up = lambda t: None if t is None else t[i:i + batch_size].to(walk.dev, non_blocking=True)
+        walk.batch(up(eeg1), up(eeg2), up(labels))
+    return walk.result()
+
+
+@torch.no_grad()
+def predict_loader(model, loader) -> Dict[str, Any]:
+    """predict_windows over a loader's device batches (data.ResidentWindows: each batch goes from the gather launch straight into
+    the inference engine, nothing crosses the host).  Returns predict_windows' dict plus labels [N] i64 (device)."""
+    if loader.n < 1:
+        raise ValueError("predict_loader needs at least one window")
+    N = len(loader._order()) if not loader.drop_last else len(loader) * loader.B
+    walk = _PredictWalk(model, N, True)
+    labels = torch.empty(N, device=walk.dev, dtype=torch.int64)
+    for b in loader:
+        labels[walk.i:walk.i + b["labels"].shape[0]].copy_(b["labels"])
+        walk.batch(b["eeg1"], b["eeg2"], b["labels"])
+    return {**walk.result(), "labels": labels}
+
+
+def majority_vote(predictions, num_classes: int) -> int:
+    """the class most windows predict; a tie goes to the lowest class id"""
+    counts = np.bincount(np.asarray(predictions, dtype=np.int64).reshape(-1), minlength=num_classes)
+    return int(np.argmax(counts))            # argmax returns the first of equal maxima
+
+
+def recording_starts(length: int, window: int, stride: int) -> np.ndarray:
+    """window starts i * stride of a recording of `length` samples; the tail shorter than a window is dropped, as the
+    reference's enumeration drops it (dual_eeg_dataset.py:62-120)"""
+    if stride < 1 or window < 1:
+        raise ValueError(f"window={window} and stride={stride} must be >= 1")
+    return np.arange(0 if length < window else (length - window) // stride + 1, dtype=np.int64) * stride
+
+
+@torch.no_grad()
+def predict_recording(model, rec1, rec2, stride: Optional[int] = None, batch_size: int = 256,
+                      preprocessing: bool = False) -> Dict[str, Any]:
+    """Classifies a whole recording pair at any stride.  rec1, rec2: (C, L) arrays or tensors (the shorter length and the smaller
+    channel count count); the window length is the one model.cfg implies (4 * max_len), stride defaults to it.  The pair is
+    uploaded once as a one-pair recording store; every batch is cut and normalised on the device (eg_window_gather) and goes
+    straight into the inference engine.  Returns starts [n] (numpy i64), logits [n, ncls] f32 and predictions [n] i64 (device
+    tensors) and vote (majority_vote of the predictions)."""
+    from .data import DeviceRecordings, validate_store
+    dev = next(model.parameters()).device
+    T = 4 * model.cfg.max_len
+    stride = T if stride is None else int(stride)
+    r1, r2 = (torch.as_tensor(np.asarray(r) if not torch.is_tensor(r) else r, dtype=torch.float32) for r in (rec1, rec2))
+    if r1.dim() != 2 or r2.dim() != 2:
+        raise ValueError(f"predict_recording needs (C, L) recordings, got {tuple(r1.shape)} and {tuple(r2.shape)}")
+    C, L = min(r1.shape[0], r2.shape[0]), min(r1.shape[1], r2.shape[1])
+    starts = recording_starts(L, T, stride)
+    n = len(starts)
+    if n < 1 or batch_size < 1:
+        raise ValueError(f"predict_recording: recordings of {L} samples hold no window of {T} (batch_size {batch_size})")
+    validate_store({"channels": C, "window_size": T, "count": n, "pairs": [{"offset": 0, "length": L}],
+                    "window_pair": [0] * n, "windows": [{"start": int(s)} for s in starts]}, 2 * C * L)
+    data = torch.stack([r1[:C, :L], r2[:C, :L]]).to(dev).contiguous().reshape(-1)
+    store = DeviceRecordings(data, [0], [L], np.zeros(n, np.int32), starts, None, C, T)
+    order = torch.arange(n, dtype=torch.int32, device=dev)
+    walk = _PredictWalk(model, n, False)
+    for i in range(0, n, batch_size):
+        x1, x2, _ = store.gather(order, i, min(batch_size, n - i), 1 if preprocessing else 0)
+        walk.batch(x1, x2, None)
+    out = walk.result()
+    return {"starts": starts, **out, "vote": majority_vote(out["predictions"].cpu().numpy(), model.cfg.num_classes)}
 
 
 CLASS_NAMES = ["Single", "Competition", "Cooperation"]          # eeg_metrics.py:558
@@ -122,7 +206,7 @@ def attention_statistics(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: 
 
 def main(args):
     from . import train_art as TA
-    from .data import WindowShards
+    from .data import ResidentWindows, WindowShards
     if not torch.cuda.is_available():
         raise SystemExit("predict.py (HIP) needs an MI355X: there is no CPU fallback")
     config = TA.load_config(args.config)
@@ -131,11 +215,21 @@ def main(args):
     ck = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
     model.load_state_dict(ck.get("model_state_dict", ck))
     d, t = config["data"], config["training"]
-    shards = TA.prepare_shards(config, Path(t["output_dir"]) / "window_shards")
-    ld = WindowShards(shards[args.split], t["per_device_eval_batch_size"], device, preprocessing=d.get("enable_preprocessing", False))
-    parts = [(b["eeg1"].cpu(), b["eeg2"].cpu(), b["labels"].cpu()) for b in ld]
-    x1, x2, y = (torch.cat(p).pin_memory() for p in zip(*parts))
-    out = predict_windows(model, x1, x2, y, batch_size=t["per_device_eval_batch_size"])
+    ebs, pre = t["per_device_eval_batch_size"], d.get("enable_preprocessing", False)
+    if args.resident or d.get("resident", False):
+        # the store is walked directly: gather launch -> inference engine, batch by batch; no window visits the host
+        stores = TA.prepare_store(config, Path(t["output_dir"]) / "recording_store")
+        ld = ResidentWindows(stores[args.split], ebs, device, preprocessing=pre)
+        out = predict_loader(model, ld)
+        y = out["labels"].cpu()
+        if args.attention_stats is not None:
+            x1, x2 = (torch.cat(p) for p in zip(*((b["eeg1"], b["eeg2"]) for b in ld)))     # stays on the device
+    else:
+        shards = TA.prepare_shards(config, Path(t["output_dir"]) / "window_shards")
+        ld = WindowShards(shards[args.split], ebs, device, preprocessing=pre)
+        parts = [(b["eeg1"].cpu(), b["eeg2"].cpu(), b["labels"].cpu()) for b in ld]
+        x1, x2, y = (torch.cat(p).pin_memory() for p in zip(*parts))
+        out = predict_windows(model, x1, x2, y, batch_size=ebs)
     extra = {}
     if args.attention_stats is not None:
         where = "cross" if args.attention_stats == "cross" else int(args.attention_stats)
@@ -156,6 +250,8 @@ if __name__ == "__main__":
     ap.add_argument("--out", type=str, required=True)
     ap.add_argument("--split", type=str, default="test", choices=["train", "test"])
     ap.add_argument("--dtype", type=str, default=None, choices=[None, "bf16", "fp16", "f32"])
+    ap.add_argument("--resident", action="store_true",
+                    help="walk the device-resident recording store (also: data.resident in the config) instead of the window shards")
     ap.add_argument("--attention-stats", type=str, nargs="?", const="cross", default=None, metavar="cross|LAYER",
                     help="also reduce the attention probabilities of the cross stage (default) or of encoder layer LAYER: "
                          "attn_mean_map, attn_diagonals and attn_class_<name>_mean_diagonal in the output file")

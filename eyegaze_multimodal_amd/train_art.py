@@ -13,7 +13,9 @@ Differences, all additive:
     data.py — the reference's CSVs are not distributed with it;
   * wandb is optional (imported only when training.report_to == ['wandb'] and the module exists);
   * `training.gradient_accumulation_steps: k` (absent = 1 = the reference's one batch per step): every k-th train_step ends
-    in the optimiser step, on the sum of the k micro-batches' gradients divided by k (Trainer.train_step / Trainer.flush).
+    in the optimiser step, on the sum of the k micro-batches' gradients divided by k (Trainer.train_step / Trainer.flush);
+  * `data.resident: true` (absent = false = the window shards): the recordings stay in device memory for the run and every
+    batch is cut and normalised there by one launch (data.ResidentWindows); the batches are the shards' bits.
 """
 from __future__ import annotations
 
@@ -35,7 +37,7 @@ if __package__ in (None, ""):
     __package__ = "eyegaze_multimodal_amd"
 
 from . import DualEEGTransformer, HipAdamW  # noqa: E402
-from .data import WindowShards, build_window_shards, synth_windows  # noqa: E402
+from .data import ResidentWindows, WindowShards, build_recording_store, build_window_shards, synth_windows  # noqa: E402
 from .engine import WindowAugmentation  # noqa: E402
 from .ddp import AccumulatingReducer, GradAllReducer, broadcast_params, bucket_ranges, shard_indices  # noqa: E402
 
@@ -358,16 +360,17 @@ def shard_fingerprint(config: Dict[str, Any]) -> str:
     return hashlib.sha256(json.dumps(key, sort_keys=True, default=str).encode()).hexdigest()[:16]
 
 
-def prepare_shards(config: Dict[str, Any], out_dir: Path, rank: int = 0, world: int = 1, timeout_s: float = 24 * 3600.0) -> Dict[str, Path]:
-    """CSV recordings -> windowed shards, once per data configuration.  Rank 0 builds and then writes `<out_dir>/READY`
-    holding the fingerprint; the other ranks poll that file (no collective: a long CSV conversion must not run into the
-    process group's timeout).  Shards built under another fingerprint are rebuilt."""
+def _prepare_windows(config: Dict[str, Any], out_dir: Path, rank: int, world: int, timeout_s: float, fingerprint: str, build,
+                     what: str) -> Dict[str, Path]:
+    """The protocol both window caches share.  Rank 0 builds (`build(items, directory)` writes one split and returns what to log) and then
+    writes `<out_dir>/READY` holding the fingerprint; the other ranks poll that file (no collective: a long CSV conversion
+    must not run into the process group's timeout).  A cache built under another fingerprint is rebuilt."""
     import json
     import shutil
     import time
     d = config["data"]
     dirs = {"train": out_dir / "train", "test": out_dir / "test"}
-    fp = shard_fingerprint(config)
+    fp = fingerprint
     ready = out_dir / "READY"
 
     def is_ready():
@@ -384,16 +387,57 @@ def prepare_shards(config: Dict[str, Any], out_dir: Path, rank: int = 0, world: 
             items = items[: d["max_samples"]]
         train_items, test_items = split_items(items, d["train_test_split"], d["random_seed"])
         for name, its in (("train", train_items), ("test", test_items)):
-            idx = build_window_shards(its, d["eeg_base_path"], d["label2id"], dirs[name], d["window_size"], d["stride"])
-            logger.info(f"{name}: {len(its)} recordings -> {idx['count']} windows in {len(idx['shards'])} shards")
+            logger.info(f"{name}: {len(its)} recordings -> " + build(its, dirs[name]))
         out_dir.mkdir(parents=True, exist_ok=True)
         ready.write_text(fp)
     t0 = time.time()
     while not is_ready():
         if time.time() - t0 > timeout_s:
-            raise TimeoutError(f"rank {rank}: window shards under {out_dir} did not become ready")
+            raise TimeoutError(f"rank {rank}: {what} under {out_dir} did not become ready")
         time.sleep(0.5)
     return dirs
+
+
+def prepare_shards(config: Dict[str, Any], out_dir: Path, rank: int = 0, world: int = 1, timeout_s: float = 24 * 3600.0) -> Dict[str, Path]:
+    """CSV recordings -> windowed shards, once per data configuration (_prepare_windows)."""
+    d = config["data"]
+
+    def build(its, path):
+        idx = build_window_shards(its, d["eeg_base_path"], d["label2id"], path, d["window_size"], d["stride"])
+        return f"{idx['count']} windows in {len(idx['shards'])} shards"
+
+    return _prepare_windows(config, out_dir, rank, world, timeout_s, shard_fingerprint(config), build, "window shards")
+
+
+def prepare_store(config: Dict[str, Any], out_dir: Path, rank: int = 0, world: int = 1, timeout_s: float = 24 * 3600.0) -> Dict[str, Path]:
+    """CSV recordings -> recording stores (data.build_recording_store) for `data.resident: true`, by prepare_shards' protocol;
+    the fingerprint carries a kind tag, so a directory of shards is never taken for a store."""
+    d = config["data"]
+
+    def build(its, path):
+        idx = build_recording_store(its, d["eeg_base_path"], d["label2id"], path, d["window_size"], d["stride"])
+        return f"{idx['count']} windows over {len(idx['pairs'])} resident recording pairs"
+
+    return _prepare_windows(config, out_dir, rank, world, timeout_s, shard_fingerprint(config) + ":store", build, "recording store")
+
+
+def window_loaders(config: Dict[str, Any], device, rank: int, world: int):
+    """CSV data -> (train loader factory, test loader factory); each factory returns the split's loader for an epoch.
+    data.resident (absent = false): false builds a WindowShards per call, as ever; true builds ONE ResidentWindows per split,
+    whose recordings stay in device memory for the run, and hands it out every time."""
+    d, t = config["data"], config["training"]
+    bs, ebs, pre = t["per_device_train_batch_size"], t["per_device_eval_batch_size"], d.get("enable_preprocessing", False)
+    # one process: every window, tail batch included, as the reference's DataLoader (train_art.py:334-341);
+    # data parallel: every rank must take the same number of steps, so the ragged tail is dropped
+    train_kw = dict(shuffle=True, seed=d["random_seed"], preprocessing=pre, drop_last=world > 1)
+    if not d.get("resident", False):
+        shards = prepare_shards(config, Path(t["output_dir"]) / "window_shards", rank, world)   # file-based wait, no collective
+        return (lambda: WindowShards(shards["train"], bs, device, rank, world, **train_kw),
+                lambda: WindowShards(shards["test"], ebs, device, rank, world, preprocessing=pre))
+    stores = prepare_store(config, Path(t["output_dir"]) / "recording_store", rank, world)
+    train_ld = ResidentWindows(stores["train"], bs, device, rank, world, **train_kw)
+    test_ld = ResidentWindows(stores["test"], ebs, device, rank, world, preprocessing=pre)
+    return (lambda: train_ld), (lambda: test_ld)
 
 
 def _batches(x1, x2, y, bs, device, idx):
@@ -418,7 +462,8 @@ def checkpoint_dict(tr: "Trainer", epoch: int, config, *, best_f1=None, metrics=
     return ck
 
 
-def main(args):
+def main(args, history: Optional[list] = None):
+    """history: a list that receives every epoch's metrics dict (train/*, eval/*, epoch), unrounded"""
     config = load_config(args.config)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -435,9 +480,9 @@ def main(args):
     C, T, ncls = config["model"]["in_channels"], d["window_size"], config["model"]["num_labels"]
     eeg_dir = Path(d.get("eeg_base_path", ""))
     use_csv = not d.get("synthetic", False) and eeg_dir.exists() and any(eeg_dir.glob("*.csv"))
-    shards = None
+    loaders = None
     if use_csv:
-        shards = prepare_shards(config, Path(t["output_dir"]) / "window_shards", rank, world)   # file-based wait, no collective
+        loaders = window_loaders(config, device, rank, world)
     else:
         n_total = d.get("max_samples") or d.get("synthetic_samples", 2048)
         logger.info(f"synthetic class-conditional windows: n={n_total} C={C} T={T} classes={ncls}")
@@ -463,11 +508,8 @@ def main(args):
     for epoch in range(tr.epochs):
         tr.opt.set_epoch(epoch, tr.epochs)           # CosineAnnealingLR stepped per epoch (train_art.py:409,494)
         sums, nb = {}, 0
-        if shards is not None:
-            # one process: every window, tail batch included, as the reference's DataLoader (train_art.py:334-341);
-            # data parallel: every rank must take the same number of steps, so the ragged tail is dropped
-            train_ld = WindowShards(shards["train"], bs, device, rank, world, shuffle=True, seed=d["random_seed"],
-                                    preprocessing=d.get("enable_preprocessing", False), drop_last=world > 1)
+        if loaders is not None:
+            train_ld = loaders[0]()
             train_ld.set_epoch(epoch)
             train_iter = ((b["eeg1"], b["eeg2"], b["labels"]) for b in train_ld)
         else:
@@ -483,13 +525,15 @@ def main(args):
             nb += 1
         tr.flush()      # gradient accumulation: no gradient crosses an epoch, no learning-rate change falls inside a group
         train_metrics = {f"train/{k}": float(sums.get(k, 0.0)) / max(nb, 1) for k in TRAIN_KEYS}   # train_art.py:248-255
-        if shards is not None:
-            test_ld = WindowShards(shards["test"], ebs, device, rank, world, preprocessing=d.get("enable_preprocessing", False))
+        if loaders is not None:
+            test_ld = loaders[1]()
             ev = tr.evaluate((b["eeg1"], b["eeg2"], b["labels"]) for b in test_ld)
         else:
             my_test = test_idx[list(shard_indices(len(test_idx), rank, world))]
             ev = tr.evaluate(_batches(x1, x2, y, min(ebs, max(1, len(my_test))), device, my_test))
         metrics = {**train_metrics, **ev, "epoch": epoch + 1}
+        if history is not None:
+            history.append(metrics)
         if rank == 0:
             logger.info(" ".join(f"{k}: {v:.4f}" for k, v in metrics.items() if k != "epoch") + f" (epoch {epoch + 1}/{tr.epochs})")
             if wandb:
@@ -510,8 +554,8 @@ def main(args):
     if best_path.exists():
         ck = torch.load(best_path, map_location="cpu", weights_only=False)   # our own file, written above
         tr.model.load_state_dict(ck["model_state_dict"])
-        if shards is not None:
-            test_ld = WindowShards(shards["test"], ebs, device, rank, world, preprocessing=d.get("enable_preprocessing", False))
+        if loaders is not None:
+            test_ld = loaders[1]()
             final = tr.evaluate((b["eeg1"], b["eeg2"], b["labels"]) for b in test_ld)
         else:
             my_test = test_idx[list(shard_indices(len(test_idx), rank, world))]

@@ -92,6 +92,30 @@ int eg_window_pack(const float* x, void* xt, int NB, int C, int T, int Cp, int p
  *   mode 1: common-average reference, then per-channel z-score, population std + 1e-8 */
 int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, int N, int C, int T, int mode, void* stream);
 
+/* The same normalisation on windows cut out of recordings that stay in device memory (data.py: the recording store).
+ * Pair p holds its two players' channels as [2][C][pair_len[p]] f32 at float offset pair_off[p] of `data`; window w lies in pair
+ * win_pair[w] and starts at sample win_start[w].  Window j of the batch is w = order[first + j]; channel c of its player `who` is
+ * the T floats at
+ *     data + pair_off[win_pair[w]] + (who * C + c) * pair_len[win_pair[w]] + win_start[w]         (64-bit arithmetic)
+ * and eeg1 / eeg2 [n, C, T] receive them normalised in `mode` with the arithmetic of eg_window_normalize -- one body, two
+ * addressings -- so they are, bit for bit, what eg_window_normalize gives on the same raw windows.  labels[j] = win_label[w]
+ * (labels may be null; it must be null when win_label is).  Rows may start at any float: every access is 4 bytes wide.
+ * Every pointer of the descriptor is a DEVICE pointer; the descriptor itself is host memory, as is eg_attn_block_desc.
+ * The tables are trusted: whoever builds them proves 0 <= win_start[w], win_start[w] + T <= pair_len[win_pair[w]], every pair
+ * inside `data`, and 0 <= order[i] < n_windows (data.validate_store).  Refused on the host: null pointers, n / C / T <= 0, empty
+ * tables, mode outside {0, 1}, T > 16384, first < 0 or first + n > order_len, labels without win_label. */
+typedef struct eg_window_gather_desc {
+  const float* data;
+  const int64_t* pair_off;    /* [n_pairs]   float offset of the pair in data */
+  const int32_t* pair_len;    /* [n_pairs]   samples per channel row of the pair */
+  const int32_t* win_pair;    /* [n_windows] */
+  const int32_t* win_start;   /* [n_windows] */
+  const int64_t* win_label;   /* [n_windows] or null */
+  int32_t n_pairs, n_windows, C, T;
+} eg_window_gather_desc;
+int eg_window_gather(const eg_window_gather_desc* d, const int32_t* order, int order_len, int first, int n, float* eeg1,
+                     float* eeg2, int64_t* labels, int mode, void* stream);
+
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
  * pl = 0 for buffer 1 and 1 for buffer 2.  Every draw is counter-based: H(site, i) = eg_hash(state->seed_lo, state->seed_hi,
