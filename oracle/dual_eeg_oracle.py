@@ -400,8 +400,11 @@ def forward(eeg1: Tensor, eeg2: Tensor, sd: Dict[str, Tensor], cfg: ModelCfg, la
         comps1.append(ibs_tokens)
         comps2.append(ibs_tokens)
     if cfg.use_spectrogram:
+        CTX["stream"] = 0
         s1 = spectrogram_tokens(eeg1, sd, cfg, p01)
+        CTX["stream"] = 1
         s2 = spectrogram_tokens(eeg2, sd, cfg, p01)
+        CTX["stream"] = 0
         comps1.append(s1)
         comps2.append(s2)
         if stages is not None:

@@ -55,15 +55,28 @@ def hip_keep_mask(seed: int, site: int, idx: np.ndarray, p: float) -> np.ndarray
     return half >= np.uint64(int(p * 65536.0 + 0.5))
 
 
-def hip_dropout_override(seed: int, B: int, num_layers: int, ctx: dict):
+# every dropout site the oracle names (oracle/dual_eeg_oracle.py, the comment above DROPOUT_OVERRIDE)
+ORACLE_SITE_KINDS = ("conv", "attn", "drop1", "ffn_a", "ffn_b", "drop2", "xdrop1", "cls", "ibscls", "spec", "ibstok", "ibsgen")
+# deliberate mask defects for negative controls (CPU side only: what the ORACLE is fed, the engine is untouched)
+OVERRIDE_DEFECTS = ("spec_stream0", "ibstok_shift", "ibscls_noscale")
+
+
+def hip_dropout_override(seed: int, B: int, num_layers: int, ctx: dict, log: dict = None, defect: str = None):
     """Returns a DROPOUT_OVERRIDE for oracle.dual_eeg_oracle that reproduces the engine's masks (engine.py: SITE_* ids,
-    _layer_sites; index = row * N + column with rows ordered (stream, window, token); attention: ((w*H+h)*S+q)*Sp2 + key)."""
+    _layer_sites; index = row * N + column with rows ordered (stream, window, token); attention: ((w*H+h)*S+q)*Sp2 + key).
+    The token families' sites (tokens.py, Engine._heads_fwd): ibstok = eg_gelu_fwd's flat element index over [B*ntok, 64];
+    ibsgen, spec, ibscls = the GEMM epilogue's m * N + n, where spec's rows are the images, stream-major (nimg = 2*B*C).
+    `log`, when given, receives log[site + (stream,)] = (keep mask, the tensor before dropout) of every call served.
+    `defect` (one of OVERRIDE_DEFECTS) hands the oracle a deliberately wrong mask: stream 0's spec mask for both streams, the
+    ibstok element index shifted by one, or the ibscls mask without its 1/(1-p)."""
     from eyegaze_multimodal_amd import engine as E
+    assert defect is None or defect in OVERRIDE_DEFECTS, defect
 
     def fn(tens, p, site):
         st = ctx["stream"]
         kind = site[0]
         shp = tens.shape
+        scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
         if kind == "conv":                                   # [B, d, T_i]  <-  rows (window, t), columns = channel
             Bn, d, Tn = shp
             w = (st * B + torch.arange(Bn)).view(Bn, 1, 1)
@@ -81,13 +94,27 @@ def hip_dropout_override(seed: int, B: int, num_layers: int, ctx: dict):
             m = ((st * B + torch.arange(Bn)).view(Bn, 1, 1) * S + torch.arange(S).view(1, S, 1))
             idx = m * N + torch.arange(N).view(1, 1, N)
             sid = E._layer_sites(num_layers)["drop1"] if kind == "xdrop1" else E._layer_sites(site[1])[kind]
-        elif kind == "cls":                                  # [B, d]
+        elif kind in ("cls", "ibsgen", "ibscls"):            # [B, N]: computed once per window pair, not per stream
             Bn, N = shp
             idx = torch.arange(Bn).view(Bn, 1) * N + torch.arange(N).view(1, N)
-            sid = E.SITE_CLS
+            sid = {"cls": E.SITE_CLS, "ibsgen": E.SITE_IBSGEN, "ibscls": E.SITE_IBSCLS}[kind]
+            if kind == "ibscls" and defect == "ibscls_noscale":
+                scale = np.float32(1.0)
+        elif kind == "ibstok":                               # [B, ntok, 64]: one token set per window pair
+            Bn, ntok, N = shp
+            idx = (torch.arange(Bn).view(Bn, 1, 1) * ntok + torch.arange(ntok).view(1, ntok, 1)) * N + torch.arange(N).view(1, 1, N)
+            if defect == "ibstok_shift":
+                idx = idx + 1
+            sid = E.SITE_IBSTOK
+        elif kind == "spec":                                 # [B*C, 2d] per stream; the engine's images are stream-major
+            R, N = shp
+            s_eff = 0 if defect == "spec_stream0" else st
+            idx = (s_eff * R + torch.arange(R).view(R, 1)) * N + torch.arange(N).view(1, N)
+            sid = E.SITE_SPEC
         else:
             raise KeyError(site)
         keep = torch.from_numpy(hip_keep_mask(seed, sid, idx.numpy().astype(np.uint32), p))
-        scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+        if log is not None:
+            log[tuple(site) + (st,)] = (keep, tens.detach().clone())
         return torch.where(keep, tens * float(scale), torch.zeros((), dtype=tens.dtype))
     return fn
