@@ -67,7 +67,7 @@ class _IBSMatrixGenerator(nn.Module):  # D:488-525, forward D:760-819 (no parame
         from . import tokens
         eeg1, eeg2 = eeg1.contiguous().float(), eeg2.contiguous().float()
         eng = owner.engine(eeg1.shape[0], eeg1.shape[2], eeg1.device)
-        return tokens.ibs_matrices(owner, eng, eeg1, eeg2).clone()
+        return tokens.ibs_matrices(eng, eeg1, eeg2).clone()
 
 
 class _IBSTokenizer(_Holder):  # D:837-877
@@ -404,18 +404,3 @@ class DualEEGTransformer(nn.Module):
 
     def compute_ibs_contrastive_loss(self, ibs_tokens, labels, temperature: float = 0.07):
         return _AuxLoss.apply("supcon", float(temperature), labels, ibs_tokens)
-
-    # ------------------------------------------------------------------------------------------
-    # hooks the engine calls for the optional token families (spectrogram / synchrony tokens)
-    # ------------------------------------------------------------------------------------------
-    def _pack_extra(self, eng: Engine):
-        from . import tokens
-        tokens.pack(self, eng)
-
-    def _extra_tokens_fwd(self, eng: Engine, eeg1, eeg2, train: bool):
-        from . import tokens
-        tokens.forward(self, eng, eeg1, eeg2, train)
-
-    def _extra_tokens_bwd(self, eng: Engine, dseq):
-        from . import tokens
-        tokens.backward(self, eng, dseq)

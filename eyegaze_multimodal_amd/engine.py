@@ -13,9 +13,10 @@ Data layout in HBM (NB = 2B windows: stream 1 = samples [0,B), stream 2 = [B,2B)
 What is stated once here:
   geometry()        the front end's and the sequence's row / column counts for (cfg, T, dtype), device-free
   LAYOUTS           every packed weight layout: shape, pack operation, source, and the direction and route that read it
-  EngineBase        device / dtype fields, step state, timed launches, gemm / wgrad, the pack table (also ImageEngine's base)
-  ForwardEngine     the encoder forward: routes, allocation and pack recording from LAYOUTS, the launches, ONE forward body that
-                    asks the engine where each stage's rows go (_rows)
+  EngineBase        device / dtype fields, step state, timed launches, gemm / wgrad, allocation and pack recording from LAYOUTS
+                    and the pack table (also ImageEngine's base)
+  ForwardEngine     the encoder forward: routes, its stages of LAYOUTS, the launches, ONE forward body that asks the engine where
+                    each stage's rows go (_rows)
   Engine            training: per-layer saved activations, the backward in stages, accumulation, the optimiser
   InferenceEngine   forward only: a ping-pong pair + scratch on demand, the forward-reading layouts, the training calls refused
 """
@@ -31,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
-from . import wgrad_plan
+from . import tokens, wgrad_plan
 from ._lib import EG_BF16, EG_F16, EG_F32, GemmDesc, GemmTNDesc, StepState, call, ptr, rowmap
 
 # dropout site ids (any fixed numbering works: the mask depends on (seed, site, element index))
@@ -240,7 +241,8 @@ def conv_bwd_data_phases(k: int, s: int, pad: int, T1: int):
 
 class EngineBase:
     """What every step engine is built on: device / dtype fields, the step state, timed launches, the GEMM and weight-gradient
-    wrappers, the table-driven parameter staging.  A subclass allocates a, w, g, defines _pack_body and ends with _init_state."""
+    wrappers, the table-driven parameter staging from LAYOUTS.  A subclass names its stages (_stages) and the layouts it holds
+    (_held), allocates a, w (_alloc_w), g, and ends with _init_state."""
     tn_cap = 0      # floats of g["partial"], the split-K partials of wgrad (a subclass sizes it)
 
     def __init__(self, model, B: int, device, dtype: int):
@@ -261,7 +263,7 @@ class EngineBase:
         self.scaler_on = False
         self.scaler_cfg = dict(init_scale=65536.0, growth=2.0, backoff=0.5, growth_interval=2000)
         # the recorded pack table (pack_params)
-        self._recording, self._plan, self._plan_ex = False, [], False
+        self._plan, self._plan_launches, self._plan_ex = [], [], False
         self._plan_key, self._plan_dev, self._plan_n, self._plan_blocks = None, None, 0, 0
         # the routes pack_params keys its table on.  Off here: an engine that has them resolves them (_resolve_routes)
         self.fused_tail = self.pack_unused = False
@@ -468,40 +470,65 @@ class EngineBase:
     # ------------------------------------------------------------------------------------------
     # parameter staging
     # ------------------------------------------------------------------------------------------
-    # table-driven staging: cast / transpose entries are recorded once and replayed as ONE launch per step
+    # table-driven staging: _pack_body walks LAYOUTS once per plan; the p_* operations record cast / transpose / ... entries,
+    # replayed as ONE launch per step, and what no table mode carries as launches of their own, issued on every pack_params
     def p_cast(self, src, dst, n):
-        if self._recording:
-            self._plan.append((src, dst, 1, n, 0, 0))
+        self._plan.append((src, dst, 1, n, 0, 0))
 
     def p_copy(self, src, dst, n):
-        if self._recording:
-            self._plan.append((src, dst, 1, n, 0, 2))
+        self._plan.append((src, dst, 1, n, 0, 2))
 
     def p_transpose(self, src, dst, R, Cc, ldd):
-        if self._recording:
-            self._plan.append((src, dst, R, Cc, ldd, 1))
+        self._plan.append((src, dst, R, Cc, ldd, 1))
 
     def p_frag(self, src, dst, R, Cc, mode, part=0):
         """fragment order of the fp32 parameter src [R, Cc]: eg_ffn_chain's (eg_pack_table modes 3-6) or eg_attn_block_fwd's
         (mode 7 with part = 0 / 1 / 2 for q / k / v_proj, mode 8 for out_proj)."""
-        if self._recording:
-            self._plan.append((src, dst, R, Cc, part, mode))
+        self._plan.append((src, dst, R, Cc, part, mode))
 
     def p_conv(self, src, dst, N, Cin, k, Cp, Kp):
         """eg_pack_conv_weight as an entry of the pack table (fused route) or as its own launch"""
         if self._plan_ex:
-            if self._recording:
-                self._plan.append((src, dst, N, Cin, 0, 9, k, Cp, Kp))
+            self._plan.append((src, dst, N, Cin, 0, 9, k, Cp, Kp))
         else:
-            call("eg_pack_conv_weight", src, dst, N, Cin, k, Cp, Kp, self.dtype, self.stream)
+            self._plan_launches.append(("eg_pack_conv_weight", src, dst, N, Cin, k, Cp, Kp))
 
     def p_convT(self, src, dst, N, Cin, k, s):
         """eg_pack_convT_weight, likewise"""
         if self._plan_ex:
-            if self._recording:
-                self._plan.append((src, dst, N, Cin, 0, 10, k, s, (k + s - 1) // s))
+            self._plan.append((src, dst, N, Cin, 0, 10, k, s, (k + s - 1) // s))
         else:
-            call("eg_pack_convT_weight", src, dst, N, Cin, k, s, self.dtype, self.stream)
+            self._plan_launches.append(("eg_pack_convT_weight", src, dst, N, Cin, k, s))
+
+    def p_conv2d(self, src, dst, Cout, Cin, transposed):
+        """eg_pack_conv2d_weight: no table mode carries it, so always its own launch"""
+        self._plan_launches.append(("eg_pack_conv2d_weight", src, dst, Cout, Cin, transposed))
+
+    def _alloc_w(self) -> Dict[str, torch.Tensor]:
+        d, F = self.cfg.d_model, getattr(self.cfg, "d_ff", None)       # (the image engine has no feed-forward stage)
+        return {f"{lay.key}{l}": self._t(*lay.shape(d, F, self), dtype=(torch.float32 if lay.op == "copy" else None))
+                for stage, _, l in self._stages() for group in LAYOUTS[stage] for lay in self._held(group, l, True)}
+
+    def _pack_body(self, record: bool):
+        """What pack_params does before the table launch: a walk of LAYOUTS when the plan is (re)recorded, then the launches that
+        the walk left beside the table."""
+        if record:
+            self._plan, self._plan_launches = [], []
+            d, F, fp = self.cfg.d_model, getattr(self.cfg, "d_ff", None), self.fp
+            for stage, pre, l in self._stages():
+                for group in LAYOUTS[stage]:
+                    held = self._held(group, l, bool(self.pack_unused))
+                    for i in range(len(group[0].src)):
+                        for lay in held:
+                            t = self.w[f"{lay.key}{l}"]
+                            src, dst, args = fp.p_ptr(pre + lay.src[i]), ptr(t), lay.args(d, F, self)
+                            # source i: the next args[0] elements (cast, copy) or columns (transpose: ldd = the buffer's width)
+                            # of the buffer; a fragment layout takes the source index as its part
+                            off = 0 if lay.op == "frag" else i * args[0] * t.element_size()
+                            extra = (t.shape[1],) if lay.op == "transpose" else (i,) if lay.op == "frag" else ()
+                            getattr(self, "p_" + lay.op)(src, dst + off, *args, *extra)
+        for name, *args in self._plan_launches:
+            call(name, *args, self.dtype, self.stream)
 
     def _extent_after(self, addr: int, elsize: int) -> int:
         """elements of size `elsize` between `addr` and the end of the engine / parameter buffer that holds it (0: not found)"""
@@ -518,10 +545,9 @@ class EngineBase:
         # the routing flags decide which layouts _pack_body records, so a flag flipped on a live engine re-records the plan
         key = (self.fp.flat.data_ptr(), ex, bool(self.pack_unused), self.fuse_ffn, self.attn_block, self.ln_proj)
         self._plan_ex = ex
-        if self._plan_key != key:
-            self._plan, self._recording = [], True
-            self._pack_body()
-            self._recording = False
+        record = self._plan_key != key
+        self._pack_body(record)
+        if record:
             ents = ((L.PackEntryEx if ex else L.PackEntry) * len(self._plan))()
             blk = 0
             for e, ent in zip(ents, self._plan):
@@ -548,18 +574,16 @@ class EngineBase:
             raw = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8)
             self._plan_dev = raw.to(self.device)
             self._plan_n, self._plan_blocks, self._plan_key = len(self._plan), blk, key
-        else:
-            self._pack_body()
         call("eg_pack_table_ex" if ex else "eg_pack_table", ptr(self._plan_dev), self._plan_n, self._plan_blocks, self.dtype,
              self.stream)
 
 
 # ------------------------------------------------------------------------------------------------
-# packed weight layouts of the EEG engines: the one declaration that allocation and pack recording are derived from
+# packed weight layouts of every engine: the one declaration that allocation and pack recording are derived from
 # ------------------------------------------------------------------------------------------------
 # w[key + stage]: one packed form of a parameter (or, with several sources, of the parameters that share the buffer)
 #   shape   (d, F, engine) -> shape of the buffer; fp32 for "copy", else the compute dtype
-#   op      cast | copy | transpose | frag | conv | convT: the p_* operation that fills it
+#   op      cast | copy | transpose | frag | conv | convT | conv2d: the p_* operation that fills it
 #   args    (d, F, engine) -> that operation's arguments behind (src, dst), for one source
 #   src     parameter names under the stage's prefix; part i of the buffer comes from src[i]
 #   bwd     read by the backward; else by the forward
@@ -614,6 +638,24 @@ LAYOUTS = {
         (_lay("i0", lambda d, F, e: (d // 2, d), "cast", lambda d, F, e: ((d // 2) * d,), "ibs_classifier.0.weight"),),
         (_lay("i0T", lambda d, F, e: (d, _align(d // 2, e.bk)), "transpose", lambda d, F, e: (d // 2, d), "ibs_classifier.0.weight",
               bwd=True),)],
+    # the token families (tokens.py).  "cnn" is the 2-D CNN of the spectrogram tokens and of the image engine: conv-2's weights
+    # tap-major for the forward and transposed for the backward-data (eg_pack_conv2d_weight), the two projections
+    "cnn": [
+        (_lay("spc2", lambda d, F, e: (64, 384), "conv2d", lambda d, F, e: (64, 32, 0), "spec_conv.3.weight"),),
+        (_lay("spc2T", lambda d, F, e: (32, 768), "conv2d", lambda d, F, e: (64, 32, 1), "spec_conv.3.weight", bwd=True),),
+        (_lay("spp0", lambda d, F, e: (2 * d, 1024), "cast", lambda d, F, e: (2 * d * 1024,), "proj.0.weight"),),
+        (_lay("spp0T", lambda d, F, e: (1024, 2 * d), "transpose", lambda d, F, e: (2 * d, 1024), "proj.0.weight", bwd=True),),
+        (_lay("spp3", lambda d, F, e: (d, 2 * d), "cast", lambda d, F, e: (d * 2 * d,), "proj.3.weight"),),
+        (_lay("spp3T", lambda d, F, e: (2 * d, d), "transpose", lambda d, F, e: (d, 2 * d), "proj.3.weight", bwd=True),)],
+    "ibs_tok": [    # matrix-form synchrony tokens: the bottleneck over the C x C connectivity entries
+        (_lay("ib0", lambda d, F, e: (64, e.C * e.C), "cast", lambda d, F, e: (64 * e.C * e.C,), "bottleneck.0.weight"),),
+        (_lay("ib0T", lambda d, F, e: (e.C * e.C, 64), "transpose", lambda d, F, e: (64, e.C * e.C), "bottleneck.0.weight", bwd=True),),
+        (_lay("ib3", lambda d, F, e: (d, 64), "cast", lambda d, F, e: (d * 64,), "bottleneck.3.weight"),),
+        (_lay("ib3T", lambda d, F, e: (64, d), "transpose", lambda d, F, e: (d, 64), "bottleneck.3.weight", bwd=True),)],
+    "ibs_gen": [    # scalar-form synchrony token: 28 features, zero-padded to the K-tile as a 1-tap convolution
+        (_lay("ig0", lambda d, F, e: (2 * d, 64), "conv", lambda d, F, e: (2 * d, 28, 1, 28, 64), "0.weight"),),
+        (_lay("ig3", lambda d, F, e: (d, 2 * d), "cast", lambda d, F, e: (d * 2 * d,), "3.weight"),),
+        (_lay("ig3T", lambda d, F, e: (2 * d, d), "transpose", lambda d, F, e: (d, 2 * d), "3.weight", bwd=True),)],
 }
 _ALL_LAYOUTS = [lay for groups in LAYOUTS.values() for group in groups for lay in group]
 # forward layout of an unfused route -> the fragment-ordered layout of the same parameters that the fused route reads instead
@@ -665,6 +707,7 @@ class ForwardEngine(EngineBase):
         self.M = self.NB * self.S
         self._resolve_routes()
         self._alloc()
+        tokens.alloc(self)
         self._init_state(state_dev)
 
     def _resolve_routes(self):
@@ -699,7 +742,7 @@ class ForwardEngine(EngineBase):
         self.pack_unused = False
 
     # ------------------------------------------------------------------------------------------
-    # packed weights: allocation and pack recording, both walks of LAYOUTS
+    # packed weights: the stages of LAYOUTS that EngineBase's two walks (_alloc_w, _pack_body) visit
     # ------------------------------------------------------------------------------------------
     def _reads(self, lay, l) -> bool:
         """whether a route chosen NOW reads layout `lay` of stage l (the cross-attention block "x" has no fused route)"""
@@ -716,28 +759,14 @@ class ForwardEngine(EngineBase):
         yield "heads", "", ""
         if self.cfg.use_ibs:
             yield "ibs", "", ""
+        if self.cfg.use_spectrogram:
+            yield "cnn", "spectrogram_generator.", ""
+        if self.cfg.use_ibs:
+            yield ("ibs_tok", "ibs_tokenizer.", "") if self.cfg.use_robust_ibs else ("ibs_gen", "ibs_generator.proj.", "")
 
-    def _alloc_w(self) -> Dict[str, torch.Tensor]:
-        d, F = self.cfg.d_model, self.cfg.d_ff
-        return {f"{lay.key}{l}": self._t(*lay.shape(d, F, self), dtype=(torch.float32 if lay.op == "copy" else None))
-                for stage, _, l in self._stages() for group in LAYOUTS[stage] for lay in self._held(group, l, True)}
-
-    def _pack_body(self):
-        if self._recording or not self._plan_ex:        # (a replayed table that carries the convolutions leaves nothing to do here)
-            d, F, fp = self.cfg.d_model, self.cfg.d_ff, self.fp
-            for stage, pre, l in self._stages():
-                for group in LAYOUTS[stage]:
-                    held = self._held(group, l, bool(self.pack_unused))
-                    for i in range(len(group[0].src)):
-                        for lay in held:
-                            t = self.w[f"{lay.key}{l}"]
-                            src, dst, args = fp.p_ptr(pre + lay.src[i]), ptr(t), lay.args(d, F, self)
-                            # source i: the next args[0] elements (cast, copy) or columns (transpose: ldd = the buffer's width)
-                            # of the buffer; a fragment layout takes the source index as its part
-                            off = 0 if lay.op == "frag" else i * args[0] * t.element_size()
-                            extra = (t.shape[1],) if lay.op == "transpose" else (i,) if lay.op == "frag" else ()
-                            getattr(self, "p_" + lay.op)(src, dst + off, *args, *extra)
-        self.model._pack_extra(self)
+    def _pack_body(self, record: bool):
+        super()._pack_body(record)
+        tokens.pack(self)           # (the one packed buffer that is no layout of one parameter)
 
     def _head_alloc(self) -> Dict[str, torch.Tensor]:
         a = {n: self._t(*shape, dtype=(torch.float32 if is32 else None)) for n, (shape, is32) in _head_tensors(self.cfg, self.B).items()}
@@ -939,7 +968,7 @@ class ForwardEngine(EngineBase):
         # CLS rows (D:1157) + pos row 0
         call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
              0, 1, self.dtype, st)
-        self.model._extra_tokens_fwd(self, eeg1, eeg2, train)
+        tokens.forward(self, eeg1, eeg2, train)
         return a["x0"]
 
     def _heads_fwd(self, z, labels, train: bool, p: float):
@@ -1107,6 +1136,7 @@ class Engine(ForwardEngine):
         if self.attn_long:          # delta = rowsum(dctx * ctx) of eg_attention_long_bwd, [NB, H, S]
             g["attn_delta"] = self._t(NB * self.cfg.num_heads * self.S, dtype=torch.float32)
         self.g = g
+        tokens.alloc_bwd(self)
 
     def check_overflow_and_update_scaler(self):
         """autograd path at fp16: flags a non-finite gradient norm (eg_step_state.found_inf) and adapts the internal loss scale,
@@ -1424,7 +1454,7 @@ class Engine(ForwardEngine):
         else:
             call("eg_batch_rowsum", ptr(dseq), fp.g_ptr("pos_embed.pos_embed.weight"), NB, S, d, S, self.dtype, st)
             call("eg_cast", fp.g_ptr("pos_embed.pos_embed.weight"), fp.g_ptr("cls_token"), d, EG_F32, st)
-        self.model._extra_tokens_bwd(self, dseq)
+        tokens.backward(self, dseq)
         b.seg("tokens")         # positions, token generators, the extra heads: everything registered between conv-1 and the encoder
         if not b.fused_tokens:
             call("eg_rows_gather_gate", ptr(dseq), ptr(a["h1"]), dy1, ymap, NB, S, d,
@@ -1539,7 +1569,7 @@ def _inference_tensors(cfg, B: int, T: int, dtype: int):
 def inference_workspace_bytes(cfg, B: int, T: int, dtype: int) -> Tuple[int, int]:
     """(with the shared scratch set, without it): bytes of the activations an InferenceEngine of this shape holds, device-free.
     Independent of num_layers.  Not counted: the packed parameters `w`, the 4-byte counter of the fused heads, and the buffers of
-    the optional token families (tokens.py), which are the training engine's."""
+    the optional token families (tokens.alloc), which are the training engine's."""
     es = 4 if dtype == EG_F32 else 2
     a, sc = _inference_tensors(cfg, B, T, dtype)
 
@@ -1559,7 +1589,8 @@ class AttnStats:
 
 class InferenceEngine(ForwardEngine):
     """Forward-only engine for a fixed (B, T): predicts without saving what a backward would read.  No per-layer activations (two
-    ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts, always p = 0, and
+    ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts -- _held's one
+    rule (no `bwd`, no `fused`) over every stage of LAYOUTS, the token families' among them -- always p = 0, and
     it neither reads nor writes the model's step state, forward counter or seeds.  Where a layer half has a lean launch
     (eg_attn_block_fwd / eg_ffn_chain with only ln_out stored) it takes it; every other launch is the training engine's, writing
     into ONE shared scratch set allocated on first need.  Same bits as Engine.forward(train=False)."""

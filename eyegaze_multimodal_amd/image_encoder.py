@@ -72,6 +72,7 @@ class ImageEngine(EngineBase):
         # business (MultimodalTrainer._engines copies the EEG engine's scaler_on)
         self.fused_tail, self.scaler_on = False, False
         d, nc = model.d_model, model.num_classes
+        self.w = self._alloc_w()
         tokens.spec_cnn_alloc(self, 2 * B, F, W)
         self.a["feat"] = self._t(2 * B, d)                     # image order (b, player): a row pair IS the head's input row
         self.a["logits"] = self._t(B, nc, dtype=torch.float32)
@@ -91,8 +92,11 @@ class ImageEngine(EngineBase):
         g["partial"] = self._t(self.tn_cap, dtype=torch.float32)
         g["cspart"] = self._t(512 * 1024, dtype=torch.float32)
 
-    def _pack_body(self):
-        tokens.spec_cnn_pack(self, "cnn.")
+    def _stages(self):
+        yield "cnn", "cnn.", ""
+
+    def _held(self, group, l, every: bool):
+        return group
 
     def forward(self, img1: torch.Tensor, img2: torch.Tensor, train: bool):
         B, sp = self.B, self.sp

@@ -1,6 +1,6 @@
 """Optional token families in front of the temporal tokens: spectrogram tokens (D:40-135) and inter-stream
-synchrony (IBS) tokens, matrix form (D:473-911) or scalar form (D:178-470).  Called by the engine through the
-module hooks; every op is a C-ABI kernel (signal.hip, spec.hip, gemm.hip).  D = dual_eeg_transformer.py."""
+synchrony (IBS) tokens, matrix form (D:473-911) or scalar form (D:178-470).  Called by the engine directly; their packed
+weights are stages of engine.LAYOUTS; every op is a C-ABI kernel (signal.hip, spec.hip, gemm.hip).  D = dual_eeg_transformer.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,23 +10,18 @@ import torch
 
 from . import _lib as L
 from ._lib import EG_F32, call, ptr, rowmap
-from .engine import SITE_IBSGEN, SITE_IBSTOK, SITE_SPEC, Engine
 
 ROBUST_BANDS = [(0.5, 45.0), (0.5, 4.0), (4.0, 8.0), (8.0, 13.0), (13.0, 30.0), (30.0, 45.0)]  # D:500-507
 SCALAR_BANDS = [(4.0, 8.0), (8.0, 13.0), (13.0, 30.0), (30.0, 45.0)]                           # D:201-206
 
 
-def _bands(eng: Engine, bands):
-    key = ("bands", len(bands))
-    if key not in eng.w:
-        lo = (C.c_float * len(bands))(*[b[0] for b in bands])
-        hi = (C.c_float * len(bands))(*[b[1] for b in bands])
-        eng.w[key] = (lo, hi)
-    lo, hi = eng.w[key]
-    return C.addressof(lo), C.addressof(hi), len(bands)
+def _bands(eng):
+    """(address of the lower band edges, of the upper ones, their count) for the synchrony kernels"""
+    lo, hi = eng.band_edges
+    return C.addressof(lo), C.addressof(hi), len(lo)
 
 
-def _nbin(eng: Engine, bands) -> int:
+def _nbin(eng, bands) -> int:
     return nbin_for(eng.T, eng.cfg.sampling_rate, max(b[1] for b in bands))
 
 
@@ -45,18 +40,18 @@ def nbin_for(T: int, fs: float, hi: float) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
-def _alloc(model, eng: Engine):
-    if getattr(eng, "_tok_alloc", False):
-        return
+def alloc(eng):
+    """The families' activations and metadata (eng.sp, eng.ib, eng.band_edges), at the engine's construction"""
     cfg, d, B, NB, Cn, T = eng.cfg, eng.cfg.d_model, eng.B, eng.NB, eng.C, eng.T
     f32 = torch.float32
-    a, w = eng.a, eng.w
+    a = eng.a
     if cfg.use_spectrogram:
         spec_cnn_alloc(eng, NB * Cn, cfg.spec_freq_bins, 1 + T // cfg.spec_hop_length)
     if cfg.use_ibs:
         bands = ROBUST_BANDS if cfg.use_robust_ibs else SCALAR_BANDS
         nb, nsig = len(bands), NB * Cn
-        eng.ib = dict(nb=nb, nsig=nsig, nbin=_nbin(eng, bands), bands=bands)
+        eng.ib = dict(nb=nb, nsig=nsig, nbin=_nbin(eng, bands))
+        eng.band_edges = tuple((C.c_float * nb)(*[b[i] for b in bands]) for i in (0, 1))    # host arrays the kernels' launchers read
         a["ib_xb"] = eng._t(nb, nsig, T, dtype=f32)
         a["ib_ph"] = eng._t(nb, nsig, T, dtype=f32)
         a["ib_stats"] = eng._t(nb, nsig, 4, dtype=f32)
@@ -72,24 +67,15 @@ def _alloc(model, eng: Engine):
             a["ib_xhat"] = eng._t(B * ntok, E, dtype=f32)
             a["ib_u"] = eng._t(B * ntok, 64)
             a["ib_h"] = eng._t(B * ntok, 64)
-            w["ib_add"] = eng._t(1, 1 + ntok, d)
-            w["ib0"] = eng._t(64, E)
-            w["ib0T"] = eng._t(E, 64)
-            w["ib3"] = eng._t(d, 64)
-            w["ib3T"] = eng._t(64, d)
+            eng.w["ib_add"] = eng._t(1, 1 + ntok, d)
         else:
             a["ig_feat"] = eng._t(B, 64, dtype=f32)
             a["ig_featp"] = eng._t(B, 64)
             a["ig_h"] = eng._t(B, 2 * d)
-            w["ig0"] = eng._t(2 * d, 64)
-            w["ig3"] = eng._t(d, 2 * d)
-            w["ig3T"] = eng._t(2 * d, d)
-    eng._tok_alloc = True
 
 
-def _alloc_bwd(model, eng: Engine):
-    if getattr(eng, "_tok_alloc_bwd", False):
-        return
+def alloc_bwd(eng):
+    """The families' gradient buffers, from Engine._alloc_bwd"""
     cfg, d, B = eng.cfg, eng.cfg.d_model, eng.B
     g = eng.g
     if cfg.use_spectrogram:
@@ -105,63 +91,47 @@ def _alloc_bwd(model, eng: Engine):
         else:
             g["ig_dtok"] = eng._t(B, d)
             g["ig_dh"] = eng._t(B, 2 * d)
-    eng._tok_alloc_bwd = True
 
 
-# ------------------------------------------------------------------------------------------------
-def pack(model, eng: Engine):
-    cfg, d, fp, w, dt, st = eng.cfg, eng.cfg.d_model, eng.fp, eng.w, eng.dtype, eng.stream
-    if not (cfg.use_spectrogram or cfg.use_ibs):
-        return
-    _alloc(model, eng)
-    if cfg.use_spectrogram:
-        pre = "spectrogram_generator."
-        spec_cnn_pack(eng, pre)
+def pack(eng):
+    """w["ib_add"], the additive row table of the token GEMM: type_embedding[i] + pos[1 + i]   (D:909, A:120-126).  Filled from two
+    parameters, so no layout of engine.LAYOUTS; every other packed weight of the families is one."""
+    cfg, fp = eng.cfg, eng.fp
     if cfg.use_ibs and cfg.use_robust_ibs:
-        pre, ntok, E = "ibs_tokenizer.", cfg.num_ibs_tokens, eng.C * eng.C
-        eng.p_cast(fp.p_ptr(pre + "bottleneck.0.weight"), ptr(w["ib0"]), 64 * E)
-        eng.p_transpose(fp.p_ptr(pre + "bottleneck.0.weight"), ptr(w["ib0T"]), 64, E, 64)
-        eng.p_cast(fp.p_ptr(pre + "bottleneck.3.weight"), ptr(w["ib3"]), d * 64)
-        eng.p_transpose(fp.p_ptr(pre + "bottleneck.3.weight"), ptr(w["ib3T"]), d, 64, d)
-        # additive row table of the token GEMM: type_embedding[i] + pos[1 + i]   (D:909, A:120-126)
-        call("eg_rows_bcast_f32", fp.p_ptr(pre + "type_embedding"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(w["ib_add"]), 1,
-             1 + ntok, d, ntok, 1, 1, dt, st)
-    elif cfg.use_ibs:
-        pre = "ibs_generator.proj."
-        call("eg_pack_conv_weight", fp.p_ptr(pre + "0.weight"), ptr(w["ig0"]), 2 * d, 28, 1, 28, 64, dt, st)
-        eng.p_cast(fp.p_ptr(pre + "3.weight"), ptr(w["ig3"]), d * 2 * d)
-        eng.p_transpose(fp.p_ptr(pre + "3.weight"), ptr(w["ig3T"]), d, 2 * d, d)
+        ntok = cfg.num_ibs_tokens
+        call("eg_rows_bcast_f32", fp.p_ptr("ibs_tokenizer.type_embedding"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(eng.w["ib_add"]),
+             1, 1 + ntok, cfg.d_model, ntok, 1, 1, eng.dtype, eng.stream)
 
 
 # ------------------------------------------------------------------------------------------------
-def ibs_analytic(eng: Engine, eeg1, eeg2):
+def ibs_analytic(eng, eeg1, eeg2):
     """Band-passed signals, Hilbert phases and per-signal statistics of all 2B*C signals (D:527-591)."""
     ib, a = eng.ib, eng.a
-    lo, hi, nb = _bands(eng, ib["bands"])
+    lo, hi, nb = _bands(eng)
     xcat = torch.cat([eeg1, eeg2], 0)  # [NB, C, T] player-1 windows then player-2 windows (device copy, plumbing)
     eng._keep = xcat
     call("eg_ibs_analytic", ptr(xcat), ptr(a["ib_xb"]), ptr(a["ib_ph"]), ptr(a["ib_stats"]), ptr(a["ib_spec"]), ib["nsig"], eng.T,
          float(eng.cfg.sampling_rate), ib["nbin"], lo, hi, nb, eng.stream)
 
 
-def ibs_pairs(eng: Engine):
+def ibs_pairs(eng):
     """[B, 6, 7, C, C] connectivity matrices from the analytic signals (D:593-819)."""
     ib, a = eng.ib, eng.a
-    lo, hi, nb = _bands(eng, ib["bands"])
+    lo, hi, nb = _bands(eng)
     call("eg_ibs_pairs", ptr(a["ib_xb"]), ptr(a["ib_ph"]), ptr(a["ib_stats"]), ptr(a["ib_spec"]), ptr(a["ib_conn"]), eng.B, eng.C,
          eng.T, float(eng.cfg.sampling_rate), ib["nbin"], lo, hi, nb, eng.stream)
 
 
-def ibs_matrices(model, eng: Engine, eeg1, eeg2) -> torch.Tensor:
+def ibs_matrices(eng, eeg1, eeg2) -> torch.Tensor:
     """Stand-alone call of the matrix generator (what `model.ibs_matrix_generator(eeg1, eeg2)` returns, D:760-819)."""
-    _alloc(model, eng)
     ibs_analytic(eng, eeg1, eeg2)
     ibs_pairs(eng)
     return eng.a["ib_conn"].index_select(2, eng.a["ib_fidx"].long())
 
 
-def forward(model, eng: Engine, eeg1, eeg2, train: bool):
-    cfg = eng.cfg
+def forward(eng, eeg1, eeg2, train: bool):
+    from .engine import SITE_IBSGEN, SITE_IBSTOK
+    cfg, model = eng.cfg, eng.model
     if not (cfg.use_spectrogram or cfg.use_ibs):
         return
     d, B, NB, Cn, T, S, a, w, fp, es, st, dt = cfg.d_model, eng.B, eng.NB, eng.C, eng.T, eng.S, eng.a, eng.w, eng.fp, eng.es, eng.stream, eng.dtype
@@ -169,7 +139,7 @@ def forward(model, eng: Engine, eeg1, eeg2, train: bool):
     n_ibs = eng.n_ibs
     if cfg.use_ibs:
         ib = eng.ib
-        lo, hi, nb = _bands(eng, ib["bands"])
+        lo, hi, nb = _bands(eng)
         fs = float(cfg.sampling_rate)
         ibs_analytic(eng, eeg1, eeg2)
         if cfg.use_robust_ibs:
@@ -227,6 +197,7 @@ def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
     epilogue writes rows addressed by c_map at out_ptr (+ residual rows r_map).  Images are eng.a["spimg"] [nimg, F, nfr] f32;
     parameters are `pre`spec_conv.{0,3}.* / `pre`proj.{0,3}.*.  Shared by the spectrogram tokens of DualEEGTransformer and by the
     image branch of the multimodal fusion model (image_encoder.py)."""
+    from .engine import SITE_SPEC
     a, w, fp, dt, st, sp, d = eng.a, eng.w, eng.fp, eng.dtype, eng.stream, eng.sp, eng.cfg.d_model
     F, nfr, Hp, Wp, nimg = sp["F"], sp["nfr"], sp["Hp"], sp["Wp"], sp["nimg"]
     call("eg_spec_conv1_fwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
@@ -258,29 +229,12 @@ def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
              residual=residual_ptr)
 
 
-def spec_cnn_pack(eng, pre):
-    """compute-dtype copies of the CNN's GEMM weights (run once per optimiser step, from the fp32 masters)"""
-    fp, w, dt, st, d = eng.fp, eng.w, eng.dtype, eng.stream, eng.cfg.d_model
-    call("eg_pack_conv2d_weight", fp.p_ptr(pre + "spec_conv.3.weight"), ptr(w["spc2"]), 64, 32, 0, dt, st)
-    call("eg_pack_conv2d_weight", fp.p_ptr(pre + "spec_conv.3.weight"), ptr(w["spc2T"]), 64, 32, 1, dt, st)
-    eng.p_cast(fp.p_ptr(pre + "proj.0.weight"), ptr(w["spp0"]), 2 * d * 1024)
-    eng.p_transpose(fp.p_ptr(pre + "proj.0.weight"), ptr(w["spp0T"]), 2 * d, 1024, 2 * d)
-    eng.p_cast(fp.p_ptr(pre + "proj.3.weight"), ptr(w["spp3"]), d * 2 * d)
-    eng.p_transpose(fp.p_ptr(pre + "proj.3.weight"), ptr(w["spp3T"]), d, 2 * d, d)
-
-
 def spec_cnn_alloc(eng, nimg, F, nfr):
     """workspaces of spec_cnn_forward / spec_cnn_backward for nimg images of F x nfr"""
     d, f32 = eng.cfg.d_model, torch.float32
-    a, w = eng.a, eng.w
+    a = eng.a
     Hp, Wp = F // 2, nfr // 2
     eng.sp = dict(F=F, nfr=nfr, Hp=Hp, Wp=Wp, nimg=nimg, rows=nimg * (Hp + 2) * Wp)
-    w["spc2"] = eng._t(64, 384)
-    w["spc2T"] = eng._t(32, 768)
-    w["spp0"] = eng._t(2 * d, 1024)
-    w["spp0T"] = eng._t(1024, 2 * d)
-    w["spp3"] = eng._t(d, 2 * d)
-    w["spp3T"] = eng._t(2 * d, d)
     a["spimg"] = eng._t(nimg, F, nfr, dtype=f32)
     a["sp_p1"] = eng._t(nimg * (Hp + 2) * (Wp + 4) * 32 + 4 * (Wp + 4) * 32)   # + slack rows read by the unused tail rows
     a["sp_out2"] = eng._t(nimg * (Hp + 2) * Wp, 64)
@@ -334,11 +288,11 @@ def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01):
 
 
 # ------------------------------------------------------------------------------------------------
-def backward(model, eng: Engine, dseq):
+def backward(eng, dseq):
+    from .engine import SITE_IBSTOK
     cfg = eng.cfg
     if not (cfg.use_spectrogram or cfg.use_ibs):
         return
-    _alloc_bwd(model, eng)
     d, B, NB, Cn, S, a, w, g, fp, es, st, dt = cfg.d_model, eng.B, eng.NB, eng.C, eng.S, eng.a, eng.w, eng.g, eng.fp, eng.es, eng.stream, eng.dtype
     p, p01, train = eng.train_flags
     sc01 = 1.0 / (1.0 - p01) if p01 > 0 else 1.0
@@ -371,7 +325,7 @@ def backward(model, eng: Engine, dseq):
         spec_cnn_backward(eng, "spectrogram_generator.", ptr(dseq) + off, rowmap(d, S * d, Cn), sc01)
 
 
-def fire_spec_backward_hooks(model, eng: Engine):
+def fire_spec_backward_hooks(model, eng):
     """Full backward hooks on spectrogram_generator.spec_conv[3] (Grad-CAM, eeg_metrics.py:758-764) receive
     grad_output = d score / d (that layer's output), stream 2 first (autograd runs the second call's backward first)."""
     if not eng.cfg.use_spectrogram:

@@ -207,6 +207,11 @@ def main():
     WIDE = dict(SMALL, d_model=256, num_heads=4)
     case("l_wide_step", eeg("bf16", **WIDE))
     case("l_wide_infer", infer("bf16", kw=WIDE))
+    # the scalar synchrony token alone (the matrix form and the spectrogram tokens are in a_* / b_* / k_infer_a5_full)
+    SCALAR = dict(use_spectrogram=False, use_robust_ibs=False)
+    for dt in ("bf16", "f32"):
+        case(f"m_scalar_ibs_step_{dt}", eeg(dt, B=4, **SCALAR))
+        case(f"m_scalar_ibs_infer_{dt}", infer(dt, kw=SCALAR))
     with open(args.out, "w") as f:
         json.dump(cases, f, indent=0)
     print(json.dumps({"cases": len(cases), "rows": sum(len(r) for r in cases.values()),

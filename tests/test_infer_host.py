@@ -123,7 +123,8 @@ def test_macro_metrics_from_the_confusion_matrix_reference_known_answer():
 
 
 # ---- the inference engine, recorded on the CPU (profiles/tools/launch_trace.py's recorder: launches are listed, not issued) ----
-BACKWARD_LAYOUTS = ("qkvT", "oT", "oTf", "w1T", "w2T", "w1Tf", "w2Tf", "conv1T", "sfT", "c0T", "i0T")
+BACKWARD_LAYOUTS = ("qkvT", "oT", "oTf", "w1T", "w2T", "w1Tf", "w2Tf", "conv1T", "sfT", "c0T", "i0T",
+                    "spc2T", "spp0T", "spp3T", "ib0T", "ib3T", "ig3T")
 
 
 def test_the_layout_table_marks_exactly_these_layouts_as_the_backward_s():
@@ -166,11 +167,9 @@ def held_ranges(model, eng, extra):
     held = list(eng.a.values()) + list(eng.sc.values()) + [model._flat.flat, eng.state_dev, eng._plan_dev, *extra]
     held += [b for b in model.buffers()] + [getattr(eng, "_keep", None)]
     out = [(t_.data_ptr(), t_.data_ptr() + t_.numel() * t_.element_size()) for t_ in held if torch.is_tensor(t_) and t_.numel()]
-    for v in eng.w.values():
-        if torch.is_tensor(v):
-            out.append((v.data_ptr(), v.data_ptr() + v.numel() * v.element_size()))
-        else:                               # the band-edge arrays of the synchrony kernels (ctypes)
-            out += [(C.addressof(c), C.addressof(c) + C.sizeof(c)) for c in v]
+    out += [(v.data_ptr(), v.data_ptr() + v.numel() * v.element_size()) for v in eng.w.values()]
+    # the band-edge arrays of the synchrony kernels (ctypes)
+    out += [(C.addressof(c), C.addressof(c) + C.sizeof(c)) for c in getattr(eng, "band_edges", ())]
     return out
 
 
