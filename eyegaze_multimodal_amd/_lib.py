@@ -192,6 +192,9 @@ SIGNATURES = {
     "eg_ibs_scalar": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _I, _I, _I, _I, _P],
     "eg_affine_grad": [_P, _P, _P, _I, _I, _I, _I, _P],
     "eg_ibs_inorm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "eg_ibs_inorm_band": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "eg_ibs_class_accumulate_scratch_elems": [_I, _I, _I, _I, _I],   # returns int64_t: ibs_class_scratch_elems() below
+    "eg_ibs_class_accumulate": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "eg_gelu_fwd": [_P, _P, _L, _I, _F, _U, _P, _P],
     "eg_gelu_bwd": [_P, _P, _P, _L, _I, _F, _U, _P, _P],
     "eg_stft_logmag": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -244,6 +247,13 @@ def attn_stats_scratch_elems(NB: int, S: int, H: int) -> int:
     l = lib()
     l.eg_attention_stats_scratch_elems.restype = C.c_int64
     return int(l.eg_attention_stats_scratch_elems(NB, S, H))
+
+
+def ibs_class_scratch_elems(B: int, nbands: int, nfeat: int, E: int, ncls: int) -> int:
+    """Floats of scratch eg_ibs_class_accumulate needs for this shape (host only; 0: none, -1: bad shape)"""
+    l = lib()
+    l.eg_ibs_class_accumulate_scratch_elems.restype = C.c_int64
+    return int(l.eg_ibs_class_accumulate_scratch_elems(B, nbands, nfeat, E, ncls))
 
 
 def exported_symbols():

@@ -641,11 +641,12 @@ __global__ __launch_bounds__(64) void stft_logmag_kernel(const float* __restrict
 // grid (column blocks of 256, B): a thread owns ONE column e of a window pair and requests its nb * nf <= 56 values before the first
 // is used (the first form walked four columns per thread through three passes of dependent loads: 161 us at C = 32 for 44 MB).
 // The additions run in the order of that form.
-template <typename T>
-__global__ __launch_bounds__(256) void ibs_inorm_kernel(const float* __restrict__ conn, const int* __restrict__ fidx,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        T* __restrict__ out, float* __restrict__ xhat, int B, int nb, int nf, int E,
-                                                        int use_norm) {
+// BAND (eg_ibs_inorm_band): the nf tokens of band `zero_band` enter as exact zeros without being loaded (-1: none), and xhat may
+// be null (not stored).  Everything else is the one body, so both kernels round alike.
+template <typename T, bool BAND>
+__device__ __forceinline__ void ibs_inorm_body(const float* __restrict__ conn, const int* __restrict__ fidx,
+                                               const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ out,
+                                               float* __restrict__ xhat, int nb, int nf, int E, int use_norm, int zero_band) {
   constexpr int MAXTOK = MAX_BANDS * 7;
   const int b = blockIdx.y;
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -657,7 +658,7 @@ __global__ __launch_bounds__(256) void ibs_inorm_kernel(const float* __restrict_
     v[tkn] = 0.f;
     if (tkn < ntok) {
       const int band = tkn / nf, f = fidx[tkn % nf];
-      v[tkn] = conn[(((size_t)b * nb + band) * 7 + f) * E + e];
+      if (!BAND || band != zero_band) v[tkn] = conn[(((size_t)b * nb + band) * 7 + f) * E + e];
     }
   }
   float s = 0.f;
@@ -680,11 +681,83 @@ __global__ __launch_bounds__(256) void ibs_inorm_kernel(const float* __restrict_
       float o = v[tkn];
       if (use_norm) {
         const float xh = (v[tkn] - mean) * rstd;
-        xhat[((size_t)b * ntok + tkn) * E + e] = xh;
+        if (!BAND || xhat) xhat[((size_t)b * ntok + tkn) * E + e] = xh;
         o = xh * ga + be;
       }
       Elem<T>::st(out + ((size_t)b * ntok + tkn) * E + e, o);
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void ibs_inorm_kernel(const float* __restrict__ conn, const int* __restrict__ fidx,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        T* __restrict__ out, float* __restrict__ xhat, int B, int nb, int nf, int E,
+                                                        int use_norm) {
+  ibs_inorm_body<T, false>(conn, fidx, gamma, beta, out, xhat, nb, nf, E, use_norm, -1);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void ibs_inorm_band_kernel(const float* __restrict__ conn, const int* __restrict__ fidx,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             T* __restrict__ out, float* __restrict__ xhat, int nb, int nf, int E,
+                                                             int use_norm, int zero_band) {
+  ibs_inorm_body<T, true>(conn, fidx, gamma, beta, out, xhat, nb, nf, E, use_norm, zero_band);
+}
+
+// Per-class sums of the connectivity matrices (eg_ibs_class_accumulate).  A "column" is one (band, selected feature, e) entry:
+// ncol = nb * nf * E of them per sample.  grid (column blocks of 256, nsplit): a thread owns ONE column and walks the `chunk`
+// samples of its split in ascending order, CA_UNROLL loads in flight; the label is the same for the whole wave.  The up to 16
+// class accumulators are named by an unrolled class loop of selects (a runtime-indexed register array would live in scratch
+// memory).  nsplit == 1: the sums are added straight into class_sum; else they go to part[split][class][column] and
+// ibs_class_reduce_kernel adds the splits in ascending order.  Workgroup (0, 0) also counts the labels.
+constexpr int CA_MAX_CLS = 16, CA_UNROLL = 8;
+__global__ __launch_bounds__(256) void ibs_class_accumulate_kernel(const float* __restrict__ conn, const int* __restrict__ fidx,
+                                                                   const int64_t* __restrict__ labels, float* __restrict__ class_sum,
+                                                                   int* __restrict__ class_count, float* __restrict__ part, int B,
+                                                                   int nb, int nf, int E, int ncls, int chunk, int nsplit) {
+  const int ncol = nb * nf * E;
+  const int col = blockIdx.x * 256 + threadIdx.x, sp = blockIdx.y;
+  if (blockIdx.x == 0 && sp == 0 && (int)threadIdx.x < ncls) {
+    int n = 0;
+    for (int b = 0; b < B; ++b) n += labels[b] == (int64_t)threadIdx.x;
+    class_count[threadIdx.x] += n;
+  }
+  if (col >= ncol) return;
+  const int tkn = col / E, e = col - tkn * E;
+  const int band = tkn / nf, f = fidx[tkn - band * nf];
+  const size_t stride = (size_t)nb * 7 * E;
+  const float* src = conn + ((size_t)band * 7 + f) * E + e;
+  const int b0 = sp * chunk, b1 = min(B, b0 + chunk);
+  float acc[CA_MAX_CLS];
+#pragma unroll
+  for (int c = 0; c < CA_MAX_CLS; ++c) acc[c] = 0.f;
+  for (int bb = b0; bb < b1; bb += CA_UNROLL) {
+    float v[CA_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CA_UNROLL; ++u) v[u] = bb + u < b1 ? src[(size_t)(bb + u) * stride] : 0.f;
+#pragma unroll
+    for (int u = 0; u < CA_UNROLL; ++u)
+      if (bb + u < b1) {
+        const int64_t lab = labels[bb + u];
+#pragma unroll
+        for (int c = 0; c < CA_MAX_CLS; ++c) acc[c] = lab == c ? acc[c] + v[u] : acc[c];
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < CA_MAX_CLS; ++c)
+    if (c < ncls) {
+      if (nsplit == 1) class_sum[(size_t)c * ncol + col] += acc[c];
+      else part[((size_t)sp * ncls + c) * ncol + col] = acc[c];
+    }
+}
+
+// class_sum[i] += part[0][i] + part[1][i] + ... over i < n = ncls * ncol, the splits in ascending order
+__global__ __launch_bounds__(256) void ibs_class_reduce_kernel(const float* __restrict__ part, float* __restrict__ class_sum,
+                                                               long long n, int nsplit) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int sp = 0; sp < nsplit; ++sp) s += part[(long long)sp * n + i];
+  class_sum[i] += s;
 }
 
 // GELU(erf) forward with dropout / backward:  h = drop(gelu(u));  du = dh * mask * gelu'(u)
@@ -850,6 +923,71 @@ extern "C" int eg_ibs_inorm(const float* conn, const int* fidx, const float* gam
                        nfeat, E, use_norm);
   });
   EG_LAUNCH_CHECK("ibs_inorm");
+  return 0;
+}
+
+extern "C" int eg_ibs_inorm_band(const float* conn, const int* fidx, const float* gamma, const float* beta, void* out,
+                                 float* xhat, int B, int nbands, int nfeat, int E, int use_norm, int zero_band, int dtype,
+                                 void* stream) {
+  if (eg_dtype_check("eg_ibs_inorm_band", dtype, true)) return 1;
+  EG_CHECK(B > 0 && B < 65536 && nbands > 0 && nbands <= MAX_BANDS && nfeat > 0 && nfeat <= 7 && E > 0,
+           "eg_ibs_inorm_band: bad shape B=%d nbands=%d nfeat=%d E=%d", B, nbands, nfeat, E);
+  EG_CHECK(zero_band >= -1 && zero_band < nbands, "eg_ibs_inorm_band: zero_band=%d outside [-1, %d)", zero_band, nbands);
+  EG_CHECK(conn && fidx && out, "eg_ibs_inorm_band: null pointer");
+  EG_CHECK(!use_norm || (gamma && beta), "eg_ibs_inorm_band: instance norm needs gamma and beta");
+  hipStream_t s = (hipStream_t)stream;
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ibs_inorm_band_kernel<T>, dim3((E + 255) / 256, B), dim3(256), 0, s, conn, fidx, gamma, beta, (T*)out, xhat,
+                       nbands, nfeat, E, use_norm, zero_band);
+  });
+  EG_LAUNCH_CHECK("ibs_inorm_band");
+  return 0;
+}
+
+// The split of eg_ibs_class_accumulate, from the shapes alone: chunks of CA_CHUNK samples, doubled while the grid would exceed
+// CA_MAX_BLOCKS workgroups (C = 32: the columns alone fill the GPU, and fewer splits mean fewer partials to write and re-read).
+constexpr int CA_CHUNK = 16, CA_MAX_BLOCKS = 1024;
+struct ClassPlan { int ncol, colblocks, chunk, nsplit; };
+static bool class_shape_ok(int B, int nbands, int nfeat, int E, int ncls) {
+  return B > 0 && B < 65536 && nbands > 0 && nbands <= MAX_BANDS && nfeat > 0 && nfeat <= 7 && E > 0 && E <= 65536 && ncls >= 1 &&
+         ncls <= CA_MAX_CLS;
+}
+static ClassPlan class_plan(int B, int nbands, int nfeat, int E) {
+  ClassPlan pl;
+  pl.ncol = nbands * nfeat * E;
+  pl.colblocks = (pl.ncol + 255) / 256;
+  pl.chunk = CA_CHUNK;
+  while (pl.chunk < B && (int64_t)pl.colblocks * ((B + pl.chunk - 1) / pl.chunk) > CA_MAX_BLOCKS) pl.chunk *= 2;
+  pl.nsplit = (B + pl.chunk - 1) / pl.chunk;
+  return pl;
+}
+
+extern "C" int64_t eg_ibs_class_accumulate_scratch_elems(int B, int nbands, int nfeat, int E, int ncls) {
+  if (!class_shape_ok(B, nbands, nfeat, E, ncls)) return -1;
+  const ClassPlan pl = class_plan(B, nbands, nfeat, E);
+  return pl.nsplit == 1 ? 0 : (int64_t)pl.nsplit * ncls * pl.ncol;
+}
+
+extern "C" int eg_ibs_class_accumulate(const float* conn, const int* fidx, const int64_t* labels, float* class_sum,
+                                        int32_t* class_count, float* scratch, int64_t scratch_elems, int B, int nbands, int nfeat,
+                                        int E, int ncls, void* stream) {
+  const char* who = "eg_ibs_class_accumulate";
+  EG_CHECK(ncls >= 1 && ncls <= CA_MAX_CLS, "%s: ncls=%d outside [1, 16]", who, ncls);
+  EG_CHECK(class_shape_ok(B, nbands, nfeat, E, ncls), "%s: bad shape B=%d nbands=%d nfeat=%d E=%d", who, B, nbands, nfeat, E);
+  const ClassPlan pl = class_plan(B, nbands, nfeat, E);
+  const long long need = pl.nsplit == 1 ? 0 : (long long)pl.nsplit * ncls * pl.ncol;
+  EG_CHECK(conn && fidx && labels && class_sum && class_count && (scratch || need == 0), "%s: null pointer", who);
+  EG_CHECK(scratch_elems >= need, "%s: scratch holds %lld floats, %lld are needed", who, (long long)scratch_elems, need);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ibs_class_accumulate_kernel, dim3(pl.colblocks, pl.nsplit), dim3(256), 0, s, conn, fidx, labels, class_sum,
+                     (int*)class_count, scratch, B, nbands, nfeat, E, ncls, pl.chunk, pl.nsplit);
+  if (pl.nsplit > 1) {
+    const long long n = (long long)ncls * pl.ncol;
+    hipLaunchKernelGGL(ibs_class_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)scratch, class_sum, n,
+                       pl.nsplit);
+  }
+  EG_LAUNCH_CHECK("ibs_class_accumulate");
   return 0;
 }
 

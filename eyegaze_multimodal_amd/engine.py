@@ -866,6 +866,10 @@ class ForwardEngine(EngineBase):
     def _attn_stats(self, l, qkv, lse, kv_shift):
         """Where a stage's q|k|v rows and lse are complete.  Only the inference engine reduces them (InferenceEngine.attn_stats)."""
 
+    def _conn_stats(self):
+        """Where a["ib_conn"] is complete, after any hook on ibs_matrix_generator (tokens.forward).  Only the inference engine
+        reduces it (InferenceEngine.conn_stats)."""
+
     def ln_fwd(self, x, gname, y, stats):
         call("eg_layernorm_fwd", ptr(x), self.fp.p_ptr(gname + ".weight"), self.fp.p_ptr(gname + ".bias"), ptr(y),
              ptr(stats), self.M, self.cfg.d_model, self.dtype, self.stream)
@@ -883,6 +887,11 @@ class ForwardEngine(EngineBase):
         if pack:
             self.pack_params()
         x = self._front_end_fwd(eeg1, eeg2, train, p01, self.a.get("h1"))
+        self._encode(x, labels, train, p)
+
+    def _encode(self, x, labels, train: bool, p: float):
+        """Token rows x -> the heads' results: layers, final norm, cross stage, heads"""
+        cfg = self.cfg
         # encoder (A:292-295, 326-328), both streams batched (Siamese weights)
         for l in range(cfg.num_layers):
             x = self._layer_fwd(l, x, p)
@@ -932,9 +941,10 @@ class ForwardEngine(EngineBase):
         self.gemm(ptr(hff), ptr(w[f"w2{l}"]), ptr(r2), M, d, F, bias=fp.p_ptr(pre + "ffn.linear2.bias"),
                   drop1=(p, sites["ffn_b"]), drop2=(p, sites["drop2"]), residual=ptr(y1))
 
-    def _front_end_fwd(self, eeg1, eeg2, train: bool, p01: float, h1):
+    def _front_end_fwd(self, eeg1, eeg2, train: bool, p01: float, h1, tokenise: bool = True):
         """Input windows -> token rows a["x0"] (returned): window pack, conv-0, conv-1 (+ positions), the CLS rows and the optional
-        token families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written)."""
+        token families.  h1: conv-1's pre-activation copy, which only the backward reads (None: not written).  tokenise=False
+        leaves the matrix-form synchrony token rows unwritten (tokens.forward)."""
         cfg, d = self.cfg, self.cfg.d_model
         B, NB, S, a, w, fp, es, st = self.B, self.NB, self.S, self.a, self.w, self.fp, self.es, self.stream
         for x in (eeg1, eeg2):
@@ -968,7 +978,7 @@ class ForwardEngine(EngineBase):
         # CLS rows (D:1157) + pos row 0
         call("eg_rows_bcast_f32", fp.p_ptr("cls_token"), fp.p_ptr("pos_embed.pos_embed.weight"), ptr(a["x0"]), NB, S, d, 1,
              0, 1, self.dtype, st)
-        tokens.forward(self, eeg1, eeg2, train)
+        tokens.forward(self, eeg1, eeg2, train, tokenise)
         return a["x0"]
 
     def _heads_fwd(self, z, labels, train: bool, p: float):
@@ -1587,6 +1597,14 @@ class AttnStats:
         self.map_sum, self.diag, self.scratch = map_sum, diag, scratch
 
 
+class ConnStats:
+    """A request to InferenceEngine.conn_stats.  labels [B] i64 -- the current batch's; class_sum [ncls, nbands, nfeat, C, C] f32 and
+    class_count [ncls] i32 are added to; scratch holds at least _lib.ibs_class_scratch_elems(B, nbands, nfeat, C * C, ncls) floats."""
+
+    def __init__(self, labels: torch.Tensor, class_sum: torch.Tensor, class_count: torch.Tensor, scratch: torch.Tensor):
+        self.labels, self.class_sum, self.class_count, self.scratch = labels, class_sum, class_count, scratch
+
+
 class InferenceEngine(ForwardEngine):
     """Forward-only engine for a fixed (B, T): predicts without saving what a backward would read.  No per-layer activations (two
     ping-pong row buffers + one for the normed mid-layer rows), no backward workspace, no backward weight layouts -- _held's one
@@ -1614,6 +1632,7 @@ class InferenceEngine(ForwardEngine):
         self.sc = {}                                       # the shared scratch set: qkv, lse, ctx, r, hff, st -- see _scratch
         self.routes_taken = []                             # (layer, "attn" | "ffn", "lean" | "scratch") of the last forward
         self.attn_stats: Optional[AttnStats] = None        # a plain attribute: the stage whose probabilities the next forwards reduce
+        self.conn_stats: Optional[ConnStats] = None        # likewise: where the next forwards add their connectivity matrices
 
     def _scratch(self, name: str) -> torch.Tensor:
         if name not in self.sc:
@@ -1652,10 +1671,64 @@ class InferenceEngine(ForwardEngine):
         call("eg_attention_stats", ptr(qkv), ptr(lse), ptr(st.map_sum), ptr(st.diag), ptr(st.scratch), st.scratch.numel(),
              self.NB, self.S, self.cfg.num_heads, self.head_dim, kv_shift, self.dtype, self.stream)
 
+    def _conn_stats(self):
+        """eg_ibs_class_accumulate on the batch's matrices: per-class sums and counts added into the request's tensors, no
+        [N, ..., C, C] tensor anywhere (predict.connectivity_statistics)"""
+        st = self.conn_stats
+        if st is None:
+            return
+        conn, nf = self.a["ib_conn"], self.cfg.num_ibs_features
+        ncls = st.class_count.numel()
+        for name, t, shape, dt in (("labels", st.labels, (self.B,), torch.int64),
+                                   ("class_sum", st.class_sum, (ncls, self.ib["nb"], nf, self.C, self.C), torch.float32),
+                                   ("class_count", st.class_count, (ncls,), torch.int32)):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != conn.device:
+                raise L.EgError(f"conn_stats.{name} must be a contiguous {dt} {list(shape)} tensor on {conn.device}")
+        if st.scratch.dtype != torch.float32 or not st.scratch.is_contiguous() or st.scratch.device != conn.device:
+            raise L.EgError(f"conn_stats.scratch must be a contiguous f32 tensor on {conn.device}")
+        call("eg_ibs_class_accumulate", ptr(conn), ptr(self.a["ib_fidx"]), ptr(st.labels), ptr(st.class_sum), ptr(st.class_count),
+             ptr(st.scratch), st.scratch.numel(), self.B, self.ib["nb"], nf, self.C * self.C, ncls, self.stream)
+
     def forward(self, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: Optional[torch.Tensor] = None, pack: bool = True):
         """pack=False: the packed weights of an earlier call still hold (a caller walking many batches packs once)"""
         self.routes_taken = []
         self._forward(eeg1, eeg2, labels, False, pack=pack or self._plan_key is None)
+
+    def forward_band_masks(self, eeg1: torch.Tensor, eeg2: torch.Tensor, bands, each, pack: bool = True):
+        """One forward per entry of `bands` -- None: the plain model; an int b: the model with band b of the connectivity matrices
+        zeroed, what eeg_metrics.py's FrequencyMaskHook causes -- sharing everything the mask does not touch: the front end, the
+        spectrogram tokens, eg_ibs_analytic / eg_ibs_pairs, the hook dispatch and the conn_stats reduction run once; per entry
+        run the tokeniser (eg_ibs_inorm_band, no xhat), the layers, the final norm, the cross stage and the heads, then each(i)
+        is called and reads a["logits"].  The front end writes the token rows into one more [NB, S, d] buffer (allocated on first
+        need), which no layer overwrites: _rows sends layer 0's output to xa.  A model without matrix-form synchrony tokens has
+        nothing to mask (the reference registers no hook then): one plain forward, whose logits serve every entry."""
+        cfg = self.cfg
+        bands = list(bands)
+        if not (cfg.use_ibs and cfg.use_robust_ibs):
+            self.forward(eeg1, eeg2, None, pack=pack)
+            for i in range(len(bands)):
+                each(i)
+            return
+        for b in bands:
+            if b is not None and not (isinstance(b, int) and 0 <= b < self.ib["nb"]):
+                raise L.EgError(f"forward_band_masks: a band is None or an int in [0, {self.ib['nb']}), got {b!r}")
+        self.routes_taken = []
+        self.stream = self._cur_stream()
+        self.train_flags = (0.0, 0.0, False)
+        if pack or self._plan_key is None:
+            self.pack_params()
+        a = self.a
+        if "xf" not in self.sc:
+            self.sc["xf"] = self._t(self.M, cfg.d_model)
+        a["x0"] = self.sc["xf"]
+        try:
+            x = self._front_end_fwd(eeg1, eeg2, False, 0.0, None, tokenise=False)
+            for i, b in enumerate(bands):
+                tokens.ibs_tokens(self, False, zero_band=-1 if b is None else b)
+                self._encode(x, None, False, 0.0)
+                each(i)
+        finally:
+            a["x0"] = a["xa"]
 
 
 def _refused(name: str):

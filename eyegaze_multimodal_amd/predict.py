@@ -5,10 +5,13 @@ attention_statistics is eeg_metrics.py's extract_attention_weights (:465-594) ov
 per-sample diagonals reduced on the device from each batch's q|k|v rows (eg_attention_stats), never a [B, H, S, S] tensor.
 
 predict_loader walks a data.ResidentWindows store instead (--resident: gather launch -> engine, no window visits the host), and
-predict_recording classifies one whole recording pair at any stride.
+predict_recording classifies one whole recording pair at any stride.  connectivity_statistics and
+frequency_sensitivity are eeg_metrics.py's class-mean connectivity matrices (:183-311) and band-masking sensitivity (:318-413)
+with the matrices consumed where eg_ibs_pairs leaves them.
 
     python -m eyegaze_multimodal_amd.predict --config CONFIG.yaml --checkpoint best_model.pt --out FILE.npz [--resident]
-                                             [--attention-stats [cross|LAYER]]
+                                             [--attention-stats [cross|LAYER]] [--connectivity-stats]
+                                             [--frequency-sensitivity]
 """
 from __future__ import annotations
 
@@ -204,6 +207,121 @@ def attention_statistics(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: 
             "predictions": pred.long()}
 
 
+BAND_NAMES = ["broadband", "delta", "theta", "alpha", "beta", "gamma"]      # eeg_metrics.py:372
+
+
+@torch.no_grad()
+def connectivity_statistics(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: torch.Tensor, batch_size: int = 256,
+                            max_samples: Optional[int] = None, class_names=None) -> Dict[str, Any]:
+    """extract_ibs_matrices -> compute_mean_ibs_by_class -> compute_ibs_difference (eeg_metrics.py:183-311) without the per-sample
+    matrices: windows, batches and the whole-batch rule of max_samples as attention_statistics; every batch's [B, 6, nfeat, C, C]
+    matrices -- after any forward hook on model.ibs_matrix_generator -- are added per class on the device
+    (eg_ibs_class_accumulate), the host syncs once, at the end.  Returns
+      class_mean {class name: [nbands, nfeat, C, C] f32 numpy} for every name (zeros for a class that never occurred),
+      class_count {class name: int}, difference (Cooperation - Competition, when both names exist), count = n,
+      logits [n, ncls] f32 and predictions [n] i64 (device tensors, the bits of model.predict).
+    A model without matrix-form synchrony tokens: {} (the reference warns and captures nothing)."""
+    from .engine import ConnStats
+    from ._lib import ibs_class_scratch_elems
+    cfg = model.cfg
+    N, ncls = eeg1.shape[0], cfg.num_classes
+    if batch_size < 1 or N < 1 or labels is None or labels.shape[0] != N or (max_samples is not None and max_samples < 1):
+        raise ValueError(f"connectivity_statistics needs N >= 1 labelled windows, batch_size >= 1 and max_samples >= 1 or None "
+                         f"(got {N}, {batch_size}, {max_samples})")
+    if not (cfg.use_ibs and cfg.use_robust_ibs):
+        return {}
+    names = CLASS_NAMES if class_names is None else list(class_names)
+    if not 1 <= len(names) <= 16:
+        raise ValueError(f"connectivity_statistics serves 1 to 16 class names, got {len(names)}")
+    n = N if max_samples is None else min(N, -(-max_samples // batch_size) * batch_size)
+    dev = next(model.parameters()).device
+    logits = torch.empty(n, ncls, device=dev)
+    pred = torch.empty(n, device=dev, dtype=torch.int32)
+    class_sum = None
+    class_count = torch.zeros(len(names), device=dev, dtype=torch.int32)
+    packed, scratch = set(), {}
+    for i in range(0, n, batch_size):
+        up = lambda t: t[i:min(i + batch_size, n)].to(dev, non_blocking=True)
+        x1, x2, y = model._check_windows(up(eeg1), up(eeg2), up(labels))
+        B = x1.shape[0]
+        eng = model.inference_engine(B, x1.shape[2], dev)
+        nb, nf, Cn = eng.ib["nb"], cfg.num_ibs_features, eng.C
+        if class_sum is None:
+            class_sum = torch.zeros(len(names), nb, nf, Cn, Cn, device=dev)
+        if id(eng) not in scratch:
+            need = ibs_class_scratch_elems(B, nb, nf, Cn * Cn, len(names))
+            if need < 0:
+                raise EgError(f"eg_ibs_class_accumulate does not cover B={B} nbands={nb} nfeat={nf} C={Cn} ncls={len(names)}")
+            scratch[id(eng)] = torch.empty(need, device=dev)
+        eng.conn_stats = ConnStats(y, class_sum, class_count, scratch[id(eng)])
+        try:
+            eng.forward(x1, x2, None, pack=id(eng) not in packed)
+        finally:
+            eng.conn_stats = None           # the engine is model.predict's too
+        packed.add(id(eng))
+        logits[i:i + B].copy_(eng.a["logits"])
+        call("eg_eval_accumulate", ptr(eng.a["logits"]), 0, 0, pred.data_ptr() + 4 * i, 0, 0, B, ncls, eng.stream)
+    counts = class_count.cpu().numpy()                           # the one host sync
+    mean = (class_sum / class_count.clamp(min=1).float().view(-1, 1, 1, 1, 1)).cpu().numpy()
+    out = {"class_mean": {name: mean[c] for c, name in enumerate(names)},
+           "class_count": {name: int(counts[c]) for c, name in enumerate(names)}, "count": n, "logits": logits,
+           "predictions": pred.long()}
+    if "Cooperation" in names and "Competition" in names:
+        out["difference"] = mean[names.index("Cooperation")] - mean[names.index("Competition")]
+    return out
+
+
+def band_metrics_from_confusion(cm) -> Dict[str, float]:
+    """{"accuracy", "f1"} of compute_frequency_sensitivity (eeg_metrics.py:403-411) from a confusion matrix cm[true][predicted]:
+    accuracy_score and the macro F1 of precision_recall_fscore_support(average="macro", zero_division=0), which averages over
+    the classes that occur in the labels or in the predictions -- train_art.macro_metrics_from_confusion's rule."""
+    from .train_art import macro_metrics_from_confusion
+    m = macro_metrics_from_confusion(cm)
+    return {"accuracy": m["eval/accuracy"], "f1": m["eval/f1"]}
+
+
+@torch.no_grad()
+def frequency_sensitivity(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: torch.Tensor, batch_size: int = 256,
+                          band_names=None) -> Dict[str, Any]:
+    """compute_frequency_sensitivity (eeg_metrics.py:318-413) in ONE walk instead of one per band: every batch makes one
+    InferenceEngine.forward_band_masks call over [None, 0, ..., nbands - 1], so the front end, the spectrogram tokens and the
+    synchrony matrices are computed once and only the tokeniser and the encoder run per variant; argmax and the confusion counts
+    stay on the device (eg_eval_accumulate), the host syncs once, at the end.  Returns
+      sensitivity {band name: {"accuracy", "f1"}} with that band masked, baseline (the same pair, nothing masked),
+      confusion [1 + nbands, ncls, ncls] (numpy, [variant][true][predicted]; variant 0 is the baseline),
+      logits [1 + nbands, N, ncls] f32 (device).
+    A model without matrix-form synchrony tokens has nothing to mask (the reference registers no hook): every band equals the
+    baseline."""
+    from . import tokens
+    cfg = model.cfg
+    names = BAND_NAMES if band_names is None else list(band_names)
+    nbands = len(tokens.ROBUST_BANDS)
+    N, ncls = eeg1.shape[0], cfg.num_classes
+    if batch_size < 1 or N < 1 or labels is None or labels.shape[0] != N or len(names) != nbands:
+        raise ValueError(f"frequency_sensitivity needs N >= 1 labelled windows, batch_size >= 1 and {nbands} band names "
+                         f"(got {N}, {batch_size}, {len(names)})")
+    dev = next(model.parameters()).device
+    bands = [None] + list(range(nbands))
+    logits = torch.empty(len(bands), N, ncls, device=dev)
+    pred = torch.empty(N, device=dev, dtype=torch.int32)
+    cm = torch.zeros(len(bands), ncls, ncls, device=dev, dtype=torch.int32)
+    packed = set()
+    for i in range(0, N, batch_size):
+        up = lambda t: t[i:i + batch_size].to(dev, non_blocking=True)
+        x1, x2, y = model._check_windows(up(eeg1), up(eeg2), up(labels))
+        B = x1.shape[0]
+        eng = model.inference_engine(B, x1.shape[2], dev)
+
+        def each(v):
+            logits[v, i:i + B].copy_(eng.a["logits"])
+            call("eg_eval_accumulate", ptr(eng.a["logits"]), ptr(y), 0, pred.data_ptr() + 4 * i, ptr(cm[v]), 0, B, ncls, eng.stream)
+        eng.forward_band_masks(x1, x2, bands, each, pack=id(eng) not in packed)
+        packed.add(id(eng))
+    conf = cm.cpu().numpy()                                      # the one host sync
+    return {"sensitivity": {name: band_metrics_from_confusion(conf[1 + b]) for b, name in enumerate(names)},
+            "baseline": band_metrics_from_confusion(conf[0]), "confusion": conf, "logits": logits}
+
+
 def main(args):
     from . import train_art as TA
     from .data import ResidentWindows, WindowShards
@@ -216,13 +334,15 @@ def main(args):
     model.load_state_dict(ck.get("model_state_dict", ck))
     d, t = config["data"], config["training"]
     ebs, pre = t["per_device_eval_batch_size"], d.get("enable_preprocessing", False)
+    # (callers that build `args` themselves, from before the two flags existed, leave them out)
+    conn_stats, band_masks = getattr(args, "connectivity_stats", False), getattr(args, "frequency_sensitivity", False)
     if args.resident or d.get("resident", False):
         # the store is walked directly: gather launch -> inference engine, batch by batch; no window visits the host
         stores = TA.prepare_store(config, Path(t["output_dir"]) / "recording_store")
         ld = ResidentWindows(stores[args.split], ebs, device, preprocessing=pre)
         out = predict_loader(model, ld)
         y = out["labels"].cpu()
-        if args.attention_stats is not None:
+        if args.attention_stats is not None or conn_stats or band_masks:
             x1, x2 = (torch.cat(p) for p in zip(*((b["eeg1"], b["eeg2"]) for b in ld)))     # stays on the device
     else:
         shards = TA.prepare_shards(config, Path(t["output_dir"]) / "window_shards")
@@ -238,6 +358,18 @@ def main(args):
         if st:
             extra = {"attn_mean_map": st["mean_map"], "attn_diagonals": st["diagonals"],
                      **{f"attn_class_{k}_mean_diagonal": v["mean_diagonal_vector"] for k, v in st["diagonal_stats"].items()}}
+    if conn_stats:
+        st = connectivity_statistics(model, x1, x2, y, batch_size=ebs)
+        if st:
+            extra.update({f"conn_class_{k}_mean": v for k, v in st["class_mean"].items()})
+            extra["conn_class_count"] = np.array(list(st["class_count"].values()), dtype=np.int64)
+            if "difference" in st:
+                extra["conn_difference"] = st["difference"]
+    if band_masks:
+        st = frequency_sensitivity(model, x1, x2, y, batch_size=ebs)
+        for k, v in st["sensitivity"].items():
+            extra[f"band_{k}_accuracy"], extra[f"band_{k}_f1"] = v["accuracy"], v["f1"]
+        extra["band_confusion"] = st["confusion"]
     np.savez(args.out, logits=out["logits"].cpu().numpy(), predictions=out["predictions"].cpu().numpy(), labels=y.numpy(),
              confusion=out["confusion"], loss=out["loss"], **{k.replace("/", "_"): v for k, v in out["metrics"].items()}, **extra)
     print(" ".join(f"{k}: {v:.4f}" for k, v in {"eval/loss": out["loss"], **out["metrics"]}.items()))
@@ -256,4 +388,10 @@ if __name__ == "__main__":
                     help="also reduce the attention probabilities of the cross stage (default) or of encoder layer LAYER: "
                          "attn_mean_map, attn_diagonals and attn_class_<name>_mean_diagonal in the output file")
     ap.add_argument("--attention-max-samples", type=int, default=200, help="the reference's max_samples (whole batches until reached)")
+    ap.add_argument("--connectivity-stats", action="store_true",
+                    help="also average the connectivity matrices per class on the device: conn_class_<name>_mean, conn_difference "
+                         "(Cooperation - Competition) and conn_class_count in the output file")
+    ap.add_argument("--frequency-sensitivity", action="store_true",
+                    help="also classify with each frequency band of the connectivity matrices masked, in one walk: "
+                         "band_<name>_accuracy, band_<name>_f1 and band_confusion in the output file")
     main(ap.parse_args())

@@ -129,8 +129,32 @@ def ibs_matrices(eng, eeg1, eeg2) -> torch.Tensor:
     return eng.a["ib_conn"].index_select(2, eng.a["ib_fidx"].long())
 
 
-def forward(eng, eeg1, eeg2, train: bool):
-    from .engine import SITE_IBSGEN, SITE_IBSTOK
+def ibs_tokens(eng, train: bool, zero_band=None):
+    """a["ib_conn"] -> the synchrony token rows of both streams (D:893-909, D:1163-1165): instance norm over the token axis, the
+    bottleneck, the copy into stream 2.  zero_band None: eg_ibs_inorm, as every forward.  An int in [-1, nbands)
+    (InferenceEngine.forward_band_masks): eg_ibs_inorm_band with that band's tokens zero and no xhat stored."""
+    from .engine import SITE_IBSTOK
+    cfg, d, B, S, a, w, fp, es, st, dt = eng.cfg, eng.cfg.d_model, eng.B, eng.S, eng.a, eng.w, eng.fp, eng.es, eng.stream, eng.dtype
+    ntok, E, nb = cfg.num_ibs_tokens, eng.C * eng.C, eng.ib["nb"]
+    pre, inorm = "ibs_tokenizer.", cfg.ibs_instance_norm
+    gamma, beta = (fp.p_ptr(pre + "instance_norm.weight"), fp.p_ptr(pre + "instance_norm.bias")) if inorm else (0, 0)
+    if zero_band is None:
+        call("eg_ibs_inorm", ptr(a["ib_conn"]), ptr(a["ib_fidx"]), gamma, beta, ptr(a["ib_in"]), ptr(a["ib_xhat"]), B, nb,
+             cfg.num_ibs_features, E, 1 if inorm else 0, dt, st)
+    else:
+        call("eg_ibs_inorm_band", ptr(a["ib_conn"]), ptr(a["ib_fidx"]), gamma, beta, ptr(a["ib_in"]), 0, B, nb,
+             cfg.num_ibs_features, E, 1 if inorm else 0, int(zero_band), dt, st)
+    eng.gemm(ptr(a["ib_in"]), ptr(w["ib0"]), ptr(a["ib_u"]), B * ntok, 64, E, bias=fp.p_ptr(pre + "bottleneck.0.bias"))
+    call("eg_gelu_fwd", ptr(a["ib_u"]), ptr(a["ib_h"]), B * ntok * 64, dt, 0.1 if train else 0.0, SITE_IBSTOK, eng.st_ptr, st)
+    eng.gemm(ptr(a["ib_h"]), ptr(w["ib3"]), ptr(a["x0"]) + d * es, B * ntok, d, 64, c=rowmap(d, S * d, ntok),
+             r=rowmap(d, 0, ntok), bias=fp.p_ptr(pre + "bottleneck.3.bias"), residual=ptr(w["ib_add"]) + d * es)
+    # both streams carry the same synchrony tokens (D:1163-1165)
+    call("eg_rows_copy", ptr(a["x0"]), S, d, eng.n_ibs, 1, 0, B, B, dt, st)
+
+
+def forward(eng, eeg1, eeg2, train: bool, tokenise: bool = True):
+    """tokenise=False (InferenceEngine.forward_band_masks): everything but ibs_tokens, which that caller runs once per variant"""
+    from .engine import SITE_IBSGEN
     cfg, model = eng.cfg, eng.model
     if not (cfg.use_spectrogram or cfg.use_ibs):
         return
@@ -143,7 +167,6 @@ def forward(eng, eeg1, eeg2, train: bool):
         fs = float(cfg.sampling_rate)
         ibs_analytic(eng, eeg1, eeg2)
         if cfg.use_robust_ibs:
-            ntok, E = cfg.num_ibs_tokens, Cn * Cn
             ibs_pairs(eng)
             gen = model.ibs_matrix_generator
             if gen._forward_hooks or gen._forward_pre_hooks:
@@ -153,15 +176,9 @@ def forward(eng, eeg1, eeg2, train: bool):
                 gen._pending = a["ib_conn"].index_select(2, idx)
                 out = gen(eeg1, eeg2)
                 a["ib_conn"].index_copy_(2, idx, out.to(device=eng.device, dtype=torch.float32))
-            pre = "ibs_tokenizer."
-            inorm = cfg.ibs_instance_norm
-            call("eg_ibs_inorm", ptr(a["ib_conn"]), ptr(a["ib_fidx"]), fp.p_ptr(pre + "instance_norm.weight") if inorm else 0,
-                 fp.p_ptr(pre + "instance_norm.bias") if inorm else 0, ptr(a["ib_in"]), ptr(a["ib_xhat"]), B, nb,
-                 cfg.num_ibs_features, E, 1 if inorm else 0, dt, st)
-            eng.gemm(ptr(a["ib_in"]), ptr(w["ib0"]), ptr(a["ib_u"]), B * ntok, 64, E, bias=fp.p_ptr(pre + "bottleneck.0.bias"))
-            call("eg_gelu_fwd", ptr(a["ib_u"]), ptr(a["ib_h"]), B * ntok * 64, dt, p01, SITE_IBSTOK, eng.st_ptr, st)
-            eng.gemm(ptr(a["ib_h"]), ptr(w["ib3"]), ptr(a["x0"]) + d * es, B * ntok, d, 64, c=rowmap(d, S * d, ntok),
-                     r=rowmap(d, 0, ntok), bias=fp.p_ptr(pre + "bottleneck.3.bias"), residual=ptr(w["ib_add"]) + d * es)
+            eng._conn_stats()       # the matrices the tokeniser consumes, hooks' edits included (InferenceEngine.conn_stats)
+            if tokenise:
+                ibs_tokens(eng, train)
         else:
             call("eg_ibs_scalar", ptr(a["ib_xb"]), ptr(a["ib_ph"]), ptr(a["ib_spec"]), ptr(a["ig_feat"]), B, Cn, T, fs, ib["nbin"],
                  lo, hi, nb, 0, nb, 64, st)
@@ -171,8 +188,8 @@ def forward(eng, eeg1, eeg2, train: bool):
                      drop1=(p01, SITE_IBSGEN))
             eng.gemm(ptr(a["ig_h"]), ptr(w["ig3"]), ptr(a["x0"]) + d * es, B, d, 2 * d, c=rowmap(S * d), r=rowmap(0),
                      bias=fp.p_ptr(pre + "3.bias"), residual=ptr(w["pos"]) + d * es)
-        # both streams carry the same synchrony tokens (D:1163-1165)
-        call("eg_rows_copy", ptr(a["x0"]), S, d, n_ibs, 1, 0, B, B, dt, st)
+            # both streams carry the same synchrony token (D:1163-1165)
+            call("eg_rows_copy", ptr(a["x0"]), S, d, n_ibs, 1, 0, B, B, dt, st)
     if cfg.use_spectrogram:
         sp, pre = eng.sp, "spectrogram_generator."
         F, nfr = sp["F"], sp["nfr"]

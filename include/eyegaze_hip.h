@@ -626,6 +626,24 @@ int eg_ibs_scalar(const float* xb, const float* phase, const float* spec, float*
                   void* stream);
 int eg_ibs_inorm(const float* conn, const int* fidx, const float* gamma, const float* beta, void* out, float* xhat, int B,
                  int nbands, int nfeat, int E, int use_norm, int dtype, void* stream);
+/* eg_ibs_inorm for the analyses that run forward only.  zero_band in [-1, nbands): the nfeat tokens of that
+ * band enter the instance norm as exact zeros (what a hook that zeroes conn[:, band] causes: the mean and variance of every
+ * token move), -1: none.  xhat may be NULL: not stored.  zero_band = -1 with xhat gives eg_ibs_inorm's bits in out and xhat;
+ * zero_band = b gives the bits of eg_ibs_inorm on a copy of conn whose band b is zero. */
+int eg_ibs_inorm_band(const float* conn, const int* fidx, const float* gamma, const float* beta, void* out, float* xhat, int B,
+                      int nbands, int nfeat, int E, int use_norm, int zero_band, int dtype, void* stream);
+/* Per-class sums of the connectivity matrices of one batch (conn [B, nbands, 7, E] fp32 as eg_ibs_pairs writes it, fidx the
+ * nfeat selected features, labels [B] int64):
+ *   class_sum[c, band, f, e] += sum over b with labels[b] == c of conn[b, band, fidx[f], e]     [ncls, nbands, nfeat, E] fp32
+ *   class_count[c]           += the number of such b                                            [ncls] int32
+ * both read-modify-written: zero them once, issue every batch's call on one stream, read after the last (as eg_attention_stats'
+ * map_sum).  A label outside [0, ncls) counts in no class (eg_eval_accumulate's rule); 1 <= ncls <= 16.  scratch: at least
+ * eg_ibs_class_accumulate_scratch_elems(...) floats, contents irrelevant on entry (0: one split, scratch may be NULL; -1: bad
+ * shape).  The launch shape and the scratch size follow from the shapes alone; samples are added in ascending order inside a
+ * split and the splits in ascending order: deterministic, no atomics. */
+int64_t eg_ibs_class_accumulate_scratch_elems(int B, int nbands, int nfeat, int E, int ncls);   /* host only, no device needed */
+int eg_ibs_class_accumulate(const float* conn, const int* fidx, const int64_t* labels, float* class_sum, int32_t* class_count,
+                            float* scratch, int64_t scratch_elems, int B, int nbands, int nfeat, int E, int ncls, void* stream);
 /* InstanceNorm affine gradients: dgamma[e] = sum_m dy[m,e]*xhat[m,e], dbeta[e] = sum_m dy[m,e], as nsplit row-split
  * partials partial[sp][0][e] (gamma) | partial[sp][1][e] (beta); sum them in order with eg_reduce_partials */
 int eg_affine_grad(const void* dy, const float* xhat, float* partial, int nsplit, int M, int E, int dtype, void* stream);
