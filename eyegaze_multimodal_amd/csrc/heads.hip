@@ -582,30 +582,105 @@ constexpr int HD = 256;            // d_model of the fused head kernels
 constexpr int HK = 3 * HD;         // width of comb / zf
 constexpr int HP = HD + 8;         // LDS pitch (elements) of a 16-row operand image: 528 B, 16-B aligned, conflict-free b128 reads
 
-// acc[t] += X[16 rows, K] * W[n, K]^T for the wave's NT column tiles (W rows n0 + 16 t + l15), k-steps [ks0, ks1) of 32.
-// The operand order (weights first) and the ascending k-steps are gemm_nt_kernel's, so the sums carry its bits.  X rows are read
-// at xrow (this lane's row, 8 g elements in), advancing 32 elements per step; W straight from global memory (L2-resident).
-// These launches have a handful of workgroups and one dependent pass over the weights each, so what they cost is load round trips:
-// a wave requests ALL its weight fragments of a product (NT x KS 16-B loads per lane) before the first MFMA and pays one trip.
-template <typename T, int NT, int KS>
-__device__ __forceinline__ void head_mma(f32x4 (&acc)[NT], const T* xrow, const T* __restrict__ W, const int ldw, const int n0,
-                                         const int lane) {
+// One wave, one 16 x 16 output tile: X[16 rows, 32 KS] * W[16 rows, 32 KS]^T.  The operand order (weights first) and the
+// ascending k-steps in one accumulator are gemm_nt_kernel's, so the sums carry its bits.  Both operands come straight from global
+// memory (L2-resident) as MFMA fragments: xrow / wrow are this lane's row, 8 g elements in.  What these launches cost is dependent
+// load round trips, so a wave requests EVERY fragment of its product (2 KS 16-B loads per lane) before the first MFMA: one trip.
+template <typename T, int KS>
+__device__ __forceinline__ f32x4 slice_mma(const T* __restrict__ xrow, const T* __restrict__ wrow) {
   typedef typename H16<T>::frag frag;
-  const int l15 = lane & 15, g = lane >> 4;
-  const T* wp = W + (size_t)(n0 + l15) * ldw + 8 * g;
-  frag wf[KS][NT];
+  frag wf[KS], xf[KS];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
+  for (int ks = 0; ks < KS; ++ks) wf[ks] = *(const frag*)(wrow + 32 * ks);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) wf[ks][t] = *(const frag*)(wp + (size_t)16 * t * ldw + 32 * ks);
+  for (int ks = 0; ks < KS; ++ks) xf[ks] = *(const frag*)(xrow + 32 * ks);
   __builtin_amdgcn_sched_barrier(0);      // keep the loads above in one clause (the scheduler would sink them to their uses)
+  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const frag xf = *(const frag*)(xrow + 32 * ks);
+  for (int ks = 0; ks < KS; ++ks) acc = H16<T>::mfma(wf[ks], xf[ks], acc);
+  return acc;
+}
+
+// classifier_ce_fwd_row for R rows of one wave at once (hidden rows hs, hs + pitch, ...; samples b0 .. b0 + nrows - 1 are stored),
+// K = 256, at most NC classes.  Every sum is that function's: per lane k = lane, lane + 64, ... ascending in one chain, wave_sum's
+// butterfly, then the bias; the CE in class order.  What differs is when the loads are requested: there each class's weight is
+// loaded behind its own `c < ncls` test and used at once, a dependent round trip per class and k-step (12 per row at 3 classes:
+// 4.6 us per row, measured in-kernel); here all of them are requested before the first use (classes beyond ncls re-read the
+// last class and are dropped), and the R x NC wave sums are independent chains that interleave.
+template <typename T, int R, int NC>
+__device__ __forceinline__ void classifier_ce_fwd_rows(const T* hs, const int pitch, const float* __restrict__ W,
+                                                       const float* __restrict__ bias, const long long* __restrict__ labels,
+                                                       float* __restrict__ logits, float* __restrict__ sample_loss, const int b0,
+                                                       const int nrows, const int ncls, const int lane) {
+  float w[NC][HD / 64], bs[NC], lg[R][NC];
+  int y[R];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = H16<T>::mfma(wf[ks][t], xf, acc[t]);
+  for (int c = 0; c < NC; ++c) {
+    const int cc = min(c, ncls - 1);
+#pragma unroll
+    for (int i = 0; i < HD / 64; ++i) w[c][i] = W[(size_t)cc * HD + lane + 64 * i];
+    bs[c] = bias[cc];
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    y[r] = (labels && sample_loss && r < nrows) ? (int)labels[b0 + r] : -1;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) lg[r][c] = 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < HD / 64; ++i)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float x = Elem<T>::ld(hs + (size_t)r * pitch + lane + 64 * i);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) lg[r][c] += x * w[c][i];
+    }
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) lg[r][c] = wave_sum(lg[r][c]) + bs[c];
+  if (lane != 0) return;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r >= nrows) break;
+    const int b = b0 + r;
+    float mx = -INFINITY, se = 0.f, ly = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < ncls) mx = fmaxf(mx, lg[r][c]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < ncls) {
+        logits[(size_t)b * ncls + c] = lg[r][c];
+        se += expf(lg[r][c] - mx);
+        if (c == y[r]) ly = lg[r][c];
+      }
+    if (labels && sample_loss) sample_loss[b] = (mx + logf(se)) - ly;
   }
 }
+
+// Whether this workgroup is the LAST of `total` to arrive at *ctr (every thread of the workgroup calls it; `flag` is a word of LDS).
+// What the workgroup stored before is visible to the whole device by then, and the last one may read what the others stored --
+// with loads that bypass the vector cache (block_mean256<true>).  It also puts the counter back to zero for the next launch.
+// ONE thread runs the device-scope fences, behind a barrier that has completed every wave's stores: on gfx950 a release at that
+// scope is an L2 write-back (buffer_wbl2) and an acquire an invalidate (buffer_inv), which the XCD's L2 takes one at a time.
+// With __threadfence() in every wave (256 waves, four fences each) these fences WERE the launch: 42 us of 42.
+__device__ __forceinline__ bool last_arrival(unsigned int* ctr, const int total, int* flag) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const bool last = atomicAdd(ctr, 1u) == (unsigned)(total - 1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (last) *ctr = 0u;
+    *flag = last;
+  }
+  __syncthreads();
+  return *flag != 0;
+}
+
+// The head products are sliced over the GPU: a 256-thread workgroup owns 16 samples and HSL output columns, wave w the 16-column
+// tile HSL s + 16 w.  blockIdx.x = group * (N / HSL) + slice.
+constexpr int HSL = 64;
 
 template <typename T>
 struct HeadsFwd {
@@ -617,80 +692,70 @@ struct HeadsFwd {
   DropCfg d1;
 };
 
-// eg_heads_fwd: zf[:, :256] = comb Wsf^T + b -> hcl = dropout(relu(zf Wc0^T + b)) -> logits, per-sample CE, mean loss.
-// One 512-thread workgroup per 16 samples; wave w owns output columns 32 w .. + 31 of both products.  The 16 x 768 operand rows
-// sit in LDS (comb, then zf: its first 256 columns are product 1's output, the pooled rest eg_pool_fuse_fwd's), the weights come
-// from L2 as MFMA operands in one trip per product; zf and hcl are also stored (the backward reads them).  The workgroup that
-// finishes last (a device counter, reset for the next launch) takes the mean of the per-sample losses in mean_kernel's order.
-constexpr int HKP = HK + 8;        // LDS pitch (elements) of a 768-wide operand row: 1552 B
+// eg_heads_fwd, launch 1: zf[:, :256] = comb Wsf^T + b.  grid = groups x 4 column slices.
 template <typename T>
-__global__ __launch_bounds__(512) void heads_fwd_kernel(HeadsFwd<T> p) {
-  __shared__ __attribute__((aligned(16))) T xs[2][16][HKP];     // [0] comb rows, [1] zf rows
+__global__ __launch_bounds__(256) void heads_fwd_sf_kernel(HeadsFwd<T> p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int m = (blockIdx.x / (HD / HSL)) * 16 + l15;        // rows beyond B: operands clamped, nothing stored
+  const int n0 = (blockIdx.x % (HD / HSL)) * HSL + 16 * wave;
+  const f32x4 acc = slice_mma<T, HK / 32>(p.comb + (size_t)min(m, p.B - 1) * HK + 8 * g, p.Wsf + (size_t)(n0 + l15) * HK + 8 * g);
+  const int n = n0 + 4 * g;
+  float bv[4], v[4];
+  load4(p.bsf + n, bv);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = acc[e] + bv[e];
+  if (m < p.B) store4(p.zf + (size_t)m * HK + n, v);
+}
+
+// eg_heads_fwd, launch 2 (the launch boundary hands it every column of zf): hcl = dropout(relu(zf Wc0^T + b)), same grid.  The
+// pieces that need all 256 columns of hcl go to the workgroup that finishes LAST, found with device counters (no workgroup ever
+// waits for another): per group of 16 samples (counter[1 + group]) the class projection and the per-sample CE on that group's
+// rows of hcl, read back past this CU's vector cache into LDS; over the launch (counter[0], with labels) the mean of the
+// per-sample losses in mean_kernel's order.  Whoever consumes a counter resets it, so the next launch or graph replay starts clean.
+template <typename T>
+__global__ __launch_bounds__(256) void heads_fwd_cls_kernel(HeadsFwd<T> p) {
   __shared__ __attribute__((aligned(16))) T hs[16][HP];
   __shared__ float red[256];
   __shared__ int last_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * 16;
-  const int m = m0 + l15;                            // rows beyond B: operands clamped, nothing stored
-  const int n0 = 32 * wave;
-  for (int c = tid; c < 16 * (HK / 8); c += 512) {   // 16-B chunks: comb whole, zf's pooled columns
-    const int r = c / (HK / 8), ch = c % (HK / 8);
-    const size_t row = (size_t)min(m0 + r, p.B - 1) * HK;
-    *(u32x4*)&xs[0][r][ch * 8] = *(const u32x4*)(p.comb + row + ch * 8);
-    if (ch >= HD / 8) *(u32x4*)&xs[1][r][ch * 8] = *(const u32x4*)(p.zf + row + ch * 8);
-  }
-  __syncthreads();
-
-  f32x4 acc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  head_mma<T, 2, HK / 32>(acc, &xs[0][l15][8 * g], p.Wsf, HK, n0, lane);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int n = n0 + 16 * t + 4 * g;
-    float bv[4], v[4];
-    load4(p.bsf + n, bv);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = acc[t][e] + bv[e];
-    store4(&xs[1][l15][n], v);
-    if (m < p.B) store4(p.zf + (size_t)m * HK + n, v);
-    acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  __syncthreads();
-  head_mma<T, 2, HK / 32>(acc, &xs[1][l15][8 * g], p.Wc0, HK, n0, lane);
+  const int grp = blockIdx.x / (HD / HSL), ngrp = gridDim.x / (HD / HSL);
+  const int m0 = grp * 16, m = m0 + l15;
+  const int n0 = (blockIdx.x % (HD / HSL)) * HSL + 16 * wave;
+  const f32x4 acc = slice_mma<T, HK / 32>(p.zf + (size_t)min(m, p.B - 1) * HK + 8 * g, p.Wc0 + (size_t)(n0 + l15) * HK + 8 * g);
   uint32_t seed_lo = 0, seed_hi = 0;
   if (p.d1.thresh) {
     seed_lo = p.st->seed_lo;
     seed_hi = p.st->seed_hi;
   }
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int n = n0 + 16 * t + 4 * g;
+  {
+    const int n = n0 + 4 * g;
     float bv[4], v[4];
     load4(p.bc0 + n, bv);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[t][e] + bv[e], 0.f);
+    for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + bv[e], 0.f);
     eg_dropout_run<4>(v, p.d1, seed_lo, seed_hi, (uint32_t)m * (uint32_t)HD + (uint32_t)n);
-    store4(&hs[l15][n], v);
     if (m < p.B) store4(p.hcl + (size_t)m * HD + n, v);
   }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = 2 * wave + i;
-    if (m0 + r < p.B)
-      classifier_ce_fwd_row<T>(&hs[r][0], p.W3, p.b3, p.labels, p.logits, p.sloss, m0 + r, HD, p.ncls, lane);
+  if (!last_arrival(p.counter + 1 + grp, HD / HSL, &last_s)) return;
+  for (int c = tid; c < 16 * (HD / 4); c += 256) {            // the group's 16 x 256 rows of hcl, 8-B pieces
+    const int r = c / (HD / 4), ch = c % (HD / 4);
+    const T* src = p.hcl + (size_t)min(m0 + r, p.B - 1) * HD + ch * 4;
+    *(unsigned long long*)&hs[r][ch * 4] = __hip_atomic_load((const unsigned long long*)src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (!p.labels) return;
-  __threadfence();
   __syncthreads();
-  if (tid == 0) last_s = atomicAdd(p.counter, 1u) == gridDim.x - 1;
-  __syncthreads();
-  if (!last_s || tid >= 256) return;                 // (the waves that leave take no further part in a barrier)
-  __threadfence();
+  {
+    const int b0 = m0 + 4 * wave, nrows = min(4, p.B - b0);      // four rows per wave
+    if (nrows > 0) {
+      if (p.ncls <= 4)
+        classifier_ce_fwd_rows<T, 4, 4>(&hs[4 * wave][0], HP, p.W3, p.b3, p.labels, p.logits, p.sloss, b0, nrows, p.ncls, lane);
+      else
+        classifier_ce_fwd_rows<T, 4, 16>(&hs[4 * wave][0], HP, p.W3, p.b3, p.labels, p.logits, p.sloss, b0, nrows, p.ncls, lane);
+    }
+  }
+  if (!p.labels || !last_arrival(p.counter, ngrp, &last_s)) return;
   block_mean256<true>(p.sloss, p.loss, p.B, red);
-  if (tid == 0) *p.counter = 0u;
 }
 
 // dW[n0 .. n0+63][k0 .. k0+63] = sum_m dY[m, n] X[m, k] (+ db = column sums of dY, from the k0 == 0 tiles) for M <= 256 rows,
@@ -772,27 +837,92 @@ __device__ __forceinline__ void small_tn_tile(const T* __restrict__ dY, const in
 }
 constexpr int TN_SMEM = 2 * 64 * TNP * 2;    // 34 816 B
 
+// classifier_dlogits_row for at most NC classes with every load requested before the first use (classes beyond ncls re-read the
+// last one and give 0): the same arithmetic in the same order.  There each logit is loaded behind its own `c < ncls` test.
+template <int NC>
+__device__ __forceinline__ void classifier_dlogits_row_pre(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                           const float* __restrict__ gloss, const float* __restrict__ glogits,
+                                                           const int b, int B, int ncls, float (&dl)[NC]) {
+  float lg[NC], ge[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int cc = min(c, ncls - 1);
+    lg[c] = logits[(size_t)b * ncls + cc];
+    ge[c] = glogits ? glogits[(size_t)b * ncls + cc] : 0.f;
+  }
+  const float gl = (gloss && labels) ? *gloss / (float)B : 0.f;
+  const int y = labels ? (int)labels[b] : -1;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < ncls) mx = fmaxf(mx, lg[c]);
+  float se = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    dl[c] = 0.f;
+    if (c < ncls) {
+      dl[c] = expf(lg[c] - mx);
+      se += dl[c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < ncls) {
+#pragma clang fp contract(off)      // there the product is rounded before the upstream gradient, loaded behind its own test, is added
+      float d = gl * (dl[c] / se - (c == y ? 1.f : 0.f));
+      if (glogits) d += ge[c];
+      dl[c] = d;
+    }
+}
+
 // eg_classifier_ce_bwd_fused: classifier_ce_bwd_kernel's rows (blocks [0, nce)) and classifier_wgrad_kernel's sums (blocks
 // [nce, ..): one per 64 columns of h, all classes) in ONE launch.  A weight-gradient block derives the dlogits itself (the same
 // function of logits / labels / upstream gradients the row blocks store) instead of waiting for another launch to have written
 // them, and stages its [B, 64] slice of h in LDS with every load in flight at once; the sums keep classifier_wgrad_kernel's order
 // (four lanes over b mod 4, ascending b, then lane 0 + 1 + 2 + 3).  B <= 256.
-template <typename T>
-__global__ __launch_bounds__(256) void classifier_ce_bwd_fused_kernel(const T* __restrict__ h, const float* __restrict__ W,
-                                                                      const float* __restrict__ logits,
-                                                                      const long long* __restrict__ labels,
-                                                                      const float* __restrict__ gloss,
-                                                                      const float* __restrict__ glogits,
-                                                                      float* __restrict__ dlogits, T* __restrict__ dh,
-                                                                      float* __restrict__ dW, float* __restrict__ db, int B,
-                                                                      int K, int ncls, int use_gate, float gate_scale, int nce) {
-  __shared__ __attribute__((aligned(16))) T hts[256][64];
-  __shared__ float dls[256][16];
-  __shared__ float red[4][64], redb[4];
+// What the launch cost was dependent trips, measured in-kernel (B = 256, 3 classes): a row block's loads sat one by one behind
+// their `c < ncls` tests (6.4 us), and a weight block's batch loop waited for four LDS reads per sample, 64 samples in a row
+// (16.4 us of the launch's 23.5).  So the body is built for at most NC = 4 or 16 classes: every load of a phase is requested before
+// its first use (classes beyond ncls re-read the last one and are dropped), and the batch loop reads a sample's dlogits as 16-B
+// vectors (zero beyond ncls: exact) eight samples ahead.  The sums and their order are unchanged.
+template <typename T, int NC>
+__device__ __forceinline__ void classifier_ce_bwd_fused_body(const T* __restrict__ h, const float* __restrict__ W,
+                                                             const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                             const float* __restrict__ gloss, const float* __restrict__ glogits,
+                                                             float* __restrict__ dlogits, T* __restrict__ dh, float* __restrict__ dW,
+                                                             float* __restrict__ db, int B, int K, int ncls, int use_gate,
+                                                             float gate_scale, int nce, T (*hts)[64], float (*dls)[16],
+                                                             float (*red)[64], float* redb) {
   const int lane = threadIdx.x & 63, bl = threadIdx.x >> 6;
-  if ((int)blockIdx.x < nce) {
+  if ((int)blockIdx.x < nce) {                                 // classifier_ce_bwd_row's sample, one per wave
     const int b = blockIdx.x * 4 + bl;
-    if (b < B) classifier_ce_bwd_row<T>(b, lane, h, W, logits, labels, gloss, glogits, dlogits, dh, B, K, ncls, use_gate, gate_scale);
+    if (b >= B) return;
+    float dl[NC];
+    classifier_dlogits_row_pre<NC>(logits, labels, gloss, glogits, b, B, ncls, dl);
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < ncls) dlogits[(size_t)b * ncls + c] = dl[c];
+    }
+    for (int k0 = lane; k0 < K; k0 += 256) {
+      float w[4][NC], hv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int kk = min(k0 + 64 * j, K - 1);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) w[j][c] = W[(size_t)min(c, ncls - 1) * K + kk];
+        hv[j] = use_gate ? Elem<T>::ld(h + (size_t)b * K + kk) : 1.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (c < ncls) s += dl[c] * w[j][c];
+        if (use_gate) s = hv[j] > 0.f ? s * gate_scale : 0.f;
+        if (k0 + 64 * j < K) Elem<T>::st(dh + (size_t)b * K + k0 + 64 * j, s);
+      }
+    }
     return;
   }
   const int kb = (blockIdx.x - nce) * 64, k = kb + lane;
@@ -805,27 +935,31 @@ __global__ __launch_bounds__(256) void classifier_ce_bwd_fused_kernel(const T* _
         if (kb + ch * 8 + e < K) hts[b][ch * 8 + e] = h[(size_t)b * K + kb + ch * 8 + e];
   }
   for (int b = threadIdx.x; b < B; b += 256) {
-    float dl[16];
-    classifier_dlogits_row(logits, labels, gloss, glogits, b, B, ncls, dl);
+    float dl[NC];
+    classifier_dlogits_row_pre<NC>(logits, labels, gloss, glogits, b, B, ncls, dl);
 #pragma unroll
-    for (int c = 0; c < 16; ++c) dls[b][c] = dl[c];
+    for (int c = 0; c < NC; ++c) dls[b][c] = dl[c];
   }
   __syncthreads();
-  float s[16], sb[16];
+  float s[NC], sb[NC];
 #pragma unroll
-  for (int c = 0; c < 16; ++c) s[c] = sb[c] = 0.f;
+  for (int c = 0; c < NC; ++c) s[c] = sb[c] = 0.f;
+#pragma unroll 8
   for (int b = bl; b < B; b += 4) {
     const float hv = H16<T>::ld(hts[b][lane]);
 #pragma unroll
-    for (int c = 0; c < 16; ++c)
-      if (c < ncls) {
-        const float dl = dls[b][c];
-        if (k < K) s[c] = fmaf(dl, hv, s[c]);
-        sb[c] += dl;
-      }
-  }
+    for (int c4 = 0; c4 < NC; c4 += 4) {
+      const f32x4 d4 = *(const f32x4*)&dls[b][c4];
 #pragma unroll
-  for (int c = 0; c < 16; ++c)
+      for (int e = 0; e < 4; ++e) {
+        if (k < K) s[c4 + e] = fmaf(d4[e], hv, s[c4 + e]);
+        sb[c4 + e] += d4[e];
+      }
+    }
+  }
+  // the four batch lanes combined, class by class
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
     if (c < ncls) {
       red[bl][lane] = s[c];
       if (lane == 0) redb[bl] = sb[c];
@@ -838,47 +972,58 @@ __global__ __launch_bounds__(256) void classifier_ce_bwd_fused_kernel(const T* _
     }
 }
 
-// eg_heads_bwd_chain: blocks [0, nrt): 16 samples each (512 threads, wave w owns columns 96 w .. + 95), dzf = dhcl Wc0 (all 768
-// columns, stored) then dcomb = dzf[:, :256] Wsf with both 16 x 256 operands in LDS and each product's weights requested in one
-// trip; blocks [nrt, nrt + 48): classifier.0's weight and bias gradient tiles (dhcl^T zf).
 template <typename T>
-__global__ __launch_bounds__(512) void heads_bwd_chain_kernel(const T* __restrict__ dhcl, const T* __restrict__ c0T,
-                                                              const T* __restrict__ sfT, const T* __restrict__ zf,
-                                                              T* __restrict__ dzf, T* __restrict__ dcomb, float* __restrict__ dWc0,
-                                                              float* __restrict__ dbc0, int B, int nrt) {
+__global__ __launch_bounds__(256) void classifier_ce_bwd_fused_kernel(const T* __restrict__ h, const float* __restrict__ W,
+                                                                      const float* __restrict__ logits,
+                                                                      const long long* __restrict__ labels,
+                                                                      const float* __restrict__ gloss,
+                                                                      const float* __restrict__ glogits,
+                                                                      float* __restrict__ dlogits, T* __restrict__ dh,
+                                                                      float* __restrict__ dW, float* __restrict__ db, int B,
+                                                                      int K, int ncls, int use_gate, float gate_scale, int nce) {
+  __shared__ __attribute__((aligned(16))) T hts[256][64];
+  __shared__ __attribute__((aligned(16))) float dls[256][16];
+  __shared__ float red[4][64], redb[4];
+  if (ncls <= 4)
+    classifier_ce_bwd_fused_body<T, 4>(h, W, logits, labels, gloss, glogits, dlogits, dh, dW, db, B, K, ncls, use_gate, gate_scale, nce,
+                                       hts, dls, red, redb);
+  else
+    classifier_ce_bwd_fused_body<T, 16>(h, W, logits, labels, gloss, glogits, dlogits, dh, dW, db, B, K, ncls, use_gate, gate_scale, nce,
+                                        hts, dls, red, redb);
+}
+
+// eg_heads_bwd_chain, launch 1: blocks [0, 12 nrt): dzf = dhcl Wc0, one (16 samples, 64 of the 768 columns) slice each, all
+// columns stored; blocks [12 nrt, 12 nrt + 48): classifier.0's weight and bias gradient tiles (dhcl^T zf), which need nothing of
+// this launch and fill the CUs the slices leave free.
+template <typename T>
+__global__ __launch_bounds__(256) void heads_bwd_dzf_kernel(const T* __restrict__ dhcl, const T* __restrict__ c0T,
+                                                            const T* __restrict__ zf, T* __restrict__ dzf,
+                                                            float* __restrict__ dWc0, float* __restrict__ dbc0, int B, int nsl) {
   __shared__ __attribute__((aligned(16))) char smem[TN_SMEM];
-  if ((int)blockIdx.x >= nrt) {
-    small_tn_tile<T>(dhcl, HD, zf, HK, dWc0, dbc0, B, HK, blockIdx.x - nrt, smem);
+  if ((int)blockIdx.x >= nsl) {
+    small_tn_tile<T>(dhcl, HD, zf, HK, dWc0, dbc0, B, HK, blockIdx.x - nsl, smem);
     return;
   }
-  T (*xs)[16][HP] = (T(*)[16][HP])smem;          // [0] dhcl rows, [1] dzf[:, :256] rows
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * 16;
-  const int m = m0 + l15;
-  {
-    const int r = tid >> 5, ch = tid & 31;       // 16 rows x 32 chunks of 16 B
-    *(u32x4*)&xs[0][r][ch * 8] = *(const u32x4*)(dhcl + (size_t)min(m0 + r, B - 1) * HD + ch * 8);
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int prod = 0; prod < 2; ++prod) {
-    const T* W = prod ? sfT : c0T;
-    T* out = prod ? dcomb : dzf;
-    const int n0 = 96 * wave;
-    f32x4 acc[6];
-#pragma unroll
-    for (int t = 0; t < 6; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    head_mma<T, 6, HD / 32>(acc, &xs[prod][l15][8 * g], W, HD, n0, lane);
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      const int n = n0 + 16 * t + 4 * g;
-      float v[4] = {acc[t][0] + 0.f, acc[t][1] + 0.f, acc[t][2] + 0.f, acc[t][3] + 0.f};   // (gemm_nt's bias-free epilogue adds 0)
-      if (!prod && n < HD) store4(&xs[1][l15][n], v);
-      if (m < B) store4(out + (size_t)m * HK + n, v);
-    }
-    __syncthreads();
-  }
+  const int m = (blockIdx.x / (HK / HSL)) * 16 + l15;
+  const int n0 = (blockIdx.x % (HK / HSL)) * HSL + 16 * wave;
+  const f32x4 acc = slice_mma<T, HD / 32>(dhcl + (size_t)min(m, B - 1) * HD + 8 * g, c0T + (size_t)(n0 + l15) * HD + 8 * g);
+  const float v[4] = {acc[0] + 0.f, acc[1] + 0.f, acc[2] + 0.f, acc[3] + 0.f};   // (gemm_nt's bias-free epilogue adds 0)
+  if (m < B) store4(dzf + (size_t)m * HK + n0 + 4 * g, v);
+}
+
+// eg_heads_bwd_chain, launch 2 (every column of dzf[:, :256] is there at the launch boundary): dcomb = dzf[:, :256] Wsf, same slices.
+template <typename T>
+__global__ __launch_bounds__(256) void heads_bwd_dcomb_kernel(const T* __restrict__ dzf, const T* __restrict__ sfT,
+                                                              T* __restrict__ dcomb, int B) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int m = (blockIdx.x / (HK / HSL)) * 16 + l15;
+  const int n0 = (blockIdx.x % (HK / HSL)) * HSL + 16 * wave;
+  const f32x4 acc = slice_mma<T, HD / 32>(dzf + (size_t)min(m, B - 1) * HK + 8 * g, sfT + (size_t)(n0 + l15) * HD + 8 * g);
+  const float v[4] = {acc[0] + 0.f, acc[1] + 0.f, acc[2] + 0.f, acc[3] + 0.f};
+  if (m < B) store4(dcomb + (size_t)m * HK + n0 + 4 * g, v);
 }
 
 // eg_heads_bwd_pool: blocks [0, B): pool_fuse_bwd_kernel's samples; blocks [B, B + 48): symmetric_fusion.proj's weight and
@@ -1059,7 +1204,9 @@ static void launch_heads_fwd(const void* comb, void* zf, void* hcl, const void* 
   p.bsf = bsf; p.bc0 = bc0; p.W3 = W3; p.b3 = b3;
   p.labels = (const long long*)labels; p.logits = logits; p.sloss = sloss; p.loss = loss; p.counter = counter;
   p.st = state; p.B = B; p.ncls = ncls; p.d1 = make_drop(drop_p, drop_site);
-  hipLaunchKernelGGL(heads_fwd_kernel<T>, dim3((B + 15) / 16), dim3(512), 0, s, p);
+  const dim3 grid(((B + 15) / 16) * (HD / HSL));
+  hipLaunchKernelGGL(heads_fwd_sf_kernel<T>, grid, dim3(256), 0, s, p);
+  hipLaunchKernelGGL(heads_fwd_cls_kernel<T>, grid, dim3(256), 0, s, p);
 }
 
 extern "C" int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* Wsf, const float* bsf, const void* Wc0,
@@ -1074,6 +1221,7 @@ extern "C" int eg_heads_fwd(const void* comb, void* zf, void* hcl, const void* W
   EG_CHECK(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || state), "eg_heads_fwd: dropout needs the step state");
   EG_CHECK(((uintptr_t)comb | (uintptr_t)zf | (uintptr_t)hcl | (uintptr_t)Wsf | (uintptr_t)Wc0 | (uintptr_t)bsf | (uintptr_t)bc0) % 16 == 0,
            "eg_heads_fwd: alignment");
+  EG_CHECK(counter, "eg_heads_fwd: the launch counters (1 + ceil(B / 16) zeroed words) are needed with and without labels");
   hipStream_t s = (hipStream_t)stream;
   eg_dispatch_16(dtype, [&](auto t) {
     launch_heads_fwd<typename decltype(t)::type>(comb, zf, hcl, Wsf, bsf, Wc0, bc0, W3, b3, labels, logits, sample_loss, loss, counter, B,
@@ -1112,12 +1260,12 @@ extern "C" int eg_heads_bwd_chain(const void* dhcl, const void* c0T, const void*
   EG_CHECK(((uintptr_t)dhcl | (uintptr_t)c0T | (uintptr_t)sfT | (uintptr_t)zf | (uintptr_t)dzf | (uintptr_t)dcomb | (uintptr_t)dWc0) % 16 == 0,
            "eg_heads_bwd_chain: alignment");
   hipStream_t s = (hipStream_t)stream;
-  const int nrt = (B + 15) / 16;
-  dim3 grid(nrt + (HD / 64) * (HK / 64));
+  const int nsl = ((B + 15) / 16) * (HK / HSL);
   eg_dispatch_16(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(heads_bwd_chain_kernel<T>, grid, dim3(512), 0, s, (const T*)dhcl, (const T*)c0T, (const T*)sfT, (const T*)zf,
-                       (T*)dzf, (T*)dcomb, dWc0, dbc0, B, nrt);
+    hipLaunchKernelGGL(heads_bwd_dzf_kernel<T>, dim3(nsl + (HD / 64) * (HK / 64)), dim3(256), 0, s, (const T*)dhcl, (const T*)c0T,
+                       (const T*)zf, (T*)dzf, dWc0, dbc0, B, nsl);
+    hipLaunchKernelGGL(heads_bwd_dcomb_kernel<T>, dim3(nsl), dim3(256), 0, s, (const T*)dzf, (const T*)sfT, (T*)dcomb, B);
   });
   EG_LAUNCH_CHECK("heads_bwd_chain");
   return 0;

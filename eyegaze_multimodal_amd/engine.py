@@ -671,6 +671,11 @@ _FUSED_TWIN = {u.key: f for u in _ALL_LAYOUTS for f in _ALL_LAYOUTS
 Rows = namedtuple("Rows", "qkv lse ctx r1 st1 y1 hff gbits r2 st2 out", defaults=(None,) * 11)
 
 
+def _heads_counters(B: int, device) -> torch.Tensor:
+    """eg_heads_fwd's last-workgroup counters: one for the launch and one per group of 16 samples; each launch leaves them zero"""
+    return torch.zeros(1 + (B + 15) // 16, device=device, dtype=torch.int32)
+
+
 def _head_tensors(cfg, B: int):
     """{name: (shape, is fp32)} of what the heads write (compute dtype unless fp32), device-free"""
     d, nc = cfg.d_model, cfg.num_classes
@@ -770,7 +775,7 @@ class ForwardEngine(EngineBase):
 
     def _head_alloc(self) -> Dict[str, torch.Tensor]:
         a = {n: self._t(*shape, dtype=(torch.float32 if is32 else None)) for n, (shape, is32) in _head_tensors(self.cfg, self.B).items()}
-        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)   # eg_heads_fwd's last-workgroup counter
+        a["heads_ctr"] = _heads_counters(self.B, self.device)
         return a
 
     def attn_unfused_fwd(self, x, l, kv_shift, sites, p, R: Rows):
@@ -1578,7 +1583,7 @@ def _inference_tensors(cfg, B: int, T: int, dtype: int):
 
 def inference_workspace_bytes(cfg, B: int, T: int, dtype: int) -> Tuple[int, int]:
     """(with the shared scratch set, without it): bytes of the activations an InferenceEngine of this shape holds, device-free.
-    Independent of num_layers.  Not counted: the packed parameters `w`, the 4-byte counter of the fused heads, and the buffers of
+    Independent of num_layers.  Not counted: the packed parameters `w`, the few counter words of the fused heads, and the buffers of
     the optional token families (tokens.alloc), which are the training engine's."""
     es = 4 if dtype == EG_F32 else 2
     a, sc = _inference_tensors(cfg, B, T, dtype)
@@ -1627,7 +1632,7 @@ class InferenceEngine(ForwardEngine):
         shapes, self._sc_shapes = _inference_tensors(self.cfg, self.B, self.T, self.dtype)
         a = {n: self._t(*shape, dtype=(torch.float32 if is32 else None)) for n, (shape, is32) in shapes.items()}
         a["x0"] = a["xa"]                                  # the front end and the token families write the token rows here
-        a["heads_ctr"] = torch.zeros(1, device=self.device, dtype=torch.int32)
+        a["heads_ctr"] = _heads_counters(self.B, self.device)
         self.a = a
         self.sc = {}                                       # the shared scratch set: qkv, lse, ctx, r, hff, st -- see _scratch
         self.routes_taken = []                             # (layer, "attn" | "ffn", "lean" | "scratch") of the last forward

@@ -499,11 +499,14 @@ int eg_rows_gather_gate(const void* src, const void* gate, void* dst, eg_rowmap 
  * launches it replaces: same MFMA shape and K order as eg_gemm_nt / eg_gemm_tn, same rounding points, same summation trees.
  *   eg_heads_fwd       after eg_pool_fuse_fwd: zf[:, :256] = comb Wsf^T + bsf; hcl = dropout(relu(zf Wc0^T + bc0)) (site
  *                      drop_site, the state's seed); logits = hcl W3^T + b3; with labels the per-sample CE and its mean.
- *                      Wsf / Wc0 [256, 768] in the compute dtype, W3 [ncls, 256] fp32.  `counter` is one zero-initialised
- *                      device word the launch uses to find its last workgroup (left at zero again).
+ *                      Wsf / Wc0 [256, 768] in the compute dtype, W3 [ncls, 256] fp32.  Two launches, one per product, each
+ *                      sliced over (16 samples, 64 output columns) workgroups.  `counter` is 1 + ceil(B / 16) zero-initialised
+ *                      device words (always needed): word 1 + i finds the last workgroup of sample group i, which does that
+ *                      group's class projection and CE, word 0 the last group, which takes the mean; all left at zero again.
  *   eg_classifier_ce_bwd_fused  eg_classifier_ce_bwd (rows and the last Linear's weight / bias gradient) in one launch; B <= 256
  *   eg_heads_bwd_chain dzf [B, 768] = dhcl c0T^T, dcomb [B, 768] = dzf[:, :256] sfT^T (c0T / sfT [768, 256]) and
- *                      dWc0 [256, 768] = dhcl^T zf, dbc0 = colsum(dhcl), summed in-launch; B <= 256
+ *                      dWc0 [256, 768] = dhcl^T zf, dbc0 = colsum(dhcl), summed in-launch; B <= 256.  Two launches, one per
+ *                      product, sliced like eg_heads_fwd's; the weight-gradient tiles ride in the first
  *   eg_heads_bwd_pool  eg_pool_fuse_bwd plus dWsf [256, 768] = dzf[:, :256]^T comb, dbsf = colsum(dzf[:, :256]); B <= 256
  *   eg_token_grad_tail ONE pass over dseq [NB, S, D]: pos_grad[s, :] = sum_b dseq[b, s, :] (eg_batch_rowsum's order), cls_grad =
  *                      pos_grad row 0 (may be NULL), and eg_rows_gather_gate's rows dst[b, r, :] = dseq[b, off + r, :] gated by
