@@ -133,6 +133,7 @@ SIGNATURES = {
     "eg_ffn_chain": [C.POINTER(FfnDesc), _P],
     "eg_ln_bwd_proj": [C.POINTER(LnBwdProjDesc), _P],
     "eg_ln_bwd_proj_blocks": [_I],
+    "eg_ffn_bwd_ln_proj": [C.POINTER(FfnDesc), C.POINTER(LnBwdProjDesc), _P],
     "eg_attn_block_fwd": [C.POINTER(AttnBlockDesc), _P],
     "eg_attn_block_ok": [_I, _I, _I, _I],
     "eg_gemm_tn": [C.POINTER(GemmTNDesc), _P],

@@ -29,7 +29,10 @@
 //     rows themselves remain accepted as the gate (eg_ffn_desc.gate) for callers without a forward launch of this kernel.
 // Arithmetic: the same k-ordered chains of v_mfma_f32_16x16x32 as eg_gemm_nt's kernels and the same epilogue order and dropout
 // indices, so H and C are bit-identical to the two-launch path.
-#include "rowtile.h"
+// eg_ffn_bwd_ln_proj: the backward form going on, in the same launch, with norm-1's backward and out_proj's backward-data product on
+// the C rows it has just completed (the TAIL flag below; steps 2-4 of lnproj.hip through lnproj.h, bit-identical to that launch).
+#include <type_traits>
+#include "lnproj.h"
 
 namespace {
 
@@ -58,8 +61,16 @@ struct FfnArgs {
 // KEEP = false is the LEAN form of a forward that nobody differentiates (<T, 0, 0, 3, true> only): H, C and the LayerNorm statistics
 // are never stored, LN_OUT is the launch's only global store.  The hidden chunk still passes through LDS rounded to 16 bit as
 // product 2's operand and C is still rounded to 16 bit in front of the LayerNorm, so LN_OUT is bit-identical to the keeping form's.
-template <typename T, int GATE, int BOUT, int EPI, bool LNF = false, bool KEEP = true>
-__global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
+// TAIL (<T, 2, 0, 0, false, true> only: the backward pass behind eg_ffn_bwd_ln_proj): the launch goes on with norm-1's backward and
+// out_proj's backward-data product on the rows it has just completed -- steps 2-4 of ln_bwd_proj_kernel (lnproj.h) on q's operands.
+// Epilogue 2 leaves the rounded C rows in the resident tile xt (dead after the last product 1) as well as in C (when given); the
+// LayerNorm input rows come straight into registers in the half-wave layout, requested in front of epilogue 2.  LDS of the tail:
+//   xt [0, 40 KB)        dy1 rows (epilogue 2) -> dyo rows in place (step 2) -> A operand of step 3
+//   hb [0, 17 KB)        epilogue 2's four images; then [0, 16 KB) the gain / bias sums, [16 KB, 33 KB) step 4's four images
+struct FfnNoTail {};
+template <typename T, int GATE, int BOUT, int EPI, bool LNF = false, bool KEEP = true, bool TAIL = false>
+__global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::conditional_t<TAIL, LnProjArgs<T>, FfnNoTail> q) {
+  static_assert(!TAIL || (GATE == 2 && BOUT == 0 && EPI == 0 && !LNF && KEEP), "the norm-1 tail follows the backward form only");
   typedef typename H16<T>::frag frag;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const xt = smem;
@@ -306,6 +317,18 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
       eraw[i][1] = *(const u32x4*)(pe + 8);
     }
   }
+  // TAIL: the LayerNorm input rows of this half-wave (rows hw + 8 j, piece l) and their statistics travel under epilogue 2
+  const int tl = lane & 31, thw = tid >> 5;
+  u32x4 xr[TAIL ? LP_ROWS_PER_HW : 1];
+  float mean[TAIL ? LP_ROWS_PER_HW : 1], rstd[TAIL ? LP_ROWS_PER_HW : 1];
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int j = 0; j < LP_ROWS_PER_HW; ++j) {
+      const int m = min(m0 + thw + 8 * j, q.M - 1);    // (rows beyond M repeat row M - 1, as the tile load does; step 2 zeroes them)
+      xr[j] = *(const u32x4*)(q.x + (size_t)m * FD + tl * 8);
+    }
+    lp_stats(q.stats, q.M, m0, thw, mean, rstd);
+  }
   float vv[LNF ? 5 : 1][16];                       // LNF: the stored C values of this lane's rows, for the LayerNorm below
   if (LNF) {
 #pragma unroll
@@ -320,9 +343,37 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
     if (m0 + 16 * i >= p.M) break;                 // workgroup-uniform: tiles wholly beyond M
     float v[16];
     rt_image_get(timg, lane, v);
-    if (m < p.M)
+    if constexpr (TAIL) {
+      if (m < p.M) {
+        rt_row_epilogue<T, false, false>(v, bv, p.dc1, p.dc2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)FD + (uint32_t)n,
+                                         p.residual != nullptr, eraw[i][0], eraw[i][1], (T*)nullptr, vv[0]);
+        if (p.C) rt_store16(p.C + (size_t)m * (size_t)p.ldc + n, v);
+        const int r = 16 * i + er;                   // the same 16-bit values into the resident tile: step 2's dy rows
+        store8((T*)(xt + r * RT_ROWB + rt_piece(r, n >> 3)), v);
+        store8((T*)(xt + r * RT_ROWB + rt_piece(r, (n >> 3) + 1)), v + 8);
+      }
+    } else if (m < p.M)
       rt_row_epilogue<T, LNF, KEEP>(v, bv, p.dc1, p.dc2, seed_lo, seed_hi, (uint32_t)m * (uint32_t)FD + (uint32_t)n, p.residual != nullptr,
                                     eraw[i][0], eraw[i][1], KEEP ? p.C + (size_t)m * (size_t)p.ldc + n : nullptr, vv[LNF ? i : 0]);
+  }
+  if constexpr (TAIL) {
+    // gain, the out_proj fragments of the first two k-steps and the dropout seed; then steps 2-4 of ln_bwd_proj_kernel
+    const char* const wu = (const char*)(q.Wf + rt_frag_elem<4, 4>(0, wn, 0, 0));
+    frag wr[2][4];
+    float g[8], dg[8], db[8];
+    load8(q.gamma + tl * 8, g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { dg[e] = 0.f; db[e] = 0.f; }
+    const bool drop = (q.d1.thresh | q.d2.thresh) != 0;
+    uint32_t qs_lo = 0, qs_hi = 0;
+    if (drop) { qs_lo = q.st->seed_lo; qs_hi = q.st->seed_hi; }
+    lp_req_w<T>(wu, wl, 0, wr[0]);
+    lp_req_w<T>(wu, wl, 1, wr[1]);
+    __syncthreads();                               // xt holds the tile's dy1 rows; epilogue 2's images are free
+    lp_ln_rows<T, true>(q, xt, nullptr, xr, m0, thw, tl, g, mean, rstd, drop, qs_lo, qs_hi, dg, db);
+    __syncthreads();                               // xt = dyo complete
+    lp_sums(q.partial, (float*)hb, dg, db, tid, thw, tl);
+    lp_product<T>(q.dC, q.M, xt, wr, wu, wl, (float*)(hb + LP_SUMS_B + wn * RT_IMGB), m0, lane, wn);
   }
   if constexpr (LNF)
     eg_epilogue_layernorm256<T>(vv, (float*)(hb + 4 * RT_IMGB), wn, lane, min(FR, p.M - m0), (size_t)m0, p.ln_gamma, p.ln_beta,
@@ -330,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p) {
 }
 
 template <typename T>
-static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
+static FfnArgs<T> ffn_make_args(const eg_ffn_desc* d) {
   FfnArgs<T> p;
   p.A = (const T*)d->A; p.W1 = (const T*)d->W1; p.W2 = (const T*)d->W2; p.H = (T*)d->H; p.C = (T*)d->C;
   p.bits_in = (const unsigned long long*)d->gate_bits_in; p.bits_out = (unsigned long long*)d->gate_bits_out;
@@ -344,12 +395,19 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   p.dc2 = make_drop(d->drop_c2_p, d->drop_c2_site);
   p.gate_scale = d->gate_scale == 0.f ? 1.0f : d->gate_scale;
   p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.LN_OUT = (T*)d->ln_out; p.ln_stats = d->ln_stats;
+  return p;
+}
+
+template <typename T>
+static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
+  const FfnArgs<T> p = ffn_make_args<T>(d);
+  const FfnNoTail nt;
   const dim3 grid((d->M + FR - 1) / FR);
-#define FFN_LAUNCH(G_, B_, E_, L_) eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_>, F_LDS>(grid, dim3(256), s, p)
+#define FFN_LAUNCH(G_, B_, E_, L_) eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_>, F_LDS>(grid, dim3(256), s, p, nt)
   const int gsel = d->gate_bits_in ? 2 : d->gate ? 1 : 0;
   const bool bout = d->gate_bits_out != nullptr;
   const bool lnf = d->ln_out != nullptr;                                                                      // (forward form only, checked below)
-  if (!d->H) eg_launch_lds<ffn_chain_kernel<T, 0, 0, 3, true, false>, F_LDS>(grid, dim3(256), s, p);         // lean (forward form, LNF, no bits: checked below)
+  if (!d->H) eg_launch_lds<ffn_chain_kernel<T, 0, 0, 3, true, false>, F_LDS>(grid, dim3(256), s, p, nt);         // lean (forward form, LNF, no bits: checked below)
   else if (gsel == 0 && d->bias1 && p.relu) {                                                                 // the forward pass
     if (lnf) { if (bout) FFN_LAUNCH(0, 1, 3, true); else FFN_LAUNCH(0, 0, 3, true); }
     else { if (bout) FFN_LAUNCH(0, 1, 3, false); else FFN_LAUNCH(0, 0, 3, false); }
@@ -365,37 +423,69 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   return 0;
 }
 
+// the backward form with the norm-1 tail: one instantiation per dtype
+template <typename T>
+static int ffn_tail_launch(const eg_ffn_desc* f, const eg_ln_bwd_proj_desc* n, hipStream_t s) {
+  const FfnArgs<T> p = ffn_make_args<T>(f);
+  const LnProjArgs<T> q = lp_make_args<T>(n);
+  eg_launch_lds<ffn_chain_kernel<T, 2, 0, 0, false, true, true>, F_LDS>(dim3((f->M + FR - 1) / FR), dim3(256), s, p, q);
+  EG_LAUNCH_CHECK("ffn_bwd_ln_proj");
+  return 0;
+}
+
+// the descriptor's own checks, for eg_ffn_chain and (tail: H required, C optional) eg_ffn_bwd_ln_proj
+static int ffn_check_desc(const eg_ffn_desc* d, const char* who, bool tail) {
+  EG_CHECK(d && d->A && d->W1 && d->W2, "%s: null operand", who);
+  EG_CHECK(d->dtype == EG_BF16 || d->dtype == EG_F16, "%s: 16-bit compute dtypes only (got %d)", who, d->dtype);
+  const bool lean = !tail && !d->H && !d->C;
+  EG_CHECK(tail || lean || (d->H && d->C), "%s: H and C are both given (the keeping form) or both null (the lean form); got %s only", who,
+           d->H ? "H" : "C");
+  EG_CHECK(!lean || (d->bias1 && d->act1 == EG_ACT_RELU && !d->gate && !d->gate_bits_in),
+           "%s: the lean form (H and C null) serves the forward form only: bias1, ReLU, no gate, no gate_bits_in", who);
+  EG_CHECK(!lean || d->ln_out, "%s: the lean form (H and C null) needs ln_out, its only result", who);
+  EG_CHECK(!lean || !d->gate_bits_out, "%s: the lean form (H and C null) writes no gate_bits_out", who);
+  EG_CHECK(d->M > 0 && d->F > 0 && d->F % FC == 0, "%s: M=%d, F=%d (F must be a multiple of %d)", who, d->M, d->F, FC);
+  EG_CHECK(d->act1 == EG_ACT_NONE || d->act1 == EG_ACT_RELU, "%s: act1 %d", who, d->act1);
+  EG_CHECK(d->lda >= FD && d->lda % 8 == 0 && (lean || (d->ldh >= d->F && d->ldh % 8 == 0 && (!d->C || (d->ldc >= FD && d->ldc % 8 == 0)))),
+           "%s: row strides must be 16-B multiples covering the rows", who);
+  EG_CHECK(!d->gate || (d->ldg >= d->F && d->ldg % 4 == 0), "%s: gate stride", who);
+  EG_CHECK(!(d->gate_bits_out && (d->gate_bits_in || d->gate)), "%s: a launch either writes gate bits or applies a gate", who);
+  EG_CHECK(((uintptr_t)d->gate_bits_in | (uintptr_t)d->gate_bits_out) % 8 == 0, "%s: gate bit words must be 8-B aligned", who);
+  EG_CHECK(!d->residual || (d->ldr >= FD && d->ldr % 8 == 0), "%s: residual stride", who);
+  EG_CHECK((long long)d->M * d->F < (1ll << 32), "%s: M*F exceeds the 32-bit dropout index", who);
+  EG_CHECK(!d->ln_out || (d->ln_gamma && d->ln_beta && (lean || d->ldc == FD) &&!d->gate && !d->gate_bits_in && d->bias1 && d->act1 == EG_ACT_RELU &&
+                          (uintptr_t)d->ln_out % 16 == 0),
+           "%s: the fused LayerNorm serves the forward form (bias + ReLU, no gate) with contiguous C rows", who);
+  const float ps[3] = {d->drop_h_p, d->drop_c1_p, d->drop_c2_p};
+  for (float q : ps) EG_CHECK(q >= 0.f && q < 1.f, "%s: dropout p", who);
+  EG_CHECK((ps[0] == 0.f && ps[1] == 0.f && ps[2] == 0.f) || d->state, "%s: dropout needs a step state", who);
+  EG_CHECK(((uintptr_t)d->A | (uintptr_t)d->W1 | (uintptr_t)d->W2 | (uintptr_t)d->H | (uintptr_t)d->C | (uintptr_t)d->gate |
+            (uintptr_t)d->residual) % 16 == 0, "%s: operands must be 16-B aligned", who);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int eg_ffn_chain(const eg_ffn_desc* d, void* stream) {
-  EG_CHECK(d && d->A && d->W1 && d->W2, "eg_ffn_chain: null operand");
-  EG_CHECK(d->dtype == EG_BF16 || d->dtype == EG_F16, "eg_ffn_chain: 16-bit compute dtypes only (got %d)", d->dtype);
-  const bool lean = !d->H && !d->C;
-  EG_CHECK(lean || (d->H && d->C), "eg_ffn_chain: H and C are both given (the keeping form) or both null (the lean form); got %s only",
-           d->H ? "H" : "C");
-  EG_CHECK(!lean || (d->bias1 && d->act1 == EG_ACT_RELU && !d->gate && !d->gate_bits_in),
-           "eg_ffn_chain: the lean form (H and C null) serves the forward form only: bias1, ReLU, no gate, no gate_bits_in");
-  EG_CHECK(!lean || d->ln_out, "eg_ffn_chain: the lean form (H and C null) needs ln_out, its only result");
-  EG_CHECK(!lean || !d->gate_bits_out, "eg_ffn_chain: the lean form (H and C null) writes no gate_bits_out");
-  EG_CHECK(d->M > 0 && d->F > 0 && d->F % FC == 0, "eg_ffn_chain: M=%d, F=%d (F must be a multiple of %d)", d->M, d->F, FC);
-  EG_CHECK(d->act1 == EG_ACT_NONE || d->act1 == EG_ACT_RELU, "eg_ffn_chain: act1 %d", d->act1);
-  EG_CHECK(d->lda >= FD && d->lda % 8 == 0 && (lean || (d->ldc >= FD && d->ldh >= d->F && d->ldc % 8 == 0 && d->ldh % 8 == 0)),
-           "eg_ffn_chain: row strides must be 16-B multiples covering the rows");
-  EG_CHECK(!d->gate || (d->ldg >= d->F && d->ldg % 4 == 0), "eg_ffn_chain: gate stride");
-  EG_CHECK(!(d->gate_bits_out && (d->gate_bits_in || d->gate)), "eg_ffn_chain: a launch either writes gate bits or applies a gate");
-  EG_CHECK(((uintptr_t)d->gate_bits_in | (uintptr_t)d->gate_bits_out) % 8 == 0, "eg_ffn_chain: gate bit words must be 8-B aligned");
-  EG_CHECK(!d->residual || (d->ldr >= FD && d->ldr % 8 == 0), "eg_ffn_chain: residual stride");
-  EG_CHECK((long long)d->M * d->F < (1ll << 32), "eg_ffn_chain: M*F exceeds the 32-bit dropout index");
-  EG_CHECK(!d->ln_out || (d->ln_gamma && d->ln_beta && (lean || d->ldc == FD) &&!d->gate && !d->gate_bits_in && d->bias1 && d->act1 == EG_ACT_RELU &&
-                          (uintptr_t)d->ln_out % 16 == 0),
-           "eg_ffn_chain: the fused LayerNorm serves the forward form (bias + ReLU, no gate) with contiguous C rows");
-  const float ps[3] = {d->drop_h_p, d->drop_c1_p, d->drop_c2_p};
-  for (float q : ps) EG_CHECK(q >= 0.f && q < 1.f, "eg_ffn_chain: dropout p");
-  EG_CHECK((ps[0] == 0.f && ps[1] == 0.f && ps[2] == 0.f) || d->state, "eg_ffn_chain: dropout needs a step state");
-  EG_CHECK(((uintptr_t)d->A | (uintptr_t)d->W1 | (uintptr_t)d->W2 | (uintptr_t)d->H | (uintptr_t)d->C | (uintptr_t)d->gate |
-            (uintptr_t)d->residual) % 16 == 0, "eg_ffn_chain: operands must be 16-B aligned");
+  if (int rc = ffn_check_desc(d, "eg_ffn_chain", false)) return rc;
   hipStream_t s = (hipStream_t)stream;
   return eg_dispatch_16(d->dtype, [&](auto t) { return ffn_launch<typename decltype(t)::type>(d, s); });
+}
+
+extern "C" int eg_ffn_bwd_ln_proj(const eg_ffn_desc* f, const eg_ln_bwd_proj_desc* n, void* stream) {
+  static const char who[] = "eg_ffn_bwd_ln_proj";
+  EG_CHECK(f && n, "%s: null descriptor", who);
+  if (int rc = ffn_check_desc(f, who, true)) return rc;
+  if (int rc = lp_check_desc(n, who, false)) return rc;
+  EG_CHECK(f->gate_bits_in, "%s: f must be the backward form: gate_bits_in is not set", who);
+  EG_CHECK(!f->bias1 && f->act1 == EG_ACT_NONE && !f->gate && !f->gate_bits_out && !f->ln_out,
+           "%s: f must be the backward form: no bias1, act1, gate, gate_bits_out or ln_out", who);
+  EG_CHECK(f->H, "%s: f->H (the hidden gradient rows) must be given; only f->C may be NULL", who);
+  EG_CHECK(!n->dy || n->dy == f->C, "%s: n->dy must be NULL or f->C (the LayerNorm reads the rows the launch itself completes)", who);
+  EG_CHECK(n->M == f->M, "%s: n->M=%d differs from f->M=%d", who, n->M, f->M);
+  EG_CHECK(n->dtype == f->dtype, "%s: n->dtype=%d differs from f->dtype=%d", who, n->dtype, f->dtype);
+  hipStream_t s = (hipStream_t)stream;
+  return eg_dispatch_16(f->dtype, [&](auto t) { return ffn_tail_launch<typename decltype(t)::type>(f, n, s); });
 }
 
 extern "C" int64_t eg_ffn_gate_bits_bytes(int M, int F) {

@@ -822,8 +822,10 @@ class ForwardEngine(EngineBase):
         self._timed_end(probe)
 
     def ffn(self, A, W1f, W2f, H, Cout, M, F, *, bias1=0, bias2=0, act1=0, residual=0, gate=0, bits_out=0, bits_in=0,
-            drop_h=(0.0, 0), drop_c1=(0.0, 0), drop_c2=(0.0, 0), gate_scale=1.0, ln=None):
-        """eg_ffn_chain: H = epi1(A W1^T), C = epi2(H W2^T) in one launch (weights in fragment order)."""
+            drop_h=(0.0, 0), drop_c1=(0.0, 0), drop_c2=(0.0, 0), gate_scale=1.0, ln=None, ln_tail=None):
+        """eg_ffn_chain: H = epi1(A W1^T), C = epi2(H W2^T) in one launch (weights in fragment order).
+        ln_tail (an eg_ln_bwd_proj descriptor; the backward form only): eg_ffn_bwd_ln_proj, the same launch going on with that
+        LayerNorm backward and product on its own C rows, which are stored only if Cout is given."""
         d = self.cfg.d_model
         dsc = L.FfnDesc()
         dsc.A, dsc.W1, dsc.W2, dsc.H, dsc.C = A, W1f, W2f, H or None, Cout or None      # (both None: the forward-only form, ln's rows alone)
@@ -846,9 +848,16 @@ class ForwardEngine(EngineBase):
                 + (M * F // 8 if (bits_out or bits_in) else 0) + 4 * (F + d) + ((es * M * d + 8 * M + 8 * d) if ln is not None else 0)
             if not H:
                 nbytes = es * (2 * M * d + 2 * F * d) + 4 * (F + d) + 8 * d                           # A, norm2 rows | weights | biases, gain / bias
-            return 4.0 * M * F * d, float(nbytes), (M, F, d), 4
+            flops = 4.0 * M * F * d
+            if ln_tail is not None:         # dy1 itself moves only when it is stored; + x, dr, dyo, dC | W | statistics, gain, partials
+                nbytes += es * (M * d * (4 - (0 if Cout else 1)) + d * d) + 8 * M + 4 * d + 8 * d * self.ln_proj_blocks
+                flops += 2.0 * M * d * d
+            return flops, float(nbytes), (M, F, d), 4
         probe = self._timed(work)
-        call("eg_ffn_chain", C.byref(dsc), self.stream)
+        if ln_tail is not None:
+            call("eg_ffn_bwd_ln_proj", C.byref(dsc), C.byref(ln_tail), self.stream)
+        else:
+            call("eg_ffn_chain", C.byref(dsc), self.stream)
         self._timed_end(probe)
 
     def _probs_hook(self, drop_module, qkv, lse, kv_shift):
@@ -1076,6 +1085,10 @@ class Engine(ForwardEngine):
         # two launches (the gain / bias partials are grouped by tile instead of by LayerNorm block: equal to fp32 rounding)
         self.ln_proj = half and cfg.d_model == 256
         self.ln_proj_blocks = L.lib().eg_ln_bwd_proj_blocks(self.M) if self.ln_proj else 0
+        # the feed-forward backward launch goes on with norm1's backward and out_proj's backward-data product on the rows it has just
+        # completed (eg_ffn_bwd_ln_proj): same tiles and arithmetic as the two launches, bit for bit; dy1 never reaches memory.
+        # (fuse_ffn implies the gate-bit route: the forward launch of a training engine always leaves the bit image.)
+        self.ffn_ln_proj = bool(self.fuse_ffn and self.ln_proj)
         # True: optimizer_step takes the gradient norm and the clip coefficient in ONE launch (eg_grad_sqnorm_clip, same bits)
         # instead of eg_grad_sqnorm + eg_clip_coef.  Off by default: tests/test_gpu_accum.py counts the trainer's eg_grad_sqnorm calls
         self.fused_norm_clip = False
@@ -1237,16 +1250,20 @@ class Engine(ForwardEngine):
 
     def ln_bwd_proj(self, dy, x, stats, gname, wfrag, dx, dx_drop, dC, d1=(0.0, 0), slot=None):
         """eg_ln_bwd_proj: LayerNorm backward + the backward-data product dC = dx_drop W^T in one launch (csrc/lnproj.hip)"""
-        d = self.cfg.d_model
+        dsc = self._ln_bwd_proj_desc(dy, x, stats, gname, wfrag, dx, dx_drop, dC, d1, slot)
+        call("eg_ln_bwd_proj", C.byref(dsc), self.stream)
+        if slot is None:
+            self._reduce_ln_partials(dsc.partial, gname, self.ln_proj_blocks)
+
+    def _ln_bwd_proj_desc(self, dy, x, stats, gname, wfrag, dx, dx_drop, dC, d1, slot):
+        """the descriptor of eg_ln_bwd_proj; dy None: the rows come from the launch itself (eg_ffn_bwd_ln_proj)"""
         lp, cap = self._ln_partials(slot)
         dsc = L.LnBwdProjDesc()
         dsc.dy, dsc.x, dsc.stats, dsc.gamma, dsc.W_frag = ptr(dy), ptr(x), ptr(stats), self.fp.p_ptr(gname + ".weight"), ptr(wfrag)
         dsc.dx, dsc.dx_drop, dsc.dC, dsc.partial, dsc.state = ptr(dx), ptr(dx_drop), ptr(dC), lp, self.st_ptr
-        dsc.M, dsc.d_model, dsc.dtype, dsc.partial_capacity_blocks = self.M, d, self.dtype, cap
+        dsc.M, dsc.d_model, dsc.dtype, dsc.partial_capacity_blocks = self.M, self.cfg.d_model, self.dtype, cap
         dsc.drop1_p, dsc.drop1_site = d1
-        call("eg_ln_bwd_proj", C.byref(dsc), self.stream)
-        if slot is None:
-            self._reduce_ln_partials(lp, gname, self.ln_proj_blocks)
+        return dsc
 
     def ln_bwd(self, dy, x, stats, gname, dx, dx_drop=None, d1=(0.0, 0), d2=(0.0, 0), slot=None):
         """slot: index into the deferred gain/bias partial buffer (reduced by the grouped reduce at the end of backward)"""
@@ -1424,7 +1441,16 @@ class Engine(ForwardEngine):
                                   slot=s2)
         if not grouped:
             self.wgrad(ptr(dYf), ptr(a[f"hff{l}"]), 0, M, d, F, linear=[pre + "ffn.linear2"])
-        if self.fuse_ffn:
+        tail = self.ffn_ln_proj and self.fuse_ffn and self.ln_proj
+        if tail:
+            # the same launch, going on with norm1's backward and out_proj's backward-data product: dy1 stays on the chip
+            self.ffn(ptr(dYf), ptr(w[f"w2Tf{l}"]), ptr(w[f"w1Tf{l}"]), ptr(dh), 0, M, F, residual=ptr(dr),
+                     bits_in=ptr(a[f"gbits{l}"]), gate_scale=b.sc,
+                     ln_tail=self._ln_bwd_proj_desc(None, a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", w[f"oTf{l}"], g["dr"], dYo, g["dctx"],
+                                                    (p, sites["drop1"]) if b.has_drop else (0.0, 0), s1))
+            if s1 is None:
+                self._reduce_ln_partials(self._ln_partials(None)[0], pre + "ln1", self.ln_proj_blocks)
+        elif self.fuse_ffn:
             # dH = gate(dY W2) (stored: the weight gradients read it) and dy1 = dH W1 + dr in one launch; the gate is the
             # bit image the forward launch of this layer left
             self.ffn(ptr(dYf), ptr(w[f"w2Tf{l}"]), ptr(w[f"w1Tf{l}"]), ptr(dh), ptr(g["dy1"]), M, F, residual=ptr(dr),
@@ -1435,7 +1461,9 @@ class Engine(ForwardEngine):
             self.wgrad(ptr(dh), ptr(a[f"y1_{l}"]), 0, M, F, d, linear=[pre + "ffn.linear1"])
         if not self.fuse_ffn:
             self.gemm(ptr(dh), ptr(w[f"w1T{l}"]), ptr(g["dy1"]), M, d, F, residual=ptr(dr))
-        if self.ln_proj:        # norm1 backward + out_proj backward-data in one launch
+        if tail:
+            dr = g["dr"]
+        elif self.ln_proj:      # norm1 backward + out_proj backward-data in one launch
             self.ln_bwd_proj(g["dy1"], a[f"r1_{l}"], a[f"st1_{l}"], pre + "ln1", w[f"oTf{l}"], g["dr"], dYo, g["dctx"],
                              d1=(p, sites["drop1"]) if b.has_drop else (0.0, 0), slot=s1)
             dr = g["dr"]

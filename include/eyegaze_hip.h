@@ -304,6 +304,18 @@ int eg_ln_bwd_proj(const eg_ln_bwd_proj_desc* d, void* stream);
 int eg_ln_bwd_proj_blocks(int M);   /* rows of `partial` a launch over M rows writes */
 
 /* ---------------------------------------------------------------------------------------------
+ * eg_ffn_bwd_ln_proj — eg_ffn_chain in its backward form with eg_ln_bwd_proj as the launch's tail: both kernels walk the same
+ *   80-row tiles, so the rows C that the first completes (dy1, the gradient of the norm-1 output) stay on the chip as the second's dy.
+ *   f: the backward form only -- gate_bits_in and H set; no bias1, act1, gate, gate_bits_out or ln_out.  f->C may be NULL: then dy1
+ *      is not stored at all.
+ *   n: as for eg_ln_bwd_proj with n->dy NULL or equal to f->C; n->M == f->M, equal dtypes, d_model == 256, and `partial` with at
+ *      least eg_ln_bwd_proj_blocks(M) rows.
+ *   H, C (when given), dx, dx_drop, dC and every row of `partial` have the bits of eg_ffn_chain(f) followed by eg_ln_bwd_proj(n) on
+ *   that C: same tiles, arithmetic and summation order.  Every check of both descriptors is made before the launch.
+ * ------------------------------------------------------------------------------------------- */
+int eg_ffn_bwd_ln_proj(const eg_ffn_desc* f, const eg_ln_bwd_proj_desc* n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * eg_attn_block_fwd — the attention half of a post-LN encoder layer in ONE launch, a workgroup per WINDOW (S <= 80 rows):
  *   q|k|v = x Wqkv^T + b (A:203-205) -> softmax(q k^T / sqrt(32)), attention dropout, P v per head (A:206-212) ->
  *   r1 = x + dropout(ctx Wo^T + bo) (A:213, A:292-293's residual; the LayerNorm stays eg_layernorm_fwd).
