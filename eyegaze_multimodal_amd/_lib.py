@@ -208,6 +208,8 @@ SIGNATURES = {
     "eg_conv2d_wgrad_flat": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _P],
     "eg_conv2d_wgrad_flat_splits": [_L, _I],
     "eg_conv2d_flat": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P],
+    "eg_gradcam_scratch_elems": [_I, _I, _I, _I],                    # returns int64_t: gradcam_scratch_elems() below
+    "eg_gradcam_accumulate": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
 }
 _lib = None
 
@@ -255,6 +257,13 @@ def ibs_class_scratch_elems(B: int, nbands: int, nfeat: int, E: int, ncls: int) 
     l = lib()
     l.eg_ibs_class_accumulate_scratch_elems.restype = C.c_int64
     return int(l.eg_ibs_class_accumulate_scratch_elems(B, nbands, nfeat, E, ncls))
+
+
+def gradcam_scratch_elems(B: int, Cn: int, Hp: int, Wp: int) -> int:
+    """Floats of scratch eg_gradcam_accumulate needs for B samples of Cn channels (host only; -1: bad shape)"""
+    l = lib()
+    l.eg_gradcam_scratch_elems.restype = C.c_int64
+    return int(l.eg_gradcam_scratch_elems(B, Cn, Hp, Wp))
 
 
 def exported_symbols():

@@ -1045,7 +1045,8 @@ class ForwardEngine(EngineBase):
 #   fused_heads     the heads' backward as three launches (_fused_heads)
 #   fused_tokens    position / cls / conv-1 gradient rows from one pass over dseq
 #   dY1             ungrouped route: ONE buffer for the masked gradient that enters a branch
-BwdDecisions = namedtuple("BwdDecisions", "p train sc sc01 seg grouped pieced defer_norms gx has_drop fused_heads fused_tokens dY1")
+BwdDecisions = namedtuple("BwdDecisions", "p train sc sc01 seg grouped pieced defer_norms gx has_drop fused_heads fused_tokens dY1 until")
+BWD_UNTIL = (None, "spec_conv2")        # Engine.backward's `until`: the full backward, or the analysis cut
 
 
 class Engine(ForwardEngine):
@@ -1313,11 +1314,19 @@ class Engine(ForwardEngine):
     # Gradients land in the flat gradient buffer (overwritten, not accumulated).
     # ------------------------------------------------------------------------------------------
     def backward(self, gloss=None, gloss_ibs=None, glogits=None, gcls1=None, gcls2=None, gibs_logits=None,
-                 gibs_token=None, on_segment=None, prescaled: bool = False):
-        """Each stage takes the gradient rows and the free row buffer and returns that pair for the next stage"""
+                 gibs_token=None, on_segment=None, prescaled: bool = False, until: Optional[str] = None):
+        """Each stage takes the gradient rows and the free row buffer and returns that pair for the next stage.
+        until="spec_conv2" (the analysis backward of predict.gradcam_statistics): the same launches with the same arguments in the
+        same order, cut once g["sp_d2"] -- the gradient of the spectrogram CNN's second convolution -- is complete: the grouped
+        weight-gradient launch, the spectrogram projections' weight gradients and everything after eg_spec_avgpool_bwd are not
+        issued.  g["sp_d2"] has the full backward's bits; the flat gradient buffer is left partly written."""
+        if until not in BWD_UNTIL:
+            raise L.EgError(f"backward(until={until!r}): one of {BWD_UNTIL}")
+        if until is not None and not self.cfg.use_spectrogram:
+            raise L.EgError("backward(until=\"spec_conv2\") needs a model with spectrogram tokens")
         self._alloc_bwd()
         self.stream = self._cur_stream()
-        b = self._bwd_decisions(on_segment)
+        b = self._bwd_decisions(on_segment)._replace(until=until)
         gr = self._scale_incoming(prescaled, gloss=gloss, gloss_ibs=gloss_ibs, glogits=glogits, gcls1=gcls1, gcls2=gcls2,
                                   gibs_logits=gibs_logits, gibs_token=gibs_token)
         dz, free = self._heads_bwd(b, gr)
@@ -1326,8 +1335,11 @@ class Engine(ForwardEngine):
         dz, free = self._final_norm_bwd(b, dz, free)
         for l in reversed(range(self.cfg.num_layers)):
             dz, free = self._layer_bwd(b, l, dz, free)
-        self._wgrad_group_bwd(b)
-        self._front_end_bwd(b, dz)
+        if until is None:
+            self._wgrad_group_bwd(b)
+            self._front_end_bwd(b, dz)
+        else:       # of the front end's backward only the spectrogram branch, down to conv-2's output gradient
+            tokens.backward(self, dz, until=until)
 
     def _bwd_decisions(self, on_segment) -> BwdDecisions:
         p, p01, train = self.train_flags
@@ -1343,7 +1355,7 @@ class Engine(ForwardEngine):
             gx=self.cfg.use_cross_attention and grouped and self._wg_cross, has_drop=p > 0,
             fused_heads=self._fused_heads(backward=True),
             fused_tokens=bool(self.fused_tail) and self.dtype != EG_F32 and self.cfg.d_model % 64 == 0,
-            dY1=self.g["drm"] if p > 0 else self.g["dr"])
+            dY1=self.g["drm"] if p > 0 else self.g["dr"], until=None)
 
     def _scale_incoming(self, prescaled: bool, **grads):
         """every gradient entering the backward is multiplied by the device-resident loss scale (no host sync); the optimiser
@@ -1472,7 +1484,7 @@ class Engine(ForwardEngine):
         self._attn_stage_bwd(b, l, a[f"x{l}"], dr, dYo, 0, sites["attn"], free, dqkv, grouped, dctx_done=self.ln_proj)
         if not grouped:
             b.seg(f"layer{l}")
-        elif b.pieced and l == self._wg_plan["split_layer"]:
+        elif b.pieced and b.until is None and l == self._wg_plan["split_layer"]:
             # upper half of the encoder: its weight gradients are complete -> reduce them now, hand the buckets to the
             # all-reduce while the lower layers' backward-data chain keeps the compute stream busy
             self._wgrad_group_launch(self._wg_plan["pieces"][0], b.seg, b.gx)

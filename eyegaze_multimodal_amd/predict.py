@@ -7,11 +7,14 @@ per-sample diagonals reduced on the device from each batch's q|k|v rows (eg_atte
 predict_loader walks a data.ResidentWindows store instead (--resident: gather launch -> engine, no window visits the host), and
 predict_recording classifies one whole recording pair at any stride.  connectivity_statistics and
 frequency_sensitivity are eeg_metrics.py's class-mean connectivity matrices (:183-311) and band-masking sensitivity (:318-413)
-with the matrices consumed where eg_ibs_pairs leaves them.
+with the matrices consumed where eg_ibs_pairs leaves them.  gradcam_statistics is compute_gradcam_batch (:811-953):
+an eval forward of the training engine, the backward cut at the spectrogram CNN's second convolution and ONE eg_gradcam_accumulate
+per batch -- no activation or gradient of that layer visits the host; embedding_features is
+extract_features_for_embedding (:602-673) over the inference engine.
 
     python -m eyegaze_multimodal_amd.predict --config CONFIG.yaml --checkpoint best_model.pt --out FILE.npz [--resident]
                                              [--attention-stats [cross|LAYER]] [--connectivity-stats]
-                                             [--frequency-sensitivity]
+                                             [--frequency-sensitivity] [--gradcam [--gradcam-max-samples N]]
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from ._lib import EgError, attn_stats_scratch_elems, call, ptr
+from ._lib import EgError, attn_stats_scratch_elems, call, gradcam_scratch_elems, ptr
 
 
 class _PredictWalk:
@@ -271,6 +274,118 @@ def connectivity_statistics(model, eeg1: torch.Tensor, eeg2: torch.Tensor, label
     return out
 
 
+GRADCAM_TARGETS = ("predicted", "label")
+GRADCAM_SIZE = 64                                               # eeg_metrics.py:930: every map is resized to 64 x 64
+
+
+def _gradcam_batch(model, eng, x1, x2, y, target, cams, class_sum, class_count, scratch, ncls_names):
+    """One batch of gradcam_statistics on the training engine `eng`: eval forward, analysis backward from the one-hot of the chosen
+    logit, one eg_gradcam_accumulate.  cams: this batch's rows [B, 64, 64].  Returns the batch's logits (a copy)."""
+    ncls = model.cfg.num_classes
+    # the bookkeeping of every forward of the training engines: the forward counter moves, so the backward of an older autograd
+    # forward is refused ("newer forward") instead of reading this batch's activations
+    logits = model._run_forward(eng, x1, x2, None, train=False)["logits"]
+    idx = logits.argmax(dim=1) if target == "predicted" else y
+    one_hot = (idx.view(-1, 1) == torch.arange(ncls, device=logits.device).view(1, -1)).float()      # on the device, no host sync
+    eng.backward(glogits=one_hot, until="spec_conv2")           # fp16: scaled by the device-resident loss scale as any backward
+    sp, fp, pre = eng.sp, eng.fp, "spectrogram_generator.spec_conv.3."
+    call("eg_gradcam_accumulate", ptr(eng.a["sp_p1"]), ptr(eng.g["sp_d2"]), fp.p_ptr(pre + "weight"), fp.p_ptr(pre + "bias"),
+         ptr(eng.loss_scale_dev) if eng.scaler_on else 0, ptr(y), ptr(cams), ptr(class_sum), ptr(class_count), ptr(scratch),
+         scratch.numel(), eng.B, eng.C, sp["Hp"], sp["Wp"], ncls_names, eng.dtype, eng.stream)
+    return logits
+
+
+@torch.no_grad()
+def gradcam_statistics(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: torch.Tensor, batch_size: int = 256,
+                       max_samples: Optional[int] = 100, target: str = "predicted", class_names=None) -> Dict[str, Any]:
+    """compute_gradcam_batch (eeg_metrics.py:811-953) without the hooks: eval mode, score = the sum over the batch of each sample's
+    chosen logit -- target "predicted" (the reference's choice: the argmax) or "label" (the alternative its comment names) --,
+    Grad-CAM of spectrogram_generator.spec_conv[3] per image, the mean over the channels and the two streams, resized to 64 x 64,
+    bucketed by the TRUE label.  Windows, batches and the whole-batch rule of max_samples as attention_statistics; class buckets
+    as connectivity_statistics.  Returns
+      class_mean {class name: [64, 64] f32 numpy} for every name (zeros for a class that never occurred), class_count {name: int},
+      cams [n, 64, 64] f32 (device, one map per sample), count = n, logits [n, ncls] f32 and predictions [n] i64 (device).
+    A model without spectrogram tokens: {} (the reference prints an error and returns {}).
+    Every batch runs the TRAINING engine of its shape (the inference engine keeps no activations): an eval forward, the backward
+    cut once the gradient of that layer's output is complete (Engine.backward(until="spec_conv2")) and one eg_gradcam_accumulate;
+    cams, the class sums and counts stay on the device, the host syncs once, at the end.  No parameter, p.grad, optimiser state,
+    step state or loss-scaler state is written, but the flat gradient buffer's contents are unspecified afterwards: a call
+    between a native backward and its optimiser step loses that backward.  An autograd backward of a forward made before the
+    call is refused (the engine keeps one step's activations)."""
+    cfg = model.cfg
+    N, ncls = eeg1.shape[0], cfg.num_classes
+    if batch_size < 1 or N < 1 or labels is None or labels.shape[0] != N or (max_samples is not None and max_samples < 1):
+        raise ValueError(f"gradcam_statistics needs N >= 1 labelled windows, batch_size >= 1 and max_samples >= 1 or None "
+                         f"(got {N}, {batch_size}, {max_samples})")
+    if target not in GRADCAM_TARGETS:
+        raise ValueError(f"target must be one of {GRADCAM_TARGETS}, got {target!r}")
+    if not cfg.use_spectrogram:
+        return {}
+    names = CLASS_NAMES if class_names is None else list(class_names)
+    if not 1 <= len(names) <= 16:
+        raise ValueError(f"gradcam_statistics serves 1 to 16 class names, got {len(names)}")
+    n = N if max_samples is None else min(N, -(-max_samples // batch_size) * batch_size)
+    dev = next(model.parameters()).device
+    G = GRADCAM_SIZE
+    logits = torch.empty(n, ncls, device=dev)
+    pred = torch.empty(n, device=dev, dtype=torch.int32)
+    cams = torch.empty(n, G, G, device=dev)
+    class_sum = torch.zeros(len(names), G, G, device=dev)
+    class_count = torch.zeros(len(names), device=dev, dtype=torch.int32)
+    scratch = {}
+    for i in range(0, n, batch_size):
+        up = lambda t: t[i:min(i + batch_size, n)].to(dev, non_blocking=True)
+        x1, x2, y = model._check_windows(up(eeg1), up(eeg2), up(labels))
+        B = x1.shape[0]
+        eng = model.engine(B, x1.shape[2], dev)
+        if id(eng) not in scratch:
+            need = gradcam_scratch_elems(B, eng.C, eng.sp["Hp"], eng.sp["Wp"])
+            if need < 0:
+                raise EgError(f"eg_gradcam_accumulate does not cover B={B} C={eng.C} Hp={eng.sp['Hp']} Wp={eng.sp['Wp']}")
+            scratch[id(eng)] = torch.empty(need, device=dev)
+        lg = _gradcam_batch(model, eng, x1, x2, y, target, cams[i:i + B], class_sum, class_count, scratch[id(eng)], len(names))
+        logits[i:i + B].copy_(lg)
+        call("eg_eval_accumulate", ptr(lg), 0, 0, pred.data_ptr() + 4 * i, 0, 0, B, ncls, eng.stream)
+    counts = class_count.cpu().numpy()                           # the one host sync
+    mean = (class_sum / class_count.clamp(min=1).float().view(-1, 1, 1)).cpu().numpy()
+    return {"class_mean": {name: mean[c] for c, name in enumerate(names)},
+            "class_count": {name: int(counts[c]) for c, name in enumerate(names)}, "cams": cams, "count": n, "logits": logits,
+            "predictions": pred.long()}
+
+
+@torch.no_grad()
+def embedding_features(model, eeg1: torch.Tensor, eeg2: torch.Tensor, labels: torch.Tensor, batch_size: int = 256) -> Dict[str, Any]:
+    """extract_features_for_embedding (eeg_metrics.py:602-673) over the inference engine: windows and batches as predict_windows,
+    every batch's tokens gathered on the device, one copy to the host at the end.  Returns numpy arrays under the reference's keys:
+      cls1, cls2 [N, d] (and ibs_token [N, d] when the model has synchrony tokens) -- the bits of model.predict --,
+      z_fuse [N, 3 d] = cat(cls1, cls2, |cls1 - cls2|) (the reference's proxy of the fused features),
+      y_true [N] (the labels as given) and y_pred [N] i64 (the argmax of model.predict's logits)."""
+    cfg = model.cfg
+    N, ncls, d = eeg1.shape[0], cfg.num_classes, cfg.d_model
+    if batch_size < 1 or N < 1 or labels is None or labels.shape[0] != N:
+        raise ValueError(f"embedding_features needs N >= 1 labelled windows and batch_size >= 1 (got {N}, {batch_size})")
+    dev = next(model.parameters()).device
+    keys = {"cls1": "cls1", "cls2": "cls2", **({"ibs_token": "ibs_pool_f"} if cfg.use_ibs else {})}
+    feats = {k: torch.empty(N, d, device=dev) for k in keys}
+    pred = torch.empty(N, device=dev, dtype=torch.int32)
+    packed = set()
+    for i in range(0, N, batch_size):
+        up = lambda t: t[i:i + batch_size].to(dev, non_blocking=True)
+        x1, x2, _ = model._check_windows(up(eeg1), up(eeg2), None)
+        B = x1.shape[0]
+        eng = model.inference_engine(B, x1.shape[2], dev)
+        eng.forward(x1, x2, None, pack=id(eng) not in packed)
+        packed.add(id(eng))
+        for k, src in keys.items():
+            feats[k][i:i + B].copy_(eng.a[src])
+        call("eg_eval_accumulate", ptr(eng.a["logits"]), 0, 0, pred.data_ptr() + 4 * i, 0, 0, B, ncls, eng.stream)
+    z = torch.cat([feats["cls1"], feats["cls2"], (feats["cls1"] - feats["cls2"]).abs()], dim=-1)
+    out = {"z_fuse": z.cpu().numpy(), **{k: v.cpu().numpy() for k, v in feats.items()}}
+    out["y_true"] = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    out["y_pred"] = pred.cpu().numpy().astype(np.int64)
+    return out
+
+
 def band_metrics_from_confusion(cm) -> Dict[str, float]:
     """{"accuracy", "f1"} of compute_frequency_sensitivity (eeg_metrics.py:403-411) from a confusion matrix cm[true][predicted]:
     accuracy_score and the macro F1 of precision_recall_fscore_support(average="macro", zero_division=0), which averages over
@@ -336,13 +451,14 @@ def main(args):
     ebs, pre = t["per_device_eval_batch_size"], d.get("enable_preprocessing", False)
     # (callers that build `args` themselves, from before the two flags existed, leave them out)
     conn_stats, band_masks = getattr(args, "connectivity_stats", False), getattr(args, "frequency_sensitivity", False)
+    gradcam = getattr(args, "gradcam", False)
     if args.resident or d.get("resident", False):
         # the store is walked directly: gather launch -> inference engine, batch by batch; no window visits the host
         stores = TA.prepare_store(config, Path(t["output_dir"]) / "recording_store")
         ld = ResidentWindows(stores[args.split], ebs, device, preprocessing=pre)
         out = predict_loader(model, ld)
         y = out["labels"].cpu()
-        if args.attention_stats is not None or conn_stats or band_masks:
+        if args.attention_stats is not None or conn_stats or band_masks or gradcam:
             x1, x2 = (torch.cat(p) for p in zip(*((b["eeg1"], b["eeg2"]) for b in ld)))     # stays on the device
     else:
         shards = TA.prepare_shards(config, Path(t["output_dir"]) / "window_shards")
@@ -370,6 +486,11 @@ def main(args):
         for k, v in st["sensitivity"].items():
             extra[f"band_{k}_accuracy"], extra[f"band_{k}_f1"] = v["accuracy"], v["f1"]
         extra["band_confusion"] = st["confusion"]
+    if gradcam:
+        st = gradcam_statistics(model, x1, x2, y, batch_size=ebs, max_samples=getattr(args, "gradcam_max_samples", 100))
+        if st:
+            extra.update({f"gradcam_class_{k}_mean": v for k, v in st["class_mean"].items()})
+            extra["gradcam_class_count"] = np.array(list(st["class_count"].values()), dtype=np.int64)
     np.savez(args.out, logits=out["logits"].cpu().numpy(), predictions=out["predictions"].cpu().numpy(), labels=y.numpy(),
              confusion=out["confusion"], loss=out["loss"], **{k.replace("/", "_"): v for k, v in out["metrics"].items()}, **extra)
     print(" ".join(f"{k}: {v:.4f}" for k, v in {"eval/loss": out["loss"], **out["metrics"]}.items()))
@@ -394,4 +515,8 @@ if __name__ == "__main__":
     ap.add_argument("--frequency-sensitivity", action="store_true",
                     help="also classify with each frequency band of the connectivity matrices masked, in one walk: "
                          "band_<name>_accuracy, band_<name>_f1 and band_confusion in the output file")
+    ap.add_argument("--gradcam", action="store_true",
+                    help="also compute the class-mean Grad-CAM maps of the spectrogram CNN on the device: gradcam_class_<name>_mean "
+                         "[64, 64] and gradcam_class_count in the output file")
+    ap.add_argument("--gradcam-max-samples", type=int, default=100, help="the reference's max_samples (whole batches until reached)")
     main(ap.parse_args())

@@ -268,15 +268,21 @@ def spec_cnn_alloc_bwd(eng):
     g["sp_part"] = eng._t(sp["nimg"], 320, dtype=torch.float32)
 
 
-def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01):
-    """backward of spec_cnn_forward from the gradient rows dy (addressed by dmap) of its output"""
+def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01, until=None):
+    """backward of spec_cnn_forward from the gradient rows dy (addressed by dmap) of its output.  until="spec_conv2"
+    (Engine.backward): the backward-data launches down to g["sp_d2"], unchanged, and nothing else."""
     a, w, g, fp, dt, st, sp, d, es = eng.a, eng.w, eng.g, eng.fp, eng.dtype, eng.stream, eng.sp, eng.cfg.d_model, eng.es
     F, nfr, Hp, Wp, nimg, rows = sp["F"], sp["nfr"], sp["Hp"], sp["Wp"], sp["nimg"], sp["rows"]
-    eng.wgrad(dy_ptr, ptr(a["sp_hp0"]), 0, nimg, d, 2 * d, y=dmap, linear=[pre + "proj.3"])
+    cut = until is not None
+    if not cut:
+        eng.wgrad(dy_ptr, ptr(a["sp_hp0"]), 0, nimg, d, 2 * d, y=dmap, linear=[pre + "proj.3"])
     eng.gemm(dy_ptr, ptr(w["spp3T"]), ptr(g["sp_dhp0"]), nimg, 2 * d, d, a=dmap, gate=ptr(a["sp_hp0"]), gate_scale=sc01)
-    eng.wgrad(ptr(g["sp_dhp0"]), ptr(a["sp_pooled"]), 0, nimg, 2 * d, 1024, linear=[pre + "proj.0"])
+    if not cut:
+        eng.wgrad(ptr(g["sp_dhp0"]), ptr(a["sp_pooled"]), 0, nimg, 2 * d, 1024, linear=[pre + "proj.0"])
     eng.gemm(ptr(g["sp_dhp0"]), ptr(w["spp0T"]), ptr(g["sp_dpooled"]), nimg, 1024, 2 * d)
     call("eg_spec_avgpool_bwd", ptr(a["sp_out2"]), ptr(g["sp_dpooled"]), ptr(g["sp_d2"]), nimg, Hp, Wp, dt, st)
+    if cut:
+        return
     row32, row64 = (Wp + 4) * 32, (Wp + 4) * 64
     if _conv2_flat(eng):
         # 16-bit operands: the flat correlation (csrc/spec.hip) reads every activation / gradient byte once; the im2col product below
@@ -305,7 +311,9 @@ def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01):
 
 
 # ------------------------------------------------------------------------------------------------
-def backward(eng, dseq):
+def backward(eng, dseq, until=None):
+    """until="spec_conv2" (Engine.backward's analysis cut): the spectrogram branch alone, down to g["sp_d2"]; the synchrony
+    tokens' backward is not issued (the spectrogram rows do not depend on it)"""
     from .engine import SITE_IBSTOK
     cfg = eng.cfg
     if not (cfg.use_spectrogram or cfg.use_ibs):
@@ -314,7 +322,8 @@ def backward(eng, dseq):
     p, p01, train = eng.train_flags
     sc01 = 1.0 / (1.0 - p01) if p01 > 0 else 1.0
     n_ibs = eng.n_ibs
-    if cfg.use_ibs and cfg.use_robust_ibs:
+    ibs = cfg.use_ibs and until is None
+    if ibs and cfg.use_robust_ibs:
         pre, ntok, E = "ibs_tokenizer.", cfg.num_ibs_tokens, Cn * Cn
         M = B * ntok
         # tokens are shared by both streams: their gradient is the sum of the two sequences' rows
@@ -330,7 +339,7 @@ def backward(eng, dseq):
             call("eg_affine_grad", ptr(g["ib_dxn"]), ptr(a["ib_xhat"]), ptr(g["ib_affpart"]), nsp, M, E, dt, st)
             call("eg_reduce_partials", ptr(g["ib_affpart"]), fp.g_ptr(pre + "instance_norm.weight"), E, nsp, 2 * E, 0, st)
             call("eg_reduce_partials", ptr(g["ib_affpart"]) + 4 * E, fp.g_ptr(pre + "instance_norm.bias"), E, nsp, 2 * E, 0, st)
-    elif cfg.use_ibs:
+    elif ibs:
         pre = "ibs_generator.proj."
         call("eg_rows_gather_gate", ptr(dseq), 0, ptr(g["ig_dtok"]), rowmap(d), B, S, d, 1, 1, B, 1.0, dt, st)
         eng.wgrad(ptr(g["ig_dtok"]), ptr(a["ig_h"]), 0, B, d, 2 * d, linear=[pre + "3"])
@@ -339,7 +348,7 @@ def backward(eng, dseq):
                   conv=(28, 1, 28))
     if cfg.use_spectrogram:
         off = (1 + n_ibs) * d * es
-        spec_cnn_backward(eng, "spectrogram_generator.", ptr(dseq) + off, rowmap(d, S * d, Cn), sc01)
+        spec_cnn_backward(eng, "spectrogram_generator.", ptr(dseq) + off, rowmap(d, S * d, Cn), sc01, until)
 
 
 def fire_spec_backward_hooks(model, eng):

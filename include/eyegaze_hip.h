@@ -702,6 +702,24 @@ int eg_conv2d_wgrad_flat_splits(long long Q, int want);
  * for all Q = nimg*(Hp+2)*rowpx pixel slots; `in` must hold in_rows >= Q + 2*rowpx + 2 readable pixel rows; `splits` = workgroups wanted. */
 int eg_conv2d_flat(const void* in, const void* W, const float* bias, void* out, long long Q, long long in_rows, int rowpx, int Wp,
                    int cin, int nout, int act, int splits, int dtype, void* stream);
+/* Grad-CAM of Conv2d(32,64,3,p1) (eeg_metrics.py:775-793, 897-937) from p1 [2*B*C][Hp+2][Wp+4][32] and
+ * d2 [2*B*C][Hp+2][Wp+4][64] (the padded channel-last layouts of eg_spec_conv1_fwd / eg_spec_avgpool_bwd, compute dtype; images
+ * [0, B*C) are stream 1, the rest stream 2), w2 [64][32][3][3] and b2 [64] (fp32, torch layout), labels [B] int64:
+ *   wgt[n][c] = mean over the Hp x Wp interior of d2[n][..][c] (/ *grad_scale when grad_scale is not NULL: one device float)
+ *   cam_n     = relu(sum_c wgt[n][c] * (b2[c] + conv3x3(p1[n], w2[c])))  -- as ONE convolution with the filter sum_c wgt[n][c] w2[c]
+ *   cam_b     = (mean over C of stream 1's cam_n + mean over C of stream 2's) / 2, resized to 64 x 64 as
+ *               F.interpolate(mode="bilinear", align_corners=False) does
+ *   cams[b] = cam_b                                  [B, 64, 64] fp32, written
+ *   class_sum[labels[b]] += cam_b, class_count[labels[b]] += 1      [ncls, 64, 64] fp32 / [ncls] int32, read-modify-written (zero
+ *               them once, issue every batch's call on one stream); a label outside [0, ncls) counts in no class, its cams row
+ *               is still written; 1 <= ncls <= 16.
+ * Hp, Wp: positive multiples of 4, Hp * Wp <= 4096.  scratch: at least eg_gradcam_scratch_elems(...) floats (the channel means of
+ * both streams, [2][B][Hp][Wp]), contents irrelevant on entry (-1: bad shape).  Two launches; samples are added in ascending
+ * order: deterministic, no float atomics. */
+int64_t eg_gradcam_scratch_elems(int B, int C, int Hp, int Wp);   /* host only, no device needed */
+int eg_gradcam_accumulate(const void* p1, const void* d2, const float* w2, const float* b2, const float* grad_scale,
+                          const int64_t* labels, float* cams, float* class_sum, int32_t* class_count, float* scratch,
+                          int64_t scratch_elems, int B, int C, int Hp, int Wp, int ncls, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
