@@ -83,6 +83,11 @@ class WindowGatherDesc(C.Structure):
                 ("n_pairs", C.c_int32), ("n_windows", C.c_int32), ("C", C.c_int32), ("T", C.c_int32)]
 
 
+class RecordingRowsDesc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("row_off", C.c_void_p), ("row_len", C.c_void_p), ("ws_off", C.c_void_p),
+                ("n_rows", C.c_int32), ("C", C.c_int32), ("max_len", C.c_int32), ("_pad", C.c_int32)]
+
+
 class PackEntry(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("rows", C.c_int32), ("cols", C.c_int32), ("ldd", C.c_int32),
                 ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32)]
@@ -149,6 +154,10 @@ SIGNATURES = {
     "eg_attention_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
     "eg_window_normalize": [_P, _P, _P, _I, _I, _I, _I, _P],
     "eg_window_gather": [C.POINTER(WindowGatherDesc), _P, _I, _I, _I, _P, _P, _P, _I, _P],
+    "eg_window_cut": [C.POINTER(WindowGatherDesc), _P, _I, _I, _I, _P, _P, _P, _P],
+    "eg_recording_filtfilt": [C.POINTER(RecordingRowsDesc), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I,
+                              _P, _L, _L, _P],
+    "eg_recording_car_zscore": [C.POINTER(RecordingRowsDesc), _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],

@@ -564,6 +564,10 @@ template <class Rows>
 __device__ __forceinline__ void window_normalize_rows(const Rows in, float* __restrict__ y, int C, int T, int mode, float* car,
                                                       double* red) {
   const long long CT = (long long)C * T;
+  if (mode == 2) {            // eg_window_cut: the window as stored
+    for (auto p = in.begin(); p.e < CT; in.next(p)) y[p.e] = in.at(p);
+    return;
+  }
   if (mode == 0) {
     double s = 0.0;
     for (auto p = in.begin(); p.e < CT; in.next(p)) s += (double)in.at(p);
@@ -630,6 +634,15 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const eg_window_gath
 
 }  // namespace
 
+// mode 0 / 1: eg_window_gather's; 2: eg_window_cut's copy (no entry point passes a mode it has not checked)
+static int window_gather_launch(const eg_window_gather_desc* d, const int32_t* order, int first, int n, float* eeg1, float* eeg2,
+                                int64_t* labels, int mode, void* stream) {
+  hipLaunchKernelGGL(window_gather_kernel, dim3(2 * n), dim3(256), mode == 1 ? (size_t)d->T * 4 : 0, (hipStream_t)stream, *d, order,
+                     first, eeg1, eeg2, labels, mode);
+  EG_LAUNCH_CHECK("window_gather");
+  return 0;
+}
+
 extern "C" int eg_window_normalize(const float* raw, float* eeg1, float* eeg2, int N, int C, int T, int mode, void* stream) {
   EG_CHECK(raw && eeg1 && eeg2, "eg_window_normalize: null pointer");
   EG_CHECK(N > 0 && C > 0 && T > 0, "eg_window_normalize: bad shape N=%d C=%d T=%d", N, C, T);
@@ -652,10 +665,20 @@ extern "C" int eg_window_gather(const eg_window_gather_desc* d, const int32_t* o
   EG_CHECK(first >= 0 && (long long)first + n <= (long long)order_len, "eg_window_gather: windows [%d, %d + %d) outside the order of %d",
            first, first, n, order_len);
   EG_CHECK(!labels || d->win_label, "eg_window_gather: labels requested but the descriptor has no win_label");
-  hipLaunchKernelGGL(window_gather_kernel, dim3(2 * n), dim3(256), mode ? (size_t)d->T * 4 : 0, (hipStream_t)stream, *d, order, first,
-                     eeg1, eeg2, labels, mode);
-  EG_LAUNCH_CHECK("window_gather");
-  return 0;
+  return window_gather_launch(d, order, first, n, eeg1, eeg2, labels, mode, stream);
+}
+
+extern "C" int eg_window_cut(const eg_window_gather_desc* d, const int32_t* order, int order_len, int first, int n, float* eeg1,
+                             float* eeg2, int64_t* labels, void* stream) {
+  EG_CHECK(d && d->data && d->pair_off && d->pair_len && d->win_pair && d->win_start && order && eeg1 && eeg2,
+           "eg_window_cut: null pointer");
+  EG_CHECK(n > 0 && d->C > 0 && d->T > 0, "eg_window_cut: bad shape n=%d C=%d T=%d", n, d->C, d->T);
+  EG_CHECK(d->n_pairs > 0 && d->n_windows > 0, "eg_window_cut: empty tables (n_pairs=%d n_windows=%d)", d->n_pairs, d->n_windows);
+  EG_CHECK(d->T <= 16384, "eg_window_cut: T=%d exceeds the 16384-sample staging row", d->T);
+  EG_CHECK(first >= 0 && (long long)first + n <= (long long)order_len, "eg_window_cut: windows [%d, %d + %d) outside the order of %d",
+           first, first, n, order_len);
+  EG_CHECK(!labels || d->win_label, "eg_window_cut: labels requested but the descriptor has no win_label");
+  return window_gather_launch(d, order, first, n, eeg1, eeg2, labels, 2 /* internal: as stored */, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -248,12 +248,122 @@ class WindowShards:
 # float offset of one flat `store.npy` -- plus a window table (pair, start).  ResidentWindows uploads store and tables once and
 # cuts + normalises every batch on the device with one `eg_window_gather` launch: nothing of a batch crosses the host.
 # ------------------------------------------------------------------------------------------------------
+PREPROCESS_ORDER = 4            # the reference's Butterworth order (preprocess_eeg_windows.py:101)
+PREPROCESS_KEYS = ("sampling_rate", "filter_low", "filter_high")
+
+
+def recording_preprocessing_args(mapping) -> Dict:
+    """{sampling_rate, filter_low, filter_high} of a `recording_preprocessing` mapping as floats; ValueError names a missing key"""
+    missing = [k for k in PREPROCESS_KEYS if not hasattr(mapping, "keys") or k not in mapping]
+    if missing:
+        raise ValueError(f"recording_preprocessing needs {list(PREPROCESS_KEYS)}; missing {missing}")
+    return {k: float(mapping[k]) for k in PREPROCESS_KEYS}
+
+
+def recording_row_tables(lengths: Sequence[int], C: int, pad: int):
+    """Recordings of `lengths` samples, each [C][length] f32, back to back -> (row_off i64, row_len i32, ws_off i64, floats,
+    workspace doubles): eg_recording_filtfilt's tables, rows in storage order, row r's extended forward output at ws_off[r]."""
+    ln = np.repeat(np.asarray(lengths, dtype=np.int64), C)
+    row_off = np.concatenate([[0], np.cumsum(ln)])
+    ws_off = np.concatenate([[0], np.cumsum(ln + 2 * pad)])
+    return row_off[:-1].copy(), ln.astype(np.int32), ws_off[:-1].copy(), int(row_off[-1]), int(ws_off[-1])
+
+
+def validate_recording_rows(row_off, row_len, C: int, pad: int, data_floats: int) -> None:
+    """The only bounds check the recording kernels get (they trust their tables): every row inside the `data_floats` floats, rows
+    in ascending order without overlap, every row longer than the filter's padding (where scipy raises the reference swallows the
+    exception and goes on with the unfiltered signal; here it is a ValueError), one length inside each group of C rows."""
+    off, ln = np.asarray(row_off, dtype=np.int64), np.asarray(row_len, dtype=np.int64)
+    if C < 1 or len(off) < 1 or len(off) != len(ln) or len(off) % C:
+        raise ValueError(f"recording rows: {len(off)} offsets, {len(ln)} lengths, C={C}")
+    if ln.min() <= pad:
+        r = int(np.argmin(ln))
+        raise ValueError(f"recording rows: row {r} has {ln[r]} samples, the zero-phase filter needs more than its padding of {pad}")
+    if (ln + 2 * pad).max() >= 2 ** 31:
+        raise ValueError("recording rows: a row's padded length does not fit int32")
+    end = off + ln
+    if off[0] < 0 or (end > data_floats).any():
+        r = int(np.argmax((end > data_floats) | (off < 0)))
+        raise ValueError(f"recording rows: row {r} covers floats [{off[r]}, {end[r]}) of {data_floats}")
+    if (off[1:] < end[:-1]).any():
+        r = int(np.argmax(off[1:] < end[:-1]))
+        raise ValueError(f"recording rows: row {r + 1} at float {off[r + 1]} overlaps row {r}, which ends at {end[r]}")
+    g = ln.reshape(-1, C)
+    if (g != g[:, :1]).any():
+        raise ValueError(f"recording rows: group {int(np.argmax((g != g[:, :1]).any(axis=1)))} holds rows of different lengths")
+
+
+def preprocess_recordings(recs, sampling_rate: float, filter_low: float, filter_high: float, order: int = PREPROCESS_ORDER,
+                          device="cuda") -> List[torch.Tensor]:
+    """The reference's recording-level preprocessing (preprocess_eeg, preprocess_eeg_windows.py:145-172) on the device: recs is a
+    list of (C, L) arrays or tensors (one C, any lengths); returns f32 device tensors of the same shapes, views of one buffer --
+    zero-phase Butterworth band-pass [filter_low, filter_high] Hz (filters.butter_bandpass, eg_recording_filtfilt), common-average
+    reference over the C channels given, per-channel z-score over the whole recording (eg_recording_car_zscore).  One upload, two
+    entry-point calls on the current stream, no host sync of its own.  ValueError: a bad band, a recording not longer than the
+    filter's padding (3 * (2 * order + 1) samples), recordings of different channel counts."""
+    import ctypes
+    from . import _lib as L
+    from .filters import butter_bandpass, lfilter_zi
+    b, a = butter_bandpass(order, filter_low, filter_high, sampling_rate)
+    zi = lfilter_zi(b, a)
+    ncoef, pad = len(b), 3 * len(b)
+    ts = [r.detach().to(torch.float32) if torch.is_tensor(r) else torch.from_numpy(np.ascontiguousarray(r, dtype=np.float32)) for r in recs]
+    if not ts or any(t.dim() != 2 for t in ts) or len({int(t.shape[0]) for t in ts}) != 1:
+        raise ValueError(f"preprocess_recordings needs (C, L) recordings of one channel count, got {[tuple(t.shape) for t in ts]}")
+    C, lengths = int(ts[0].shape[0]), [int(t.shape[1]) for t in ts]
+    row_off, row_len, ws_off, floats, ws_need = recording_row_tables(lengths, C, pad)
+    validate_recording_rows(row_off, row_len, C, pad, floats)
+    L.lib()
+    dev = torch.device(device)
+    data = torch.cat([t.reshape(-1) for t in ts]).to(dev)              # the one upload (host recordings); a fresh buffer either way
+    tabs = [torch.from_numpy(x).to(dev) for x in (row_off, row_len, ws_off)]
+    ws = torch.empty(ws_need, dtype=torch.float64, device=dev)
+    desc = L.RecordingRowsDesc(L.ptr(data), L.ptr(tabs[0]), L.ptr(tabs[1]), L.ptr(tabs[2]), len(row_len), C, max(lengths), 0)
+    dbl = lambda v: (ctypes.c_double * len(v))(*[float(x) for x in v])
+    stream = torch.cuda.current_stream(dev).cuda_stream             # (tables and workspace are allocated and freed on this stream)
+    L.call("eg_recording_filtfilt", ctypes.byref(desc), dbl(b), dbl(a), dbl(zi), ncoef, L.ptr(ws), ws_need, int(ws.numel()), stream)
+    L.call("eg_recording_car_zscore", ctypes.byref(desc), stream)
+    starts = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64) * C)])
+    return [data[int(starts[i]):int(starts[i + 1])].view(C, lengths[i]) for i in range(len(ts))]
+
+
+PREPROCESS_BATCH_BYTES = 256 << 20      # recording bytes per device batch of the store builder (the fp64 workspace is twice that)
+
+
+def _preprocessed_pairs(pairs, prep: Dict, device):
+    """kept_pairs' tuples with a, b replaced by their preprocessed WHOLE recordings (host arrays), in batches of bounded bytes"""
+    batch, nbytes = [], 0
+
+    def flush():
+        out = preprocess_recordings([r for _, _, a, b, _ in batch for r in (a, b)], device=device, **prep)
+        host = [t.cpu().numpy() for t in out]
+        for j, (idx, item, _, _, nwin) in enumerate(batch):
+            yield idx, item, host[2 * j], host[2 * j + 1], nwin
+        batch.clear()
+
+    for tup in pairs:
+        batch.append(tup)
+        nbytes += 4 * (tup[2].size + tup[3].size)
+        if nbytes >= PREPROCESS_BATCH_BYTES:
+            yield from flush()
+            nbytes = 0
+    if batch:
+        yield from flush()
+
+
 def build_recording_store(items: Sequence[Dict], eeg_base_path, label2id: Dict[str, int], out_dir, window_size: int = 1024,
-                          stride: int = 256, recordings: Optional[Dict[str, np.ndarray]] = None) -> Dict:
+                          stride: int = 256, recordings: Optional[Dict[str, np.ndarray]] = None, recording_preprocessing=None,
+                          device="cuda") -> Dict:
     """`build_window_shards`' arguments, skipping rules and window order (kept_pairs), written as a recording store:
       store.npy   flat f32; pair p at float offset off[p] as [2][C][len[p]], len[p] = (nwin - 1) * stride + window_size
       labels.npy  i64 per window, as the shards'
-      index.json  the shard index's keys (without `shards`) + `pairs` [{offset, length, dataset_idx}] + `window_pair` [count]"""
+      index.json  the shard index's keys (without `shards`) + `pairs` [{offset, length, dataset_idx}] + `window_pair` [count]
+    recording_preprocessing = {sampling_rate, filter_low, filter_high}: each kept pair's two recordings go WHOLE through
+    preprocess_recordings on `device` -- before they are cut to the common length, the reference's order
+    (preprocess_eeg_windows.py:239-255) -- in batches of bounded device bytes; the layout is the same and index.json gains
+    `preprocessed` {the three values, order}.  The common-average reference runs over the channels the store keeps (the pair's
+    minimum), not over load_eeg_csv's zero-padded 32.  None (the default) writes what this function always wrote."""
+    prep = recording_preprocessing_args(recording_preprocessing) if recording_preprocessing is not None else None
     out = Path(out_dir)
     out.mkdir(parents=True, exist_ok=True)
     meta: List[Dict] = []
@@ -261,9 +371,12 @@ def build_recording_store(items: Sequence[Dict], eeg_base_path, label2id: Dict[s
     pairs: List[Dict] = []
     window_pair: List[int] = []
     C_all, total = None, 0
+    walk = kept_pairs(items, eeg_base_path, window_size, stride, recordings)
+    if prep is not None:
+        walk = _preprocessed_pairs(walk, prep, device)
     tmp = out / "store.f32.partial"                     # the total is known only after the walk: raw first, .npy after
     with open(tmp, "wb") as f:
-        for idx, item, a, b, nwin in kept_pairs(items, eeg_base_path, window_size, stride, recordings):
+        for idx, item, a, b, nwin in walk:
             C_all = a.shape[0]
             length = (nwin - 1) * stride + window_size
             np.stack([a[:, :length], b[:, :length]]).astype(np.float32, copy=False).tofile(f)
@@ -285,6 +398,8 @@ def build_recording_store(items: Sequence[Dict], eeg_base_path, label2id: Dict[s
     np.save(out / "labels.npy", np.asarray(labels, dtype=np.int64))
     index = {"window_size": window_size, "stride": stride, "channels": C_all, "count": len(meta), "windows": meta,
              "label2id": label2id, "pairs": pairs, "window_pair": window_pair}
+    if prep is not None:
+        index["preprocessed"] = {**prep, "order": PREPROCESS_ORDER}
     (out / "index.json").write_text(json.dumps(index))
     return index
 
@@ -352,12 +467,17 @@ class DeviceRecordings:
 
     def gather(self, order: torch.Tensor, first: int, n: int, mode: int):
         """windows order[first : first + n] (order: i32 device tensor of window numbers) -> eeg1, eeg2 [n, C, T] f32 normalised in
-        `mode`, labels [n] i64 or None: one launch on the current stream, no copy, no sync"""
+        `mode` (0, 1: eg_window_gather; 2: as stored, eg_window_cut), labels [n] i64 or None: one launch on the current stream, no
+        copy, no sync"""
         import ctypes
         from ._lib import call, ptr
         eeg1 = torch.empty(n, self.C, self.T, dtype=torch.float32, device=self.device)
         eeg2 = torch.empty_like(eeg1)
         labels = torch.empty(n, dtype=torch.int64, device=self.device) if self.win_label is not None else None
+        if mode == 2:
+            call("eg_window_cut", ctypes.byref(self.desc), ptr(order), int(order.numel()), int(first), int(n), ptr(eeg1), ptr(eeg2),
+                 ptr(labels), torch.cuda.current_stream(self.device).cuda_stream)
+            return eeg1, eeg2, labels
         call("eg_window_gather", ctypes.byref(self.desc), ptr(order), int(order.numel()), int(first), int(n), ptr(eeg1), ptr(eeg2),
              ptr(labels), int(mode), torch.cuda.current_stream(self.device).cuda_stream)
         return eeg1, eeg2, labels
@@ -369,7 +489,8 @@ class ResidentWindows:
     the tables once; an epoch uploads this rank's order (int32) once; a batch is ONE eg_window_gather launch on the current
     stream -- no host gather, no H2D copy, no event, no sync.  Build it once per run and iterate it every epoch.  With
     world > 1 every rank holds the whole store and takes its rank::world share.  There is no fallback: a store that does not
-    fit raises EgError."""
+    fit raises EgError.  A store whose index carries `preprocessed` (build_recording_store(recording_preprocessing=...)) is cut
+    as stored (eg_window_cut); asking for preprocessing=True on top of it raises ValueError."""
     UPLOAD_CHUNK = 1 << 24      # floats per staged upload (64 MiB)
 
     def __init__(self, root, batch_size: int, device, rank: int = 0, world: int = 1, shuffle: bool = False, seed: int = 0,
@@ -377,6 +498,10 @@ class ResidentWindows:
         from ._lib import EgError
         self.root = Path(root)
         self.index = json.loads((self.root / "index.json").read_text())
+        self.preprocessed = self.index.get("preprocessed")
+        if self.preprocessed and preprocessing:
+            raise ValueError(f"{self.root}: the store's recordings were preprocessed whole ({self.preprocessed}); "
+                             "preprocessing=True would normalise its windows a second time")
         labels = np.load(self.root / "labels.npy")
         host = np.load(self.root / "store.npy", mmap_mode="r")
         validate_store(self.index, int(host.shape[0]))
@@ -385,6 +510,8 @@ class ResidentWindows:
             raise ValueError(f"{self.root}: {labels.shape[0]} labels for {self.n} windows")
         self.B, self.device, self.rank, self.world = batch_size, torch.device(device), rank, world
         self.shuffle, self.seed, self.mode, self.drop_last = shuffle, seed, 1 if preprocessing else 0, drop_last
+        if self.preprocessed:
+            self.mode = 2                               # cut as stored: the z-score was taken over the whole recording
         self.epoch = 0
         self.dataset_idx = np.asarray([w["dataset_idx"] for w in self.index["windows"]], dtype=np.int64)
         need = 4 * int(host.shape[0])

@@ -13,6 +13,7 @@ per batch -- no activation or gradient of that layer visits the host (DESIGN.md 
 extract_features_for_embedding (:602-673) over the inference engine.
 
     python -m eyegaze_multimodal_amd.predict --config CONFIG.yaml --checkpoint best_model.pt --out FILE.npz [--resident]
+                                             [--recording-preprocessing] (raw recordings; needs --resident)
                                              [--attention-stats [cross|LAYER]] [--connectivity-stats]
                                              [--frequency-sensitivity] [--gradcam [--gradcam-max-samples N]]
 """
@@ -114,13 +115,19 @@ def recording_starts(length: int, window: int, stride: int) -> np.ndarray:
 
 @torch.no_grad()
 def predict_recording(model, rec1, rec2, stride: Optional[int] = None, batch_size: int = 256,
-                      preprocessing: bool = False) -> Dict[str, Any]:
+                      preprocessing: bool = False, recording_preprocessing=None) -> Dict[str, Any]:
     """Classifies a whole recording pair at any stride.  rec1, rec2: (C, L) arrays or tensors (the shorter length and the smaller
     channel count count); the window length is the one model.cfg implies (4 * max_len), stride defaults to it.  The pair is
     uploaded once as a one-pair recording store; every batch is cut and normalised on the device (eg_window_gather) and goes
     straight into the inference engine.  Returns starts [n] (numpy i64), logits [n, ncls] f32 and predictions [n] i64 (device
-    tensors) and vote (majority_vote of the predictions)."""
-    from .data import DeviceRecordings, validate_store
+    tensors) and vote (majority_vote of the predictions).
+    recording_preprocessing = {sampling_rate, filter_low, filter_high}: for RAW recordings -- each player's recording goes whole
+    through data.preprocess_recordings (band-pass, CAR over the channels that count, z-score) before the pair is cut to the
+    common length, and the windows are cut as stored (eg_window_cut); it excludes preprocessing=True."""
+    from .data import DeviceRecordings, preprocess_recordings, recording_preprocessing_args, validate_store
+    prep = recording_preprocessing_args(recording_preprocessing) if recording_preprocessing is not None else None
+    if prep is not None and preprocessing:
+        raise ValueError("predict_recording: recording_preprocessing already normalises; preprocessing=True would do it twice")
     dev = next(model.parameters()).device
     T = 4 * model.cfg.max_len
     stride = T if stride is None else int(stride)
@@ -134,12 +141,15 @@ def predict_recording(model, rec1, rec2, stride: Optional[int] = None, batch_siz
         raise ValueError(f"predict_recording: recordings of {L} samples hold no window of {T} (batch_size {batch_size})")
     validate_store({"channels": C, "window_size": T, "count": n, "pairs": [{"offset": 0, "length": L}],
                     "window_pair": [0] * n, "windows": [{"start": int(s)} for s in starts]}, 2 * C * L)
+    if prep is not None:
+        r1, r2 = preprocess_recordings([r1[:C], r2[:C]], device=dev, **prep)
     data = torch.stack([r1[:C, :L], r2[:C, :L]]).to(dev).contiguous().reshape(-1)
     store = DeviceRecordings(data, [0], [L], np.zeros(n, np.int32), starts, None, C, T)
     order = torch.arange(n, dtype=torch.int32, device=dev)
     walk = _PredictWalk(model, n, False)
+    mode = 2 if prep is not None else 1 if preprocessing else 0
     for i in range(0, n, batch_size):
-        x1, x2, _ = store.gather(order, i, min(batch_size, n - i), 1 if preprocessing else 0)
+        x1, x2, _ = store.gather(order, i, min(batch_size, n - i), mode)
         walk.batch(x1, x2, None)
     out = walk.result()
     return {"starts": starts, **out, "vote": majority_vote(out["predictions"].cpu().numpy(), model.cfg.num_classes)}
@@ -452,9 +462,14 @@ def main(args):
     # (callers that build `args` themselves, from before the two flags existed, leave them out)
     conn_stats, band_masks = getattr(args, "connectivity_stats", False), getattr(args, "frequency_sensitivity", False)
     gradcam = getattr(args, "gradcam", False)
-    if args.resident or d.get("resident", False):
+    if getattr(args, "recording_preprocessing", False):
+        d["recording_preprocessing"] = True                          # the three values come from the YAML's data section
+    if args.resident:
+        d["resident"] = True
+    TA.recording_preprocessing_of(config)                            # raises unless the store is walked (--resident / data.resident)
+    if d.get("resident", False):
         # the store is walked directly: gather launch -> inference engine, batch by batch; no window visits the host
-        stores = TA.prepare_store(config, Path(t["output_dir"]) / "recording_store")
+        stores = TA.prepare_store(config, TA.store_dir(config))
         ld = ResidentWindows(stores[args.split], ebs, device, preprocessing=pre)
         out = predict_loader(model, ld)
         y = out["labels"].cpu()
@@ -505,6 +520,10 @@ if __name__ == "__main__":
     ap.add_argument("--dtype", type=str, default=None, choices=[None, "bf16", "fp16", "f32"])
     ap.add_argument("--resident", action="store_true",
                     help="walk the device-resident recording store (also: data.resident in the config) instead of the window shards")
+    ap.add_argument("--recording-preprocessing", action="store_true",
+                    help="raw recordings: band-pass (data.filter_low..data.filter_high Hz at data.sampling_rate), CAR and z-score every "
+                         "whole recording on the device when the store is built (also: data.recording_preprocessing in the config); "
+                         "needs --resident")
     ap.add_argument("--attention-stats", type=str, nargs="?", const="cross", default=None, metavar="cross|LAYER",
                     help="also reduce the attention probabilities of the cross stage (default) or of encoder layer LAYER: "
                          "attn_mean_map, attn_diagonals and attn_class_<name>_mean_diagonal in the output file")

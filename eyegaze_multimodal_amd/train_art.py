@@ -15,7 +15,10 @@ Differences, all additive:
   * `training.gradient_accumulation_steps: k` (absent = 1 = the reference's one batch per step): every k-th train_step ends
     in the optimiser step, on the sum of the k micro-batches' gradients divided by k (Trainer.train_step / Trainer.flush);
   * `data.resident: true` (absent = false = the window shards): the recordings stay in device memory for the run and every
-    batch is cut and normalised there by one launch (data.ResidentWindows); the batches are the shards' bits.
+    batch is cut and normalised there by one launch (data.ResidentWindows, DESIGN.md §8i); the batches are the shards' bits;
+  * `data.recording_preprocessing: true` (absent = false; needs `data.resident: true`): for RAW recordings -- every recording
+    goes whole through the reference's preprocess_eeg on the device (band-pass `data.filter_low`..`data.filter_high` Hz at
+    `data.sampling_rate`, CAR, z-score) when the stores are built, and the windows are cut as stored.
 """
 from __future__ import annotations
 
@@ -413,12 +416,36 @@ def prepare_store(config: Dict[str, Any], out_dir: Path, rank: int = 0, world: i
     """CSV recordings -> recording stores (data.build_recording_store) for `data.resident: true`, by prepare_shards' protocol;
     the fingerprint carries a kind tag, so a directory of shards is never taken for a store."""
     d = config["data"]
+    prep = recording_preprocessing_of(config)
 
     def build(its, path):
-        idx = build_recording_store(its, d["eeg_base_path"], d["label2id"], path, d["window_size"], d["stride"])
-        return f"{idx['count']} windows over {len(idx['pairs'])} resident recording pairs"
+        idx = build_recording_store(its, d["eeg_base_path"], d["label2id"], path, d["window_size"], d["stride"],
+                                    recording_preprocessing=prep)
+        return f"{idx['count']} windows over {len(idx['pairs'])} resident recording pairs" + (f", preprocessed {prep}" if prep else "")
 
-    return _prepare_windows(config, out_dir, rank, world, timeout_s, shard_fingerprint(config) + ":store", build, "recording store")
+    kind = ":store" if prep is None else ":store:" + ",".join(f"{k}={prep[k]}" for k in sorted(prep))
+    return _prepare_windows(config, out_dir, rank, world, timeout_s, shard_fingerprint(config) + kind, build, "recording store")
+
+
+def recording_preprocessing_of(config: Dict[str, Any]) -> Optional[Dict[str, float]]:
+    """`data.recording_preprocessing: true` -> build_recording_store's mapping from data.sampling_rate / filter_low / filter_high
+    (None when absent or false).  It needs data.resident: the shards have no recording-level pass."""
+    d = config["data"]
+    if not d.get("recording_preprocessing", False):
+        return None
+    if not d.get("resident", False):
+        raise ValueError("data.recording_preprocessing: true needs data.resident: true (the window shards have no recording-level pass)")
+    if d.get("enable_preprocessing", False):
+        raise ValueError("data.recording_preprocessing: true excludes data.enable_preprocessing: true (the windows would be normalised twice)")
+    from .data import recording_preprocessing_args
+    return recording_preprocessing_args(d)
+
+
+def store_dir(config: Dict[str, Any]) -> Path:
+    """where a run keeps its recording stores: preprocessed stores under a name of their own, so that a raw store of an earlier
+    run is never taken for one"""
+    name = "recording_store_preprocessed" if recording_preprocessing_of(config) else "recording_store"
+    return Path(config["training"]["output_dir"]) / name
 
 
 def window_loaders(config: Dict[str, Any], device, rank: int, world: int):
@@ -430,11 +457,12 @@ def window_loaders(config: Dict[str, Any], device, rank: int, world: int):
     # one process: every window, tail batch included, as the reference's DataLoader (train_art.py:334-341);
     # data parallel: every rank must take the same number of steps, so the ragged tail is dropped
     train_kw = dict(shuffle=True, seed=d["random_seed"], preprocessing=pre, drop_last=world > 1)
+    recording_preprocessing_of(config)          # raises on data.recording_preprocessing without data.resident
     if not d.get("resident", False):
         shards = prepare_shards(config, Path(t["output_dir"]) / "window_shards", rank, world)   # file-based wait, no collective
         return (lambda: WindowShards(shards["train"], bs, device, rank, world, **train_kw),
                 lambda: WindowShards(shards["test"], ebs, device, rank, world, preprocessing=pre))
-    stores = prepare_store(config, Path(t["output_dir"]) / "recording_store", rank, world)
+    stores = prepare_store(config, store_dir(config), rank, world)
     train_ld = ResidentWindows(stores["train"], bs, device, rank, world, **train_kw)
     test_ld = ResidentWindows(stores["test"], ebs, device, rank, world, preprocessing=pre)
     return (lambda: train_ld), (lambda: test_ld)

@@ -116,6 +116,45 @@ typedef struct eg_window_gather_desc {
 int eg_window_gather(const eg_window_gather_desc* d, const int32_t* order, int order_len, int first, int n, float* eeg1,
                      float* eeg2, int64_t* labels, int mode, void* stream);
 
+/* eg_window_gather's addressing, tables, order, outputs and labels without a normalisation: eeg1 / eeg2 [n, C, T] receive the
+ * windows AS STORED, bit for bit (a store whose recordings were preprocessed whole, below, is cut this way).  Refused on the
+ * host: what eg_window_gather refuses (there is no mode). */
+int eg_window_cut(const eg_window_gather_desc* d, const int32_t* order, int order_len, int first, int n, float* eeg1,
+                  float* eeg2, int64_t* labels, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Recording-level preprocessing (2_Preprocessing/scripts/preprocess_eeg_windows.py:145-172, preprocess_eeg): zero-phase
+ * band-pass, common-average reference, per-channel z-score, over WHOLE recordings, in place, before windows are cut.
+ * Both entry points work on n_rows channel rows of f32: row r is the row_len[r] floats at data + row_off[r]; rows are ragged;
+ * C consecutive rows are one player's recording and share a length.  Every pointer of the descriptor is a DEVICE pointer; the
+ * descriptor itself is host memory.  The tables are trusted: whoever builds them proves that every row lies inside `data`, that
+ * rows do not overlap, that row_len[r] > 3 * ncoef, that lengths are equal inside a group of C and that ws_off is the running
+ * sum of row_len + 6 * ncoef (data.preprocess_recordings).  max_len only sizes grids: a wrong value costs time, not bounds.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct eg_recording_rows_desc {
+  float* data;
+  const int64_t* row_off;     /* [n_rows] float offset of the row in data */
+  const int32_t* row_len;     /* [n_rows] samples of the row */
+  const int64_t* ws_off;      /* [n_rows] offset (doubles) of the row's row_len + 6 ncoef workspace doubles; filtfilt only */
+  int32_t n_rows, C, max_len, _pad;
+} eg_recording_rows_desc;
+/* scipy.signal.filtfilt(b, a, x) with its defaults, restated, over every row: pad = 3 ncoef; the row is extended oddly by pad
+ * samples on both sides, 2 x[0] - x[pad..1] in front and 2 x[L-1] - x[L-2..L-pad-1] behind, IN FLOAT32 (scipy forms the
+ * extension in its input's dtype); the forward pass runs over the extended row from state zi * ext[0], the backward pass over the
+ * forward output, reversed, from state zi * (last forward output); the padding is dropped and the result rounded to f32 once.
+ * Both passes and the intermediate (workspace: sum over rows of row_len + 2 pad doubles) are fp64; the recurrence is scipy's
+ * transposed direct form II in its order: y = z[0] + b[0] x; z[i] = z[i+1] + b[i+1] x - a[i+1] y; z[n-1] = b[n] x - a[n] y.
+ * b, a [ncoef], zi [ncoef - 1] are HOST doubles and travel as kernel arguments.  One lane owns one row and walks it
+ * sequentially; a wave (one block) takes 64 consecutive rows.  Refused on the host: null pointers, n_rows <= 0, C <= 0, ncoef
+ * outside [2, 17], a[0] != 1, workspace_capacity < workspace_need (both in doubles; workspace_need is the caller's sum). */
+int eg_recording_filtfilt(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
+                          double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream);
+/* preprocess_eeg's steps 2-3, in place: per group of C rows and per sample car = (sum over c in channel order, f32) / C,
+ * v = x - car; per row out = (v - mean) / (std_pop + 1e-8) with mean and variance accumulated in double and rounded to f32
+ * before use (eg_window_normalize's mode 1 arithmetic).  Two launches: a sample-parallel CAR pass, then one block per row.
+ * Refused on the host: null pointers, n_rows <= 0, C <= 0, n_rows % C != 0. */
+int eg_recording_car_zscore(const eg_recording_rows_desc* d, void* stream);
+
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
  * pl = 0 for buffer 1 and 1 for buffer 2.  Every draw is counter-based: H(site, i) = eg_hash(state->seed_lo, state->seed_hi,
