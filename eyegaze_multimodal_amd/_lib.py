@@ -157,7 +157,18 @@ SIGNATURES = {
     "eg_window_cut": [C.POINTER(WindowGatherDesc), _P, _I, _I, _I, _P, _P, _P, _P],
     "eg_recording_filtfilt": [C.POINTER(RecordingRowsDesc), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I,
                               _P, _L, _L, _P],
+    "eg_recording_filtfilt_exact": [C.POINTER(RecordingRowsDesc), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    _I, _P, _L, _L, _P],
     "eg_recording_car_zscore": [C.POINTER(RecordingRowsDesc), _P],
+    "eg_recording_car": [C.POINTER(RecordingRowsDesc), _P],
+    "eg_trial_welch": [C.POINTER(RecordingRowsDesc), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _P],
+    "eg_trial_analytic_twiddle_doubles": [_I],                       # returns int64_t: trial_analytic_twiddle_doubles() below
+    "eg_trial_analytic_tables": [C.POINTER(RecordingRowsDesc), _P, _P, _L, _L, _P],
+    "eg_trial_analytic": [C.POINTER(RecordingRowsDesc), _P, _P, _P, _P, _P, _L, _L, _P],
+    "eg_trial_pairs_workspace_floats": [_I, _I, _I],                 # returns int64_t: trial_pairs_workspace_floats() below
+    "eg_trial_pairs": [C.POINTER(RecordingRowsDesc), _P, _P, _P, _P, _L, _P, _I, _I, _P],
+    "eg_trial_coherence_workspace_floats": [_I, _I],                 # returns int64_t: trial_coherence_workspace_floats() below
+    "eg_trial_coherence": [C.POINTER(RecordingRowsDesc), _P, _L, _P, _I, _I, _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
@@ -273,6 +284,27 @@ def gradcam_scratch_elems(B: int, Cn: int, Hp: int, Wp: int) -> int:
     l = lib()
     l.eg_gradcam_scratch_elems.restype = C.c_int64
     return int(l.eg_gradcam_scratch_elems(B, Cn, Hp, Wp))
+
+
+def trial_analytic_twiddle_doubles(max_len: int) -> int:
+    """Doubles at the head of eg_trial_analytic's workspace: the twiddle table for rows up to max_len (host only; -1: bad length)"""
+    l = lib()
+    l.eg_trial_analytic_twiddle_doubles.restype = C.c_int64
+    return int(l.eg_trial_analytic_twiddle_doubles(max_len))
+
+
+def trial_pairs_workspace_floats(n_rows: int, Cn: int, max_len: int) -> int:
+    """Floats of workspace eg_trial_pairs needs (host only; -1: bad shape)"""
+    l = lib()
+    l.eg_trial_pairs_workspace_floats.restype = C.c_int64
+    return int(l.eg_trial_pairs_workspace_floats(n_rows, Cn, max_len))
+
+
+def trial_coherence_workspace_floats(n_rows: int, max_len: int) -> int:
+    """Floats of workspace eg_trial_coherence needs (host only; -1: bad shape)"""
+    l = lib()
+    l.eg_trial_coherence_workspace_floats.restype = C.c_int64
+    return int(l.eg_trial_coherence_workspace_floats(n_rows, max_len))
 
 
 def exported_symbols():

@@ -24,8 +24,11 @@ struct IirCoef {                       // zero-padded behind ncoef: the padded r
   double b[RP_MAXC], a[RP_MAXC], zi[RP_MAXC - 1];
 };
 
-// scipy's transposed direct form II, NS = number of states kept in registers
-template <int NS>
+// scipy's transposed direct form II, NS = number of states kept in registers.  EXACT: every product and sum rounded on its own, as
+// scipy's compiled loop rounds them; otherwise the compiler contracts them into multiply-adds.  Both are correct to fp64, but the
+// recurrence amplifies the difference by the filter's conditioning: for the 0.5-50 Hz band it stays below the f32 output's rounding,
+// for a 0.5-4 Hz band at 250 Hz it reaches 1e-4 of the signal.
+template <int NS, bool EXACT>
 struct Tdf2 {
   double z[NS];
   __device__ __forceinline__ void start(const IirCoef& k, double x0) {
@@ -33,6 +36,14 @@ struct Tdf2 {
     for (int i = 0; i < NS; ++i) z[i] = k.zi[i] * x0;
   }
   __device__ __forceinline__ double step(const IirCoef& k, double x) {
+    if (EXACT) {
+#pragma clang fp contract(off)
+      const double y = z[0] + k.b[0] * x;
+#pragma unroll
+      for (int i = 0; i < NS - 1; ++i) z[i] = z[i + 1] + k.b[i + 1] * x - k.a[i + 1] * y;
+      z[NS - 1] = k.b[NS] * x - k.a[NS] * y;
+      return y;
+    }
     const double y = z[0] + k.b[0] * x;
 #pragma unroll
     for (int i = 0; i < NS - 1; ++i) z[i] = z[i + 1] + k.b[i + 1] * x - k.a[i + 1] * y;
@@ -49,7 +60,7 @@ __device__ __forceinline__ float odd_ext(const float* __restrict__ x, float x0, 
   return t < 0 ? 2.f * x0 - v : t < L ? v : 2.f * xl - v;
 }
 
-template <int NS>
+template <int NS, bool EXACT>
 __global__ __launch_bounds__(RP_ROWS) void recording_filtfilt_kernel(const eg_recording_rows_desc d, const IirCoef k, const int pad,
                                                                      double* __restrict__ ws) {
   __shared__ float ftile[RP_ROWS * RP_LD];
@@ -72,7 +83,7 @@ __global__ __launch_bounds__(RP_ROWS) void recording_filtfilt_kernel(const eg_re
   for (int i = 0; i < RP_ROWS; ++i) Emax = max(Emax, s_ext[i]);
   if (Emax == 0) return;
 
-  Tdf2<NS> f;
+  Tdf2<NS, EXACT> f;
   double ylast = 0.0;
   // forward: extended row -> workspace (fp64).  The next tile's loads are requested before this tile's recurrence and held in
   // registers, so their latency passes under it: one wave has nobody else to hide it.
@@ -190,33 +201,60 @@ int rows_desc_check(const char* who, const eg_recording_rows_desc* d) {
 
 }  // namespace
 
-extern "C" int eg_recording_filtfilt(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
-                                     double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream) {
-  if (rows_desc_check("eg_recording_filtfilt", d)) return 1;
-  EG_CHECK(d->ws_off && b && a && zi && workspace, "eg_recording_filtfilt: null pointer");
-  EG_CHECK(ncoef >= 2 && ncoef <= RP_MAXC, "eg_recording_filtfilt: ncoef=%d outside [2, %d]", ncoef, RP_MAXC);
-  EG_CHECK(a[0] == 1.0, "eg_recording_filtfilt: a[0]=%g must be 1 (normalise the coefficients)", a[0]);
+namespace {
+
+template <bool EXACT>
+int launch_filtfilt(const char* who, const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
+                    double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream) {
+  if (rows_desc_check(who, d)) return 1;
+  EG_CHECK(d->ws_off && b && a && zi && workspace, "%s: null pointer", who);
+  EG_CHECK(ncoef >= 2 && ncoef <= RP_MAXC, "%s: ncoef=%d outside [2, %d]", who, ncoef, RP_MAXC);
+  EG_CHECK(a[0] == 1.0, "%s: a[0]=%g must be 1 (normalise the coefficients)", who, a[0]);
   EG_CHECK(workspace_need > 0 && workspace_need <= workspace_capacity,
-           "eg_recording_filtfilt: the rows need %lld workspace doubles, the workspace's capacity is %lld", (long long)workspace_need,
+           "%s: the rows need %lld workspace doubles, the workspace's capacity is %lld", who, (long long)workspace_need,
            (long long)workspace_capacity);
   IirCoef k = {};
   for (int i = 0; i < ncoef; ++i) k.b[i] = b[i], k.a[i] = a[i];
   for (int i = 0; i + 1 < ncoef; ++i) k.zi[i] = zi[i];
   const dim3 grid((unsigned)((d->n_rows + RP_ROWS - 1) / RP_ROWS)), block(RP_ROWS);
   if (ncoef == 9)      // the reference's order-4 band-pass: its eight states and nothing else
-    hipLaunchKernelGGL(recording_filtfilt_kernel<8>, grid, block, 0, (hipStream_t)stream, *d, k, 3 * ncoef, workspace);
+    hipLaunchKernelGGL((recording_filtfilt_kernel<8, EXACT>), grid, block, 0, (hipStream_t)stream, *d, k, 3 * ncoef, workspace);
   else
-    hipLaunchKernelGGL(recording_filtfilt_kernel<RP_MAXC - 1>, grid, block, 0, (hipStream_t)stream, *d, k, 3 * ncoef, workspace);
+    hipLaunchKernelGGL((recording_filtfilt_kernel<RP_MAXC - 1, EXACT>), grid, block, 0, (hipStream_t)stream, *d, k, 3 * ncoef, workspace);
   EG_LAUNCH_CHECK("recording_filtfilt");
   return 0;
 }
 
-extern "C" int eg_recording_car_zscore(const eg_recording_rows_desc* d, void* stream) {
-  if (rows_desc_check("eg_recording_car_zscore", d)) return 1;
-  EG_CHECK(d->n_rows % d->C == 0, "eg_recording_car_zscore: n_rows=%d is no multiple of C=%d", d->n_rows, d->C);
+}  // namespace
+
+extern "C" int eg_recording_filtfilt(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
+                                     double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream) {
+  return launch_filtfilt<false>("eg_recording_filtfilt", d, b, a, zi, ncoef, workspace, workspace_need, workspace_capacity, stream);
+}
+
+extern "C" int eg_recording_filtfilt_exact(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
+                                           double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream) {
+  return launch_filtfilt<true>("eg_recording_filtfilt_exact", d, b, a, zi, ncoef, workspace, workspace_need, workspace_capacity, stream);
+}
+
+namespace {
+
+// the CAR launch of both entry points
+int launch_car(const char* who, const eg_recording_rows_desc* d, void* stream) {
+  if (rows_desc_check(who, d)) return 1;
+  EG_CHECK(d->n_rows % d->C == 0, "%s: n_rows=%d is no multiple of C=%d", who, d->n_rows, d->C);
   const int chunks = d->max_len > 0 ? (int)std::min<long long>(((long long)d->max_len + 255) / 256, 4096) : 1;
   hipLaunchKernelGGL(recording_car_kernel, dim3(d->n_rows / d->C, chunks), dim3(256), 0, (hipStream_t)stream, *d);
   EG_LAUNCH_CHECK("recording_car");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int eg_recording_car(const eg_recording_rows_desc* d, void* stream) { return launch_car("eg_recording_car", d, stream); }
+
+extern "C" int eg_recording_car_zscore(const eg_recording_rows_desc* d, void* stream) {
+  if (launch_car("eg_recording_car_zscore", d, stream)) return 1;
   hipLaunchKernelGGL(recording_zscore_kernel, dim3(d->n_rows), dim3(256), 0, (hipStream_t)stream, *d);
   EG_LAUNCH_CHECK("recording_zscore");
   return 0;

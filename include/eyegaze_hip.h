@@ -149,11 +149,83 @@ typedef struct eg_recording_rows_desc {
  * outside [2, 17], a[0] != 1, workspace_capacity < workspace_need (both in doubles; workspace_need is the caller's sum). */
 int eg_recording_filtfilt(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
                           double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream);
+/* eg_recording_filtfilt with every product and sum of the recurrence rounded on its own (no contracted multiply-adds): the
+ * arithmetic of scipy's compiled loop, operation by operation.  For the narrow low bands of the trial features (0.5-4 Hz at 250 Hz)
+ * the recurrence amplifies the rounding difference of a contracted multiply-add to 1e-4 of the signal; this entry point stays
+ * on scipy's side of it.  Same arguments, same refusals; about three times the time per launch (measured: DESIGN.md §8m). */
+int eg_recording_filtfilt_exact(const eg_recording_rows_desc* d, const double* b, const double* a, const double* zi, int ncoef,
+                                double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream);
 /* preprocess_eeg's steps 2-3, in place: per group of C rows and per sample car = (sum over c in channel order, f32) / C,
  * v = x - car; per row out = (v - mean) / (std_pop + 1e-8) with mean and variance accumulated in double and rounded to f32
  * before use (eg_window_normalize's mode 1 arithmetic).  Two launches: a sample-parallel CAR pass, then one block per row.
  * Refused on the host: null pointers, n_rows <= 0, C <= 0, n_rows % C != 0. */
 int eg_recording_car_zscore(const eg_recording_rows_desc* d, void* stream);
+/* The CAR pass of eg_recording_car_zscore on its own -- the same kernel, so bit for bit that pass -- and no z-score
+ * (2_Preprocessing/scripts/extract_eeg_features.py:183-186).  Refused on the host: what eg_recording_car_zscore refuses. */
+int eg_recording_car(const eg_recording_rows_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Trial features (2_Preprocessing/scripts/extract_eeg_features.py): Welch PSD and band energies, the analytic
+ * signal of a band-filtered trial, the pair sums of six connectivity metrics and the segment coherence.  All four work on
+ * eg_recording_rows_desc rows with 2 C consecutive rows per TRIAL -- player 1's C channels, then player 2's -- of one length
+ * L in [256, 65536].  Connectivity goes to con [n_trials][3][7][nbands][C][C] f32: matrix 0 = intra-brain player 1, 1 =
+ * intra-brain player 2, 2 = inter-brain (rows: player 1, columns: player 2); metric order pearson, power_corr, plv, pli, wpli,
+ * coherence, phase_diff.  The tables are trusted as above; additionally max_len must be the largest row_len (it sizes
+ * workspaces; every kernel skips a row longer than max_len, so nothing is written out of bounds).  Every entry point refuses
+ * on the host: null pointers, n_rows <= 0, C <= 0, n_rows % (2 C) != 0, max_len outside [256, 65536], a workspace below its need.
+ * ------------------------------------------------------------------------------------------- */
+#define EG_TRIAL_MIN_LEN 256
+#define EG_TRIAL_MAX_LEN 65536
+#define EG_TRIAL_NBINS 129
+#define EG_TRIAL_MAX_BANDS 8
+/* scipy.signal.welch(x, fs, nperseg=256) with its defaults, restated, per row: segments of 256 at a hop of 128 (no padding of
+ * the tail), each minus its mean, periodic Hann window, 256-point FFT in LDS in fp64, |X|^2 / (fs sum w^2), bins 1..127
+ * doubled, mean over the segments, rounded to f32 once: psd [n_rows][129].  energy [n_rows][nbands] = the mean of
+ * psd[band_k0[b] .. band_k1[b]] (bins, inclusive; 0 for an empty range); band_k0 / band_k1 are HOST arrays.  *nonfinite
+ * (device, may be null) is set to 1 when any psd value is not finite -- a NaN or Inf of the input reaches every bin of its row
+ * through the filter -- and left alone otherwise.  Refused too: fs <= 0, nbands outside [0, 8], a bin outside [0, 128]. */
+int eg_trial_welch(const eg_recording_rows_desc* d, double fs, const int32_t* band_k0, const int32_t* band_k1, int nbands,
+                   float* psd, float* energy, int32_t* nonfinite, void* stream);
+/* Doubles of workspace eg_trial_analytic needs besides the tables' own: the twiddle table of the largest transform (host only;
+ * -1: max_len outside [256, 65536]). */
+int64_t eg_trial_analytic_twiddle_doubles(int max_len);
+/* The tables eg_trial_analytic reads, written into its workspace (doubles): [0, twiddle_doubles) the twiddles of the largest
+ * transform; at chirp_off[g] (device, [n_rows / (2 C)], even) trial g's 2 M + 2 L doubles -- the spectrum of the circular chirp
+ * filter and the chirp w[n] = exp(-i pi (n^2 mod 2 L) / L), the angle formed in integers -- M the smallest power of two
+ * >= 2 L - 1.  They depend on the lengths alone: build them once and run eg_trial_analytic on as many band signals of the same
+ * rows as there are.  Two launches: twiddles, one block per trial.  workspace_need is the caller's total for both entry points. */
+int eg_trial_analytic_tables(const eg_recording_rows_desc* d, const int64_t* chirp_off, double* workspace, int64_t workspace_need,
+                             int64_t workspace_capacity, void* stream);
+/* scipy.signal.hilbert along time at every row's own length L, restated in fp64: DFT of length L, weights 1, 2..2, (1 at L/2
+ * when L is even), 0..0, inverse DFT.  One path for every L: both transforms are chirp-z (Bluestein) transforms over a
+ * power-of-two FFT of size M, from the tables eg_trial_analytic_tables wrote into the same workspace for the same descriptor.
+ * Per row, f32, at the row's own offset row_off[r] of three planes shaped as `data`: amp = |z|, cs + i sn = z / |z|, (1, 0)
+ * where |z| == 0.  `data` (the band signal) is only read.  ws_off[r] (even) is the row's own 2 M workspace doubles where
+ * M > 8192 (a shorter row transforms in LDS and its ws_off is not read).  One launch, one block per row. */
+int eg_trial_analytic(const eg_recording_rows_desc* d, const int64_t* chirp_off, float* amp, float* cs, float* sn,
+                      double* workspace, int64_t workspace_need, int64_t workspace_capacity, void* stream);
+/* Floats of workspace eg_trial_pairs needs (host only; -1: bad shape): 4 per row + 6 C C per trial, matrix and 256-sample split
+ * of max_len. */
+int64_t eg_trial_pairs_workspace_floats(int n_rows, int C, int max_len);
+/* Six metrics of every channel pair (i, j) of the three matrices, over all L samples of the band signal x = data, its amplitude
+ * a and unit phasor u = cs + i sn (eg_trial_analytic's planes), P_t = u_i(t) conj(u_j(t)), zs(v) = (v - mean) / (std_pop + 1e-8):
+ *   pearson = mean zs(x_i) zs(x_j); power_corr = the same on a; plv = |mean P|; phase_diff = angle(mean P);
+ *   pli = |mean sign(Im P)|; wpli = |mean Im P| / (mean |Im P| + 1e-8)
+ * written to con[.][.][m][band] for m in {0, 1, 2, 3, 4, 6}.  Time is split over workgroups in chunks of 256 samples; the four
+ * product sums of a chunk are f32 MFMA GEMMs over time, sign and |.| sums vector work on the same tiles with Im P formed from two
+ * rounded products; the chunks are added in ascending order in fp64 by a second launch, so the result is bit-reproducible.  On
+ * the diagonal of an intra matrix Im P counts as exactly 0: pli = wpli = phase_diff = 0.  Refused too: band outside
+ * [0, nbands), nbands outside [1, 8]. */
+int eg_trial_pairs(const eg_recording_rows_desc* d, const float* amp, const float* cs, const float* sn, float* workspace,
+                   int64_t workspace_capacity, float* con, int band, int nbands, void* stream);
+/* Floats of workspace eg_trial_coherence needs (host only; -1: bad shape): per row 129 (1 + 2 (max_len / 256)). */
+int64_t eg_trial_coherence_workspace_floats(int n_rows, int max_len);
+/* compute_coherence_fast / compute_inter_coherence (:409-462, :590-648) of the band signal: L / 256 segments of 256 without
+ * overlap, symmetric Hann window (np.hanning, rounded to f32), 256-point FFT in fp64, Pxx = mean |X|^2, Pxy = mean X_i conj X_j,
+ * con[.][.][5][band][i][j] = the mean over the 129 bins of |Pxy|^2 / (Pxx_i Pxx_j + 1e-8).  The 1e-8 is absolute: the rows are
+ * not rescaled.  Two launches: spectra per row, then one block per (trial, matrix, i). */
+int eg_trial_coherence(const eg_recording_rows_desc* d, float* workspace, int64_t workspace_capacity, float* con, int band,
+                       int nbands, void* stream);
 
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
