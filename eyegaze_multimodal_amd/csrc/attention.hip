@@ -157,8 +157,23 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
 // ------------------------------------------------------------------------------------------------
 // NKTX > 0: the tile count is a compile-time constant and, with TAIL, the last key tile holds ONE valid key (S = 16 n + 1: the
 // S = 65 windows of the benchmark); <SP, 0, false> is the general form.
+// IR: the rows of the LDS images, apart from the tile capacity SP (which governs NKT, the pair loop and accq).  Windows of up to 80
+// tokens are staged in 80-row images (IR = 80 at SP = 96): 40 192 B per workgroup instead of 46 592 and 128 registers without
+// scratch memory instead of 153, four workgroups per CU instead of three (2048 workgroups of the benchmark: two full rounds instead
+// of 2.67).  At 128 registers WITH scratch memory (what the bound alone compiles to: 136 B per lane) the step is 0.18 ms slower than
+// at three per CU; without any, 0.04 ms faster.
+constexpr int bwd1_lds(int IR) { return 2 * (3 * IR * 64 + 2 * IR * 4 + 2 * 2 * 32 * 32); }
+constexpr int bwd1_wg(int SP, int IR) { return IR < SP ? 4 : SP <= 96 ? 3 : 2; }      // workgroups per CU: registers AND LDS
+// A transposed read covers 32 rows from rbase.  At rbase = 64 its upper 16 lie beyond an 80-row image; they are rows >= S, zeros
+// in a full image, so they are zero k-slots here (and what follows the image in LDS is never an MFMA operand).
+template <typename T, int SP, int IR>
+__device__ __forceinline__ FR<T> bwd1_frag_tr(const char* img, int rbase, int dt, int lane) {
+  if (IR == SP || rbase + 32 <= IR) return hd_frag_tr<T>(img, rbase, dt, lane);
+  return hd_frag_tr_lo<T>(img, rbase, dt, lane);
+}
+
 // One key tile of the single-sweep backward (attn_bwd1_kernel): all of the wave's query pairs against key tile kt.
-template <typename T, int SP, int NKTX, bool tail>
+template <typename T, int SP, int IR, int NKTX, bool tail>
 __device__ __forceinline__ void bwd1_key_tile(const int kt, const int S, const int nkt, const bool valid, const int lane, const char* kimg,
                                               const char* qimg, const char* doimg, const float* lsel, const float* dl, char* pimg,
                                               char* simg, const T* vbase, const long long ld, FR<T>& vnext, f32x4 (&accq)[SP / 16][2],
@@ -178,7 +193,7 @@ __device__ __forceinline__ void bwd1_key_tile(const int kt, const int S, const i
   }
   FR<T> ktr[2];
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt) ktr[dt] = hd_frag_tr<T>(kimg, 32 * (kt >> 1), dt, lane);
+  for (int dt = 0; dt < 2; ++dt) ktr[dt] = bwd1_frag_tr<T, SP, IR>(kimg, 32 * (kt >> 1), dt, lane);
   f32x4 dk[2] = {zero4, zero4}, dv[2] = {zero4, zero4};
 #pragma unroll
   for (int qp = 0; qp < NKT / 2; ++qp) {
@@ -196,7 +211,9 @@ __device__ __forceinline__ void bwd1_key_tile(const int kt, const int S, const i
         const FR<T> qf = hd_frag_row<T>(qimg, q, g);
         const FR<T> dof = hd_frag_row<T>(doimg, q, g);
         const float lq = lsel[q], dq = dl[q];
-        const f32x4 sT = H16<T>::mfma(kfr, qf, zero4);
+        // (at 128 registers the key tile's K rows are read again for every block: one ds_read_b128 instead of four held registers)
+        const FR<T> kfb = IR < SP ? hd_frag_row<T>(kimg, key, g) : kfr;
+        const f32x4 sT = H16<T>::mfma(kfb, qf, zero4);
         const f32x4 dpT = H16<T>::mfma(vfr, dof, zero4);
         float pd[4] = {0.f, 0.f, 0.f, 0.f};
         f32x4 dsv = zero4;
@@ -240,9 +257,9 @@ __device__ __forceinline__ void bwd1_key_tile(const int kt, const int S, const i
       const FR<T> pdf = __builtin_bit_cast(FR<T>, pt), dsT = __builtin_bit_cast(FR<T>, stt);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        const FR<T> dotr = hd_frag_tr<T>(doimg, 32 * qp, dt, lane);
+        const FR<T> dotr = bwd1_frag_tr<T, SP, IR>(doimg, 32 * qp, dt, lane);
         dv[dt] = H16<T>::mfma(dotr, pdf, dv[dt]);
-        const FR<T> qtr = hd_frag_tr<T>(qimg, 32 * qp, dt, lane);
+        const FR<T> qtr = bwd1_frag_tr<T, SP, IR>(qimg, 32 * qp, dt, lane);
         dk[dt] = H16<T>::mfma(qtr, dsT, dk[dt]);
       }
     }
@@ -259,17 +276,20 @@ __device__ __forceinline__ void bwd1_key_tile(const int kt, const int S, const i
   }
 }
 
-template <typename T, int SP, int NKTX, bool TAIL>
-__global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const T* __restrict__ qkv, const T* __restrict__ ctx,
+template <typename T, int SP, int NKTX, bool TAIL, int IR = SP>
+__global__ __launch_bounds__(256, bwd1_wg(SP, IR)) void attn_bwd1_kernel(const T* __restrict__ qkv, const T* __restrict__ ctx,
                                                         const T* __restrict__ dctx, const float* __restrict__ lse,
                                                         T* __restrict__ dqkv, int NB, int S, int H, int kv_shift,
                                                         DropCfg dc, const eg_step_state* st) {
   constexpr int NKT = SP / 16;
-  constexpr int IMG = SP * 64;
+  constexpr int IMG = IR * 64;
   constexpr int SCR = 2 * 32 * 32;                            // one wave's P and dS images: [32 query slots][16 keys] each
-  constexpr int WB = 3 * IMG + 2 * SP * 4 + 2 * SCR;
+  constexpr int WB = 3 * IMG + 2 * IR * 4 + 2 * SCR;
+  static_assert(IR % 16 == 0 && IR <= SP && WB == bwd1_lds(IR) / 2, "attn_bwd1: image rows");
+  static_assert(2 * (NKT / 2) * 2 * 64 * 16 <= 3 * IMG, "attn_bwd1: the dQ exchange buffer lies inside the three dead images");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, role = wave & 1;
+  // (IR < SP: the wave id as a scalar, so that the head's indices and base addresses are scalars too and not vector registers)
+  const int lane = threadIdx.x & 63, wave = IR < SP ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6, role = wave & 1;
   const int l15 = lane & 15, g = lane >> 4;
   int pid = blockIdx.x * 2 + (wave >> 1);
   const bool valid = pid < NB * H;
@@ -288,18 +308,23 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
   char* kimg = base + IMG;
   char* doimg = base + 2 * IMG;
   float* lsel = (float*)(base + 3 * IMG);
-  float* dl = lsel + SP;
-  char* pimg = base + 3 * IMG + 2 * SP * 4 + role * SCR;
+  float* dl = lsel + IR;
+  char* pimg = base + 3 * IMG + 2 * IR * 4 + role * SCR;
   char* simg = pimg + 32 * 32;
   // every global read of the prologue is requested before the first wait: the three images (this wave's half) and the lane's
   // dO / O rows and log-sum-exp for delta = rowsum(dO * O)
-  constexpr int NCH = SP / 32;                               // 16-B chunks per lane and image: SP * 4 / 128
+  constexpr int NCH = (IR + 31) / 32;                        // 16-B chunks per lane and image: IR * 4 / 128, rounded up (rows_store
+                                                             // drops the chunks of rows >= IR, rows_request reads none: IR >= S)
   const int first = lane + 64 * role;
   u32x4 rq[NCH], rk[NCH], rd[NCH];
   rows_request<T, NCH>(rq, qbase, ld, S, first);
   rows_request<T, NCH>(rk, kbase, ld, S, first);
   rows_request<T, NCH>(rd, dobase, D, S, first);
-  constexpr int NQ = (SP + 127) / 128;                       // delta rows per lane (query first + 128 j)
+  constexpr int NQ = (IR + 127) / 128;                       // delta rows per lane (query first + 128 j)
+  // On 80-row images the lane's dO row is read back from the dO image after a barrier instead of fetched a second time: 16
+  // registers and four global loads fewer across the prologue's wait (same elements in the same order: delta keeps its bits).
+  // Worth 0.013 ms per step against the second fetch, both at 128 registers without scratch memory.
+  constexpr bool DIMG = IR < SP;
   u32x4 da[NQ][4], oa[NQ][4];
   float lq0[NQ];
 #pragma unroll
@@ -312,18 +337,29 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
       lq0[j] = lse[((long long)b * H + h) * S + qd];
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) {
-        da[j][c4] = *(const u32x4*)(dobase + (long long)qd * D + c4 * 8);
+        if (!DIMG) da[j][c4] = *(const u32x4*)(dobase + (long long)qd * D + c4 * 8);
         oa[j][c4] = *(const u32x4*)(obase + (long long)qd * D + c4 * 8);
       }
     }
   }
-  rows_store<NCH>(qimg, rq, SP, first);
-  rows_store<NCH>(kimg, rk, SP, first);
-  rows_store<NCH>(doimg, rd, SP, first);
+  rows_store<NCH>(qimg, rq, IR, first);
+  rows_store<NCH>(kimg, rk, IR, first);
+  rows_store<NCH>(doimg, rd, IR, first);
+  if (DIMG) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      const int qd = first + 128 * j;
+      if (qd < IR) {
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) da[j][c4] = *(const u32x4*)(doimg + hd_img_off(qd, c4));
+      }
+    }
+  }
 #pragma unroll
   for (int j = 0; j < NQ; ++j) {
     const int qd = first + 128 * j;
-    if (qd < SP) {
+    if (qd < IR) {
       float dsum = 0.f;
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) {
@@ -339,6 +375,7 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
   }
   const int nkt = (S + 15) >> 4;        // (run-time also when NKTX names it: the pair loop below keeps one basic block per pair --
                                         //  with a constant count the scheduler hoisted every pair's operand reads and spilled 31 registers)
+  if (IR < SP) __builtin_assume(nkt <= IR / 16);   // launch_bwd: S <= IR, so the accumulators of query tiles >= IR / 16 are dead registers
   uint32_t seed_lo = 0, seed_hi = 0;
   if (dc.thresh) { seed_lo = st->seed_lo; seed_hi = st->seed_hi; }
   const uint32_t headidx = (uint32_t)((b * H + h) * S);
@@ -359,10 +396,17 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
   // (compile-time flag), so neither copy carries a branch inside its unrolled blocks.
   FR<T> vnext = hd_frag_global<T>(vbase + (long long)(role * 16 + l15) * ld + g * 8, role * 16 + l15 < S && role < nkt);
   const int nfull = TAIL ? NKTX - 1 : nkt;
-#define EG_BWD1_ARGS S, nkt, valid, lane, kimg, qimg, doimg, lsel, dl, pimg, simg, vbase, ld, vnext, accq, dc, seed_lo, seed_hi, headidx, Sp2, dqkv, bk, h, D
-  for (int kt = role; kt < nfull; kt += 2) bwd1_key_tile<T, SP, NKTX, false>(kt, EG_BWD1_ARGS);
-  if (TAIL && role == ((NKTX - 1) & 1)) bwd1_key_tile<T, SP, NKTX, true>(NKTX - 1, EG_BWD1_ARGS);
+#define EG_BWD1_ARGS(lane) S, nkt, valid, lane, kimg, qimg, doimg, lsel, dl, pimg, simg, vbase, ld, vnext, accq, dc, seed_lo, seed_hi, headidx, Sp2, dqkv, bk, h, D
+  for (int kt = role; kt < nfull; kt += 2) bwd1_key_tile<T, SP, IR, NKTX, false>(kt, EG_BWD1_ARGS(lane));
+  // With 128 registers (IR < SP) whatever the tail tile and the dQ exchange derive from the lane id is formed behind the loop: the
+  // compiler computed those addresses in front of it and carried them across it in scratch memory.
+  int lane_t = lane;
+  if (IR < SP) asm volatile("" : "+v"(lane_t));
+  if (TAIL && role == ((NKTX - 1) & 1)) bwd1_key_tile<T, SP, IR, NKTX, true>(NKTX - 1, EG_BWD1_ARGS(lane_t));
 #undef EG_BWD1_ARGS
+  int lane_x = lane;
+  if (IR < SP) asm volatile("" : "+v"(lane_x));
+  const int l15x = lane_x & 15, gx = lane_x >> 4;
 
   // ---- dQ: role 0 finishes query tiles [0, NKT/2), role 1 the rest; each hands the other its partial of the other's tiles ----
   __syncthreads();                                            // the images are dead: they carry the partials
@@ -377,7 +421,7 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
       // kernel (784 us against 421 us per step when that happened to the S = 65 instantiation).
       f32x4 lo = accq[i][dt], hi = accq[NKT / 2 + i][dt];
       asm volatile("" : "+v"(lo), "+v"(hi));
-      xbuf[((role * (NKT / 2) + i) * 2 + dt) * 64 + lane] = role ? lo : hi;
+      xbuf[((role * (NKT / 2) + i) * 2 + dt) * 64 + lane_x] = role ? lo : hi;
     }
     (void)qt;
   }
@@ -385,17 +429,17 @@ __global__ __launch_bounds__(256, SP <= 96 ? 3 : 2) void attn_bwd1_kernel(const 
 #pragma unroll
   for (int i = 0; i < NKT / 2; ++i) {
     const int qt = role * (NKT / 2) + i;
-    const int q = qt * 16 + l15;
+    const int q = qt * 16 + l15x;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
-      const f32x4 other = xbuf[(((1 - role) * (NKT / 2) + i) * 2 + dt) * 64 + lane];
+      const f32x4 other = xbuf[(((1 - role) * (NKT / 2) + i) * 2 + dt) * 64 + lane_x];
       f32x4 lo = accq[i][dt], hi = accq[NKT / 2 + i][dt];
       asm volatile("" : "+v"(lo), "+v"(hi));
       const f32x4 mine = role ? hi : lo;
       const f32x4 tot = role ? other + mine : mine + other;    // fixed order: role 0's partial + role 1's partial
       if (q < S && valid) {
         float v[4] = {tot[0] * HD_SCALE, tot[1] * HD_SCALE, tot[2] * HD_SCALE, tot[3] * HD_SCALE};
-        store4(dqkv + ((long long)b * S + q) * ld + h * 32 + 16 * dt + 4 * g, v);
+        store4(dqkv + ((long long)b * S + q) * ld + h * 32 + 16 * dt + 4 * gx, v);
       }
     }
   }
@@ -531,13 +575,16 @@ void launch_bwd(const void* qkv, const void* ctx, const void* dctx, const float*
   // kernel it replaced: cfg3 step 3.87 -> 3.78 ms, cfg5 5.63 -> 5.54 ms (SP = 96); once accq stayed in registers (see the kernel; with
   // 272 B of scratch per lane it had lost at SP = 128) a5 (SP = 128) 7.38 -> 7.04 ms, a5c32 (SP = 160, 186 registers, two waves per
   // SIMD) 14.49 -> 13.84 ms.
-  constexpr int lds1 = 2 * (3 * SP * 64 + 2 * SP * 4 + 2 * 2 * 32 * 32);
+  // Windows of up to 80 tokens (the S = 65 of the benchmark, the S = 73 of cfg5 / mm5) take the 80-row images: four workgroups per CU.
   if (SP == 96 && S == 65)           // class token + 64 positions: exact tile count, single-key tail tile
-    eg_launch_lds<attn_bwd1_kernel<T, 96, 5, true>, lds1>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx, (const T*)dctx, lse,
-                                                          (T*)dqkv, NB, S, H, kv_shift, dc, st);
+    eg_launch_lds<attn_bwd1_kernel<T, 96, 5, true, 80>, bwd1_lds(80)>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx,
+                                                                      (const T*)dctx, lse, (T*)dqkv, NB, S, H, kv_shift, dc, st);
+  else if (SP == 96 && S <= 80)
+    eg_launch_lds<attn_bwd1_kernel<T, 96, 0, false, 80>, bwd1_lds(80)>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx,
+                                                                       (const T*)dctx, lse, (T*)dqkv, NB, S, H, kv_shift, dc, st);
   else
-    eg_launch_lds<attn_bwd1_kernel<T, SP, 0, false>, lds1>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx, (const T*)dctx, lse,
-                                                           (T*)dqkv, NB, S, H, kv_shift, dc, st);
+    eg_launch_lds<attn_bwd1_kernel<T, SP, 0, false>, bwd1_lds(SP)>(dim3(nblk), dim3(256), s, (const T*)qkv, (const T*)ctx,
+                                                                   (const T*)dctx, lse, (T*)dqkv, NB, S, H, kv_shift, dc, st);
 }
 
 // the 16-bit kernels' instantiation for (dtype, S): f(type tag, SP tag), SP = the tile-padded capacity 96 / 128 / HD_MAX_S

@@ -50,6 +50,16 @@ __device__ __forceinline__ FR<T> hd_frag_tr(const char* img, int rbase, int dt, 
   s16x8 t = {part[0][0], part[0][1], part[0][2], part[0][3], part[1][0], part[1][1], part[1][2], part[1][3]};
   return __builtin_bit_cast(FR<T>, t);
 }
+// hd_frag_tr of an image that ends at row rbase + 16: the upper 16 rows are zero k-slots and are not read
+template <typename T>
+__device__ __forceinline__ FR<T> hd_frag_tr_lo(const char* img, int rbase, int dt, int lane) {
+  const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
+  const int row = rbase + 4 * g + qq;
+  const int off = row * 64 + ((dt ^ (g & 1)) << 5) + pp * 8;
+  const s16x4 part = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(img + off));
+  s16x8 t = {part[0], part[1], part[2], part[3], 0, 0, 0, 0};
+  return __builtin_bit_cast(FR<T>, t);
+}
 // two accumulator tiles (key / query tiles 2 n, 2 n + 1) -> the operand whose k-slots hd_frag_tr's map names
 template <typename T>
 __device__ __forceinline__ FR<T> hd_pack_frag(const f32x4& a, const f32x4& b) {
