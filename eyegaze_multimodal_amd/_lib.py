@@ -88,6 +88,14 @@ class RecordingRowsDesc(C.Structure):
                 ("n_rows", C.c_int32), ("C", C.c_int32), ("max_len", C.c_int32), ("_pad", C.c_int32)]
 
 
+class ImageBatchDesc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("off", C.c_void_p), ("npix", C.c_void_p), ("layout", C.c_void_p),
+                ("n_images", C.c_int32), ("max_pix", C.c_int32), ("elem", C.c_int32), ("normalize", C.c_int32)]
+
+
+IMAGE_ENTROPY_CHUNK = 8192      # EG_IMAGE_ENTROPY_CHUNK
+
+
 class PackEntry(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("rows", C.c_int32), ("cols", C.c_int32), ("ldd", C.c_int32),
                 ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32)]
@@ -169,6 +177,9 @@ SIGNATURES = {
     "eg_trial_pairs": [C.POINTER(RecordingRowsDesc), _P, _P, _P, _P, _L, _P, _I, _I, _P],
     "eg_trial_coherence_workspace_floats": [_I, _I],                 # returns int64_t: trial_coherence_workspace_floats() below
     "eg_trial_coherence": [C.POINTER(RecordingRowsDesc), _P, _L, _P, _I, _I, _P],
+    "eg_trial_spectral_entropy": [C.POINTER(RecordingRowsDesc), C.c_double, C.c_double, _P, _P, _P],
+    "eg_image_entropy_workspace_doubles": [_I, _I],                  # returns int64_t: image_entropy_workspace_doubles() below
+    "eg_image_entropy": [C.POINTER(ImageBatchDesc), C.c_double, _P, _L, _P, _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
@@ -305,6 +316,13 @@ def trial_coherence_workspace_floats(n_rows: int, max_len: int) -> int:
     l = lib()
     l.eg_trial_coherence_workspace_floats.restype = C.c_int64
     return int(l.eg_trial_coherence_workspace_floats(n_rows, max_len))
+
+
+def image_entropy_workspace_doubles(n_images: int, max_pix: int) -> int:
+    """Doubles of workspace eg_image_entropy needs (host only; -1: bad shape)"""
+    l = lib()
+    l.eg_image_entropy_workspace_doubles.restype = C.c_int64
+    return int(l.eg_image_entropy_workspace_doubles(n_images, max_pix))
 
 
 def exported_symbols():

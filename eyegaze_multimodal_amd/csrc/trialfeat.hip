@@ -1,6 +1,7 @@
 // Trial features of the hyperscanning extractor (2_Preprocessing/scripts/extract_eeg_features.py): Welch PSD and band energies,
 // the analytic signal of a band-filtered trial at any length, the pair sums of six connectivity metrics and the segment
-// coherence.  include/eyegaze_hip.h states the contracts; DESIGN.md §8m the layout, the numerics and the measurements.
+// coherence; and the spectral entropy of the entropy analysis (5_Metrics/entropy_calculators.py), which shares the
+// Welch loop.  include/eyegaze_hip.h states the contracts; DESIGN.md §8m the layout, the numerics and the measurements.
 #include <algorithm>
 
 #include "common.h"
@@ -54,14 +55,10 @@ struct BandBins {
   int k0[EG_TRIAL_MAX_BANDS], k1[EG_TRIAL_MAX_BANDS], n;
 };
 
-__global__ __launch_bounds__(256) void trial_welch_kernel(const eg_recording_rows_desc d, const double fs, const BandBins bb,
-                                                          float* __restrict__ psd, float* __restrict__ energy, int32_t* nonfinite) {
-  __shared__ cplx buf[NFFT], tw[NFFT / 2];
-  __shared__ double red[4];
-  __shared__ float ps[NBIN];
-  const int row = blockIdx.x, t = threadIdx.x, L = d.row_len[row];
-  if (L < NFFT || L > d.max_len) return;
-  const float* x = d.data + d.row_off[row];
+// scipy.signal.welch(x, fs, nperseg=256) of one row of L >= 256 samples by the whole block: thread t returns bin t's PSD in fp64,
+// not yet rounded (0 for t >= 129).  eg_trial_welch and eg_trial_spectral_entropy both run this loop.
+__device__ __forceinline__ double welch_row_bin(const float* __restrict__ x, const int L, const double fs, cplx* buf, cplx* tw, double* red) {
+  const int t = threadIdx.x;
   fft256_twiddles(tw);
   const double w = 0.5 - 0.5 * cospi(2.0 * t / NFFT);                   // periodic Hann
   const double scale = 1.0 / (fs * block_sum256(w * w, red));
@@ -77,9 +74,20 @@ __global__ __launch_bounds__(256) void trial_welch_kernel(const eg_recording_row
       acc += X.x * X.x + X.y * X.y;
     }
   }
+  double p = acc / nseg * scale;
+  if (t > 0 && t < NBIN - 1) p *= 2.0;
+  return p;
+}
+
+__global__ __launch_bounds__(256) void trial_welch_kernel(const eg_recording_rows_desc d, const double fs, const BandBins bb,
+                                                          float* __restrict__ psd, float* __restrict__ energy, int32_t* nonfinite) {
+  __shared__ cplx buf[NFFT], tw[NFFT / 2];
+  __shared__ double red[4];
+  __shared__ float ps[NBIN];
+  const int row = blockIdx.x, t = threadIdx.x, L = d.row_len[row];
+  if (L < NFFT || L > d.max_len) return;
+  const double p = welch_row_bin(d.data + d.row_off[row], L, fs, buf, tw, red);
   if (t < NBIN) {
-    double p = acc / nseg * scale;
-    if (t > 0 && t < NBIN - 1) p *= 2.0;
     const float pf = (float)p;
     psd[(long long)row * NBIN + t] = pf;
     ps[t] = pf;
@@ -91,6 +99,23 @@ __global__ __launch_bounds__(256) void trial_welch_kernel(const eg_recording_row
     for (int k = bb.k0[t]; k <= bb.k1[t]; ++k) s += (double)ps[k];
     energy[(long long)row * bb.n + t] = bb.k1[t] >= bb.k0[t] ? (float)(s / (bb.k1[t] - bb.k0[t] + 1)) : 0.f;
   }
+}
+
+// Spectral entropy (5_Metrics/entropy_calculators.py:323-344): the Shannon entropy in bits of the row's Welch PSD, from the fp64
+// bins BEFORE they are rounded.  q = |p| + eps, S = sum q, T = sum q ln q, H = (ln S - T / S) / ln 2; a bin with q == 0 (eps == 0)
+// adds nothing, as scipy's entr.  A NaN or Inf of the row reaches S and makes H NaN.
+__global__ __launch_bounds__(256) void trial_spectral_entropy_kernel(const eg_recording_rows_desc d, const double fs, const double eps,
+                                                                     float* __restrict__ psd, double* __restrict__ entropy) {
+  __shared__ cplx buf[NFFT], tw[NFFT / 2];
+  __shared__ double red[4];
+  const int row = blockIdx.x, t = threadIdx.x, L = d.row_len[row];
+  if (L < NFFT || L > d.max_len) return;
+  const double p = welch_row_bin(d.data + d.row_off[row], L, fs, buf, tw, red);
+  if (psd && t < NBIN) psd[(long long)row * NBIN + t] = (float)p;
+  const double q = t < NBIN ? fabs(p) + eps : 0.0;
+  const double S = block_sum256(q, red);
+  const double T = block_sum256(q > 0.0 || q != q ? q * log(q) : 0.0, red);
+  if (t == 0) entropy[row] = (log(S) - T / S) / 0.693147180559945309417232121458;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -465,12 +490,16 @@ __global__ __launch_bounds__(256) void trial_pair_finish_kernel(const eg_recordi
   out(6, s[3] == 0.0 && s[2] >= 0.0 ? 0.0 : atan2(s[3], s[2]));
 }
 
-int trial_desc_check(const char* who, const eg_recording_rows_desc* d) {
+// pairs: the rows are trials of two players (every entry point but the spectral entropy, whose rows are single recordings)
+int trial_desc_check(const char* who, const eg_recording_rows_desc* d, bool pairs = true) {
   EG_CHECK(d && d->data && d->row_off && d->row_len, "%s: null pointer", who);
   EG_CHECK(d->n_rows > 0, "%s: n_rows=%d must be > 0", who, d->n_rows);
   EG_CHECK(d->C > 0, "%s: C=%d must be > 0", who, d->C);
-  EG_CHECK(d->n_rows % (2 * (long long)d->C) == 0, "%s: n_rows=%d is no multiple of 2 C=%lld (two players per trial)", who, d->n_rows,
-           2 * (long long)d->C);
+  if (pairs)
+    EG_CHECK(d->n_rows % (2 * (long long)d->C) == 0, "%s: n_rows=%d is no multiple of 2 C=%lld (two players per trial)", who, d->n_rows,
+             2 * (long long)d->C);
+  else
+    EG_CHECK(d->n_rows % d->C == 0, "%s: n_rows=%d is no multiple of C=%d", who, d->n_rows, d->C);
   EG_CHECK(d->max_len >= EG_TRIAL_MIN_LEN && d->max_len <= EG_TRIAL_MAX_LEN, "%s: max_len=%d outside [%d, %d]", who, d->max_len,
            EG_TRIAL_MIN_LEN, EG_TRIAL_MAX_LEN);
   return 0;
@@ -499,6 +528,16 @@ extern "C" int eg_trial_welch(const eg_recording_rows_desc* d, double fs, const 
   }
   hipLaunchKernelGGL(trial_welch_kernel, dim3(d->n_rows), dim3(256), 0, (hipStream_t)stream, *d, fs, bb, psd, energy, nonfinite);
   EG_LAUNCH_CHECK("trial_welch");
+  return 0;
+}
+
+extern "C" int eg_trial_spectral_entropy(const eg_recording_rows_desc* d, double fs, double eps, float* psd, double* entropy, void* stream) {
+  if (trial_desc_check("eg_trial_spectral_entropy", d, false)) return 1;
+  EG_CHECK(entropy, "eg_trial_spectral_entropy: null pointer");
+  EG_CHECK(fs > 0.0, "eg_trial_spectral_entropy: fs=%g must be > 0", fs);
+  EG_CHECK(eps >= 0.0, "eg_trial_spectral_entropy: eps=%g must be >= 0", eps);
+  hipLaunchKernelGGL(trial_spectral_entropy_kernel, dim3(d->n_rows), dim3(256), 0, (hipStream_t)stream, *d, fs, eps, psd, entropy);
+  EG_LAUNCH_CHECK("trial_spectral_entropy");
   return 0;
 }
 

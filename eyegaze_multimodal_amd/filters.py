@@ -9,10 +9,10 @@ import numpy as np
 MAX_NCOEF = 17          # eg_recording_filtfilt's upper bound on len(b) == len(a)
 
 
-def butter_bandpass(order: int, low_hz: float, high_hz: float, fs: float):
+def butter_bandpass(order: int, low_hz: float, high_hz: float, fs: float, high_clamp: float = 0.99):
     """(b, a) float64, each 2 * order + 1 long, of the digital Butterworth band-pass [low_hz, high_hz] at sampling rate fs.
     The band edges are normalised as the reference does (preprocess_eeg_windows.py:119-121): low = low_hz / (fs / 2),
-    high = min(high_hz / (fs / 2), 0.99)."""
+    high = min(high_hz / (fs / 2), high_clamp); the entropy calculator clamps at 0.999 (entropy_calculators.py:273)."""
     if int(order) != order or order < 1:
         raise ValueError(f"butter_bandpass: order {order} must be an integer >= 1")
     order = int(order)
@@ -21,7 +21,7 @@ def butter_bandpass(order: int, low_hz: float, high_hz: float, fs: float):
     if not fs > 0:
         raise ValueError(f"butter_bandpass: sampling rate {fs} must be > 0")
     nyquist = fs / 2
-    low, high = low_hz / nyquist, min(high_hz / nyquist, 0.99)
+    low, high = low_hz / nyquist, min(high_hz / nyquist, high_clamp)
     if not low_hz > 0:
         raise ValueError(f"butter_bandpass: low edge {low_hz} Hz must be > 0")
     if not low < high:

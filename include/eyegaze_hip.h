@@ -226,6 +226,43 @@ int64_t eg_trial_coherence_workspace_floats(int n_rows, int max_len);
  * not rescaled.  Two launches: spectra per row, then one block per (trial, matrix, i). */
 int eg_trial_coherence(const eg_recording_rows_desc* d, float* workspace, int64_t workspace_capacity, float* con, int band,
                        int nbands, void* stream);
+/* Spectral entropy (5_Metrics/entropy_calculators.py:323-344) per row: eg_trial_welch's segment loop -- the same
+ * device function -- and, from the fp64 PSD BEFORE it is rounded to f32, q_k = |p_k| + eps, S = sum q_k, T = sum q_k ln q_k,
+ * entropy[row] = (ln S - T / S) / ln 2 in bits, a double; both sums through the fixed-order block sum; a bin with q_k == 0 (only
+ * where eps == 0) adds nothing.  eps is absolute (the calculator's 1e-10 on uV^2 / Hz).  psd [n_rows][129] (may be null) receives
+ * exactly eg_trial_welch's floats.  The rows are ANY channel rows: single recordings, any C (the descriptor's C only has to divide
+ * n_rows).  There is no flag: a NaN or Inf in a row makes that row's entropy NaN and touches no other row.  A row shorter than
+ * 256 or longer than max_len is skipped.  One launch, one block per row.  Refused on the host: null pointers (d, its data and
+ * tables, entropy), n_rows <= 0, C <= 0, n_rows % C != 0, max_len outside [256, 65536], fs <= 0, eps < 0. */
+int eg_trial_spectral_entropy(const eg_recording_rows_desc* d, double fs, double eps, float* psd, double* entropy, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spatial entropy of gaze heat-map images (5_Metrics/entropy_calculators.py:145-180) for a batch of ragged images
+ * in one call.  Every pointer of the descriptor is a DEVICE pointer; the descriptor itself is host memory.  The tables are
+ * trusted: whoever builds them proves that every image lies inside `data` (npix elements for grey, 3 npix for RGB, from element
+ * off) and starts on a 16-byte boundary (an image that does not is still computed, through narrow loads).
+ * All arithmetic is fp64.  Luminance g = (0.299 R + 0.587 G) + 0.114 B, every product and sum rounded on its own (numpy's
+ * bits); with normalize: q = |(g - min) / ((max - min) + 1e-10)| + eps over the image's own min and max, without: q = |g| + eps;
+ * S = sum q, T = sum q ln q (a pixel with q == 0 adds nothing), entropy[i] = (ln S - T / S) / ln 2 in bits.  A constant image
+ * gives log2(npix).  No atomics: a workgroup owns EG_IMAGE_ENTROPY_CHUNK consecutive pixels of one image; launch 1 writes per
+ * chunk (min, max), launch 2 folds its image's (min, max) in ascending order and writes per chunk (S, T), launch 3 adds an
+ * image's chunks in ascending order.  So an image alone and inside any batch gives the same bytes, as do two runs.
+ * An image with npix outside [1, max_pix] or a layout outside {0, 1, 2} is skipped on the device: its entropy is not written.
+ * Refused on the host, before any launch: null pointers, n_images <= 0, max_pix outside [1, 2^24], elem outside {0, 1}, eps < 0,
+ * a workspace below eg_image_entropy_workspace_doubles(n_images, max_pix).
+ * ------------------------------------------------------------------------------------------- */
+#define EG_IMAGE_ENTROPY_CHUNK 8192
+typedef struct eg_image_batch_desc {
+  const void* data;            /* every image's elements back to back; each image starts on a 16-byte boundary */
+  const int64_t* off;          /* [n_images] element offset */
+  const int32_t* npix;         /* [n_images] H * W */
+  const int32_t* layout;       /* [n_images] 0 grey (H, W), 1 RGB pixel-interleaved (H, W, 3), 2 RGB planar (3, H, W) */
+  int32_t n_images, max_pix, elem /* 0 uint8, 1 float64 */, normalize;
+} eg_image_batch_desc;
+/* Doubles of workspace eg_image_entropy needs: 4 per image and chunk of max_pix (host only; -1: bad shape). */
+int64_t eg_image_entropy_workspace_doubles(int n_images, int max_pix);
+int eg_image_entropy(const eg_image_batch_desc* d, double eps, double* workspace, int64_t workspace_capacity, double* entropy,
+                     void* stream);
 
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
