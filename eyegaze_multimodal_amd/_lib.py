@@ -96,6 +96,15 @@ class ImageBatchDesc(C.Structure):
 IMAGE_ENTROPY_CHUNK = 8192      # EG_IMAGE_ENTROPY_CHUNK
 
 
+class GazeResizeDesc(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("off", C.c_void_p), ("h", C.c_void_p), ("w", C.c_void_p), ("mid_off", C.c_void_p),
+                ("tabs", C.c_void_p), ("htab", C.c_void_p), ("vtab", C.c_void_p), ("sum_h", C.c_int64),
+                ("n_images", C.c_int32), ("max_h", C.c_int32), ("F", C.c_int32), ("W", C.c_int32)]
+
+
+GAZE_MAX_SIDE, GAZE_MIN_OUT, GAZE_MAX_OUT = 4096, 8, 512      # EG_GAZE_MAX_SIDE, EG_GAZE_MIN_OUT, EG_GAZE_MAX_OUT
+
+
 class PackEntry(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("rows", C.c_int32), ("cols", C.c_int32), ("ldd", C.c_int32),
                 ("mode", C.c_int32), ("blk0", C.c_int32), ("nblk", C.c_int32)]
@@ -180,6 +189,9 @@ SIGNATURES = {
     "eg_trial_spectral_entropy": [C.POINTER(RecordingRowsDesc), C.c_double, C.c_double, _P, _P, _P],
     "eg_image_entropy_workspace_doubles": [_I, _I],                  # returns int64_t: image_entropy_workspace_doubles() below
     "eg_image_entropy": [C.POINTER(ImageBatchDesc), C.c_double, _P, _L, _P, _P],
+    "eg_gaze_resize_workspace_bytes": [_I, _L, _I],                  # returns int64_t: gaze_resize_workspace_bytes() below
+    "eg_gaze_resize": [C.POINTER(GazeResizeDesc), _P, _L, _P, _P],
+    "eg_gaze_batch": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _U, _U, _F, _F, _F, _P, _P, _P, _P, _P, _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
@@ -323,6 +335,13 @@ def image_entropy_workspace_doubles(n_images: int, max_pix: int) -> int:
     l = lib()
     l.eg_image_entropy_workspace_doubles.restype = C.c_int64
     return int(l.eg_image_entropy_workspace_doubles(n_images, max_pix))
+
+
+def gaze_resize_workspace_bytes(n_images: int, sum_h: int, W: int) -> int:
+    """Bytes of workspace eg_gaze_resize needs for n_images images of sum_h rows in all (host only; -1: bad shape)"""
+    l = lib()
+    l.eg_gaze_resize_workspace_bytes.restype = C.c_int64
+    return int(l.eg_gaze_resize_workspace_bytes(n_images, sum_h, W))
 
 
 def exported_symbols():

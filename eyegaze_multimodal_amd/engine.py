@@ -39,6 +39,8 @@ from ._lib import EG_BF16, EG_F16, EG_F32, GemmDesc, GemmTNDesc, StepState, call
 SITE_CONV0, SITE_CONV1, SITE_SPEC, SITE_IBSTOK, SITE_IBSGEN, SITE_CLS, SITE_IBSCLS = 1, 2, 3, 4, 5, 6, 7
 # eg_window_augment's own sites (EG_SITE_AUG_* of include/eyegaze_hip.h; the kernel names them, no call passes them)
 SITE_AUG_NOISE_R, SITE_AUG_NOISE_T, SITE_AUG_CHAN, SITE_AUG_TIME = 8, 9, 10, 11
+# eg_gaze_batch's own sites (EG_SITE_IMG_*; gaze.py); with them every site below 16 is taken
+SITE_IMG_FLIP, SITE_IMG_BRIGHT, SITE_IMG_CONTRAST, SITE_IMG_ORDER = 12, 13, 14, 15
 
 
 @dataclasses.dataclass(frozen=True)

@@ -22,6 +22,9 @@ rank r trains on samples r::world of the global batch; the three flat gradient b
 ddp.MultimodalReducers on one side stream (fusion scalars first, the image branch under the EEG backward, the EEG encoder's
 buckets as its backward releases them), 1/world is folded into eg_clip_coef / eg_adamw_group, and the overflow flag is made
 collective before any AdamW kernel reads it, so an fp16 overflow on ONE rank skips the step on EVERY rank.
+
+Real data: `python -m eyegaze_multimodal_amd.train_multimodal_fuzzy_fusion --config YAML` (main, below) trains on gaze heat-map files
+and EEG recordings through gaze.ResidentMultimodal -- both modalities resident on the device, two launches per batch.
 """
 from __future__ import annotations
 
@@ -313,3 +316,173 @@ def build_from_config(config: Dict, device) -> MultimodalTrainer:
                              lambda_reg=t.get("lambda_reg", 0.1), temp_reg_min=fz.get("temp_reg_min", 0.5),
                              temp_reg_max=fz.get("temp_reg_max", 5.0), warmup_steps=t.get("warmup_epochs", 0) * spe,
                              total_steps=t["epochs"] * spe, seed=config.get("system", {}).get("seed", 42))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Real data: python -m eyegaze_multimodal_amd.train_multimodal_fuzzy_fusion --config YAML
+# The reference's main (:604-900) on its config's keys, with its MultimodalDataset (1_Data/processed/multimodal_dataset.py) replaced
+# by two device-resident stores: data.ResidentWindows for the EEG windows and gaze.GazeImageStore for the images, walked together
+# by gaze.ResidentMultimodal -- two launches per batch, nothing of a batch crosses the host.
+# ------------------------------------------------------------------------------------------------------------------
+IGNORED_KEYS = (("wandb", "wandb logging"), ("resume", "resuming from a checkpoint"),
+                ("gaze_encoder.model_name", "the timm ViT (the image branch is the in-tree GazeCNNEncoder)"),
+                ("gaze_encoder.pretrained", "pretrained ViT weights"), ("gaze_encoder.checkpoint_path", "a pretrained gaze checkpoint"),
+                ("eeg_encoder.checkpoint_path", "a pretrained EEG checkpoint"))
+
+
+def multimodal_items(items, image_base_path, eeg_base_path, image_ext: str = ".jpg"):
+    """The reference's sample filter (multimodal_dataset.py:100-112): the items whose two images `<player>.jpg` and two recordings
+    `<player>.csv` all exist, in their order"""
+    from pathlib import Path
+    ib, eb = Path(image_base_path), Path(eeg_base_path)
+    return [it for it in items if all((ib / f"{it[p]}{image_ext}").exists() and (eb / f"{it[p]}.csv").exists() for p in ("player1", "player2"))]
+
+
+def image_tables(indices, image_base_path, image_ext: str = ".jpg"):
+    """Recording-store indices (data.build_recording_store; one per split) -> (paths, [pair_img per index]): the distinct image
+    files of all their pairs in first-seen order, and per index the int32 [n_pairs, 2] store numbers of every pair's two players'
+    images -- GazeImageStore.from_files(paths) and ResidentMultimodal's pair_img.  A pair's players are read from its first window."""
+    from pathlib import Path
+    base = Path(image_base_path)
+    number, paths, tables = {}, [], []
+    for index in indices:
+        tab = np.full((len(index["pairs"]), 2), -1, dtype=np.int32)
+        for w, p in zip(index["windows"], index["window_pair"]):
+            if tab[p, 0] >= 0:
+                continue
+            for pl, key in enumerate(("player1", "player2")):
+                name = w[key]
+                if name not in number:
+                    number[name] = len(paths)
+                    paths.append(base / f"{name}{image_ext}")
+                tab[p, pl] = number[name]
+        if (tab < 0).any():
+            raise ValueError(f"recording store: pair {int(np.argmax((tab < 0).any(axis=1)))} has no window")
+        tables.append(tab)
+    return paths, tables
+
+
+def check_image_size(size: int) -> int:
+    """data.image_size -> F = W; ImageEngine's shape rule and the image store's range, restated"""
+    size = int(size)
+    if size % 8 or (size // 2) % 4 or not 8 <= size <= 512:
+        raise ValueError(f"data.image_size = {size}: the image encoder needs F % 8 == 0 and floor(W / 2) % 4 == 0 with F = W = image_size "
+                         "(a multiple of 8), and the image store serves 8 to 512")
+    return size
+
+
+def checkpoint_dict(trainer: MultimodalTrainer, epoch: int, best_metric: float, config: Dict) -> Dict:
+    """The key set of the reference's save_checkpoint (:246-254).  The optimiser is the trainer's own AdamW: its state is the two
+    moment buffers of every parameter set; the scheduler is a function of the step number; the scaler lives in eg_step_state."""
+    scaler = None
+    eng = next(iter(trainer.model.eeg_encoder._engines.values()), None) if hasattr(trainer.model.eeg_encoder, "_engines") else None
+    if eng is not None and getattr(eng, "scaler_on", False):
+        st = eng.read_state()
+        scaler = {"scale": float(st.loss_scale), "_growth_tracker": int(st.good_steps)}
+    return {"epoch": epoch, "model_state_dict": trainer.model.state_dict(),
+            "optimizer_state_dict": {k: {"exp_avg": m, "exp_avg_sq": v} for k, (m, v) in trainer.state.items()},
+            "scheduler_state_dict": {"last_epoch": trainer.step_no, "warmup_steps": trainer.warmup_steps, "total_steps": trainer.total_steps},
+            "scaler_state_dict": scaler, "best_metric": best_metric, "config": config}
+
+
+def _lookup(config: Dict, dotted: str):
+    node = config
+    for k in dotted.split("."):
+        if not hasattr(node, "keys") or k not in node:
+            return None
+        node = node[k]
+    return node
+
+
+def build_loaders(config: Dict, device, out_dir):
+    """config -> (train loader, validation loader, GazeImageStore): train_art's item split and recording-store preparation over
+    the items that have all four files, one image store over the distinct images, one ResidentMultimodal per split (the training
+    one with training.image_augmentation, the validation one with none)."""
+    from pathlib import Path
+    import json
+    from .data import ResidentWindows, build_recording_store
+    from .gaze import GazeAugmentation, GazeImageStore, ResidentMultimodal
+    from .train_art import _prepare_windows, shard_fingerprint
+    d, t = config["data"], config["training"]
+    size = check_image_size(d.get("image_size", 224))
+    ext = d.get("image_ext", ".jpg")
+
+    def build(its, path):
+        kept = multimodal_items(its, d["image_base_path"], d["eeg_base_path"], ext)
+        idx = build_recording_store(kept, d["eeg_base_path"], d["label2id"], path, d["window_size"], d["stride"])
+        return f"{len(kept)} with both images and both recordings, {idx['count']} windows over {len(idx['pairs'])} resident recording pairs"
+
+    kind = f":multimodal:{d['image_base_path']}:{ext}"
+    dirs = _prepare_windows(config, Path(out_dir) / "recording_store", 0, 1, 24 * 3600.0, shard_fingerprint(config) + kind, build,
+                            "recording store")
+    bs, pre = t["batch_size"], d.get("enable_preprocessing", False)
+    train_eeg = ResidentWindows(dirs["train"], bs, device, shuffle=True, seed=d["random_seed"], preprocessing=pre)
+    val_eeg = ResidentWindows(dirs["test"], bs, device, preprocessing=pre)
+    paths, (train_tab, val_tab) = image_tables([json.loads((dirs[s] / "index.json").read_text()) for s in ("train", "test")],
+                                               d["image_base_path"], ext)
+    images = GazeImageStore.from_files(paths, size, device)
+    return (ResidentMultimodal(train_eeg, images, train_tab, GazeAugmentation.from_config(config)),
+            ResidentMultimodal(val_eeg, images, val_tab, None), images)
+
+
+def main(argv=None, history: Optional[list] = None):
+    """history: a list that receives every epoch's metrics dict"""
+    import argparse
+    import copy
+    import logging
+    from pathlib import Path
+    from .train_art import load_config
+    ap = argparse.ArgumentParser(description="Train the multimodal fuzzy-fusion model (MI355X HIP engines) on gaze images and EEG recordings")
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--resume", type=str, default=None, help="ignored: resuming is not implemented")
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    log = logging.getLogger(__name__)
+    config = load_config(args.config)
+    for dotted, what in IGNORED_KEYS:
+        v = _lookup(config, dotted)
+        if dotted == "resume" and args.resume:
+            v = {"enabled": True}
+        if v and not (hasattr(v, "keys") and not v.get("enabled", False)):
+            log.info("config key %s is ignored: %s is not part of this trainer", dotted, what)
+    if not torch.cuda.is_available():
+        raise SystemExit("train_multimodal_fuzzy_fusion (HIP) needs an MI355X: there is no CPU fallback")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    out_dir = Path(_lookup(config, "checkpoint.save_dir") or "runs/multimodal_fuzzy_fusion") / (config.get("fusion") or {}).get("mode", "full")
+    out_dir.mkdir(parents=True, exist_ok=True)
+    train_ld, val_ld, images = build_loaders(config, device, out_dir)
+    log.info("%d training and %d validation windows, %d distinct images of %dx%d resident on %s", train_ld.eeg.n, val_ld.eeg.n,
+             len(images), images.F, images.W, device)
+    if len(train_ld) == 0 or len(val_ld) == 0:
+        raise SystemExit("no windows: check data.image_base_path, data.eeg_base_path and data.metadata_path")
+    run = copy.deepcopy(config)
+    run["training"]["steps_per_epoch"] = len(train_ld)
+    run["data"].setdefault("num_classes", (config.get("model") or {}).get("num_classes", 3))
+    if run["eeg_encoder"]["in_channels"] != train_ld.eeg.C:
+        raise SystemExit(f"eeg_encoder.in_channels = {run['eeg_encoder']['in_channels']}, the recordings have {train_ld.eeg.C} channels")
+    trainer = build_from_config(run, device)
+    epochs, best = int(config["training"]["epochs"]), -math.inf
+    for epoch in range(epochs):
+        train_ld.set_epoch(epoch)
+        sums, nb = {}, 0
+        for batch in train_ld:
+            out = trainer.train_step(*batch)
+            for k in ("loss", "loss_ce", "loss_aux_img", "loss_aux_eeg", "loss_reg"):
+                sums[k] = sums.get(k, 0.0) + out[k].float()
+            nb += 1
+        metrics = {f"train_{k}": float(v) / max(nb, 1) for k, v in sums.items()}
+        metrics.update({f"val_{k}": v for k, v in trainer.evaluate(val_ld).items()})
+        metrics["epoch"] = epoch + 1
+        if history is not None:
+            history.append(metrics)
+        log.info(" ".join(f"{k}: {v:.4f}" for k, v in metrics.items() if k != "epoch") + f" (epoch {epoch + 1}/{epochs})")
+        if metrics["val_f1"] > best:
+            best = metrics["val_f1"]
+            torch.save(checkpoint_dict(trainer, epoch, best, config), out_dir / "best_model.pt")
+            log.info("New best val_f1: %.4f, saved %s", best, out_dir / "best_model.pt")
+    return best
+
+
+if __name__ == "__main__":
+    main()

@@ -264,6 +264,79 @@ int64_t eg_image_entropy_workspace_doubles(int n_images, int max_pix);
 int eg_image_entropy(const eg_image_batch_desc* d, double eps, double* workspace, int64_t workspace_capacity, double* entropy,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaze heat-map images as the multimodal trainer's input (1_Data/processed/multimodal_dataset.py:67-83): resized
+ * once into a uint8 store, then one launch per training batch.  All of it is integer or table arithmetic and bit-exact.
+ *
+ * eg_gaze_resize: n_images pixel-interleaved (h, w, 3) uint8 images back to back in `data`, image i at BYTE offset off[i], ->
+ * store [n_images, F, W, 3] uint8, the bytes of Pillow's Image.resize((W, F), BILINEAR): its antialiased two-pass resample,
+ * horizontally into a uint8 intermediate (h, W, 3) in the workspace (at byte offset mid_off[i]), then vertically.  One axis
+ * (in -> out) is a table of out rows (xmin, count, k[ksize]) built by the host in fp64 (gaze.resize_tables):
+ *   scale = in / out, fscale = max(scale, 1), support = fscale, ksize = 2 ceil(support) + 1, center = (xx + 0.5) scale,
+ *   xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in), count = xmax - xmin,
+ *   w[x] = max(0, 1 - |(x + xmin - center + 0.5) / fscale|) divided by their sequential sum, k[x] = int(0.5 + w[x] 2^22)
+ * and a pixel is clip((2^21 + sum_x src[xmin + x] k[x]) >> 22, 0, 255) in 32-bit integers.  A table lies at 32-bit word htab[i]
+ * (horizontal, w[i] -> W) or vtab[i] (vertical, h[i] -> F) of `tabs` as [0] ksize, [1 .. out] xmin, [1 + out .. 2 out] count, then
+ * k [out][ksize].  Two launches, no atomics: the horizontal pass stages a source row in LDS once by 16-byte loads and runs its
+ * threads over (x_out, channel); the vertical pass runs its threads over 16, 4 or 1 consecutive bytes of an output row (the widest
+ * that divides W * 3) and loops over the taps' rows.  An image alone and inside any batch gives the same bytes.
+ * Served: 1 <= h, w <= EG_GAZE_MAX_SIDE, EG_GAZE_MIN_OUT <= F, W <= EG_GAZE_MAX_OUT.  An image whose h or w is outside is skipped
+ * on the device: its store rows are not written.  Every pointer of the descriptor is a DEVICE pointer; the descriptor itself is
+ * host memory.  The tables are trusted (gaze.validate_resize_tables, gaze.GazeImageStore prove them): every image inside `data`,
+ * off[i] and mid_off[i] multiples of 16 with `data` readable up to the next multiple of 16 behind every image, mid_off the running
+ * sum of 3 W h[i] rounded up to 16, 0 <= xmin, xmin + count <= in, count <= ksize.  max_h only sizes the grid; sum_h is the sum of
+ * the heights.  Refused on the host, before any launch: null pointers, n_images <= 0, F / W / max_h outside the served range, a
+ * sum_h that no n_images heights give, a workspace below eg_gaze_resize_workspace_bytes(n_images, sum_h, W), data / workspace /
+ * store off a 16-byte boundary.
+ * ------------------------------------------------------------------------------------------- */
+#define EG_GAZE_MAX_SIDE 4096
+#define EG_GAZE_MIN_OUT 8
+#define EG_GAZE_MAX_OUT 512
+typedef struct eg_gaze_resize_desc {
+  const uint8_t* data;
+  const int64_t* off;          /* [n_images] byte offset of the image, a multiple of 16 */
+  const int32_t* h;            /* [n_images] */
+  const int32_t* w;            /* [n_images] */
+  const int64_t* mid_off;      /* [n_images] byte offset of the image's (h, W, 3) intermediate in the workspace, a multiple of 16 */
+  const int32_t* tabs;         /* every distinct axis table */
+  const int64_t* htab;         /* [n_images] word offset in tabs of the table w[i] -> W */
+  const int64_t* vtab;         /* [n_images] word offset in tabs of the table h[i] -> F */
+  int64_t sum_h;
+  int32_t n_images, max_h, F, W;
+} eg_gaze_resize_desc;
+/* Bytes of workspace eg_gaze_resize needs: 3 W sum_h + 16 n_images (host only; -1: n_images <= 0, sum_h outside
+ * [n_images, 4096 n_images], W outside the served range). */
+int64_t eg_gaze_resize_workspace_bytes(int n_images, int64_t sum_h, int W);
+int eg_gaze_resize(const eg_gaze_resize_desc* d, uint8_t* workspace, int64_t workspace_bytes, uint8_t* store, void* stream);
+
+/* One training batch out of the store, in ONE launch, addressed as eg_window_gather addresses its windows: sample j of the batch is
+ * window w = order[first + j], and its player pl reads image store[pair_img[2 win_pair[w] + pl]] ([F, W, 3] uint8).  Outputs:
+ * img1 / img2 [n, F, W] f32 (player 1 / 2; what ImageEngine.forward takes) and, unless null, rgb1 / rgb2 [n, 3, F, W] f32 (the
+ * reference's own tensors; both or neither).
+ *   rgb[c][y][x] = norm[c][v]      norm [3][256] f32 (device), filled by the host with (float32(v) / 255 - mean_c) / std_c in torch
+ *                                  fp32 operations (gaze.normalise_table): ToTensor followed by Normalize, exact by construction
+ *   img[y][x]    = ((r + g) + b) / 3.0f, the division correctly rounded: tensor.mean(dim=0)
+ * Augmentation runs iff hflip_p, brightness, contrast are not all 0 (or factors is given), each (j, pl) on its own, on the uint8
+ * pixels v before the table, from counter i = 2 (first + j) + pl and H(site) = eg_hash(seed_lo, seed_hi, site, i) of
+ * csrc/common.h, u(site) = (H(site) >> 8) 2^-24:
+ *   flip (x mirrored) iff u(IMG_FLIP) < hflip_p;  fb = (1 - brightness) + (2 brightness) u(IMG_BRIGHT), fc likewise from contrast and
+ *   u(IMG_CONTRAST), every operation a rounded fp32 one;  brightness goes first iff H(IMG_ORDER) >> 31 == 0
+ *   brightness: v' = uint8(trunc(clip(float32(v) fb, 0, 255)))
+ *   contrast:   v' = uint8(trunc(clip(m + fc (float32(v) - m), 0, 255))), product and sum rounded separately (no fused multiply-
+ *               add); m = int(mean_L + 0.5), mean_L the fp64 mean over the image AS IT STANDS when contrast is applied of
+ *               L = (19595 R + 38470 G + 7471 B + 32768) >> 16 (an integer sum: its order is free)
+ * These are PIL.ImageEnhance.Brightness / Contrast on the resized image, byte for byte.  factors (device, [2 n][4] f32, may be
+ * null) replaces the draws of image 2 j + pl by (flip != 0, fb, fc, brightness first != 0): it exists for parity tests against
+ * Pillow at given factors, no product path passes it.  One workgroup per (j, pl); with contrast the image is read twice (luminance
+ * sum, then the write).  The tables are trusted (gaze.GazeImageStore.batch validates pair_img; order and win_pair are
+ * ResidentWindows'); an image index outside [0, n_images) is skipped on the device.  Refused on the host: null pointers (rgb* and
+ * factors may be null), n <= 0, n_images <= 0, F / W outside the served range, first < 0 or first + n > order_len, hflip_p outside
+ * [0, 1], brightness or contrast outside [0, 1) or not finite, one of rgb1 / rgb2 without the other. */
+int eg_gaze_batch(const uint8_t* store, int n_images, int F, int W, const int32_t* pair_img, const int32_t* win_pair,
+                  const int32_t* order, int order_len, int first, int n, const float* norm, uint32_t seed_lo, uint32_t seed_hi,
+                  float hflip_p, float brightness, float contrast, const float* factors, float* img1, float* img2, float* rgb1,
+                  float* rgb2, void* stream);
+
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
  * pl = 0 for buffer 1 and 1 for buffer 2.  Every draw is counter-based: H(site, i) = eg_hash(state->seed_lo, state->seed_hi,
@@ -286,6 +359,10 @@ int eg_image_entropy(const eg_image_batch_desc* d, double eps, double* workspace
 #define EG_SITE_AUG_NOISE_T 9
 #define EG_SITE_AUG_CHAN    10
 #define EG_SITE_AUG_TIME    11
+#define EG_SITE_IMG_FLIP     12  /* eg_gaze_batch's draws (above); 12-15 were the last free sites below 16 */
+#define EG_SITE_IMG_BRIGHT   13
+#define EG_SITE_IMG_CONTRAST 14
+#define EG_SITE_IMG_ORDER    15
 int eg_window_augment(const float* in1, const float* in2, float* out1, float* out2, int N, int C, int T,
                       float noise_std, float chan_drop_p, int n_masks, int mask_max_len,
                       const eg_step_state* state, void* stream);
