@@ -17,6 +17,11 @@
 //     tiles over K = 256), its epilogue writes the 16-bit chunk into one of TWO 20 KB LDS buffers (one barrier per chunk), from
 //     where (a) all threads stream it to HBM as whole 256-B row segments and (b) product 2 reads it back as the B operand of
 //     the wave's 80 x 64 part of C (5 x 4 accumulator tiles that live in registers across all chunks);
+//   * the loop is SKEWED by one phase.  Per wave:  product 1 (0), epilogue 1 (0);  then for c = 1 .. nch - 1:  barrier,
+//     product 1 (c) with the H store of chunk c - 1 spread over its k-steps, { epilogue 1 (c) BESIDE product 2 (c - 1) };  then
+//     barrier, H store (nch - 1), product 2 (nch - 1), barrier, epilogue 2.  Epilogue 1 is vector work only, product 2 a chain of
+//     LDS reads and MFMAs that leaves most issue slots empty; they touch different accumulators and different halves of the chunk
+//     image, and in one scheduling region per tile the MFMAs run under the hash / pack arithmetic;
 //   * WEIGHTS NEVER TOUCH LDS: a wave's W1 / W2 fragments (pre-packed in fragment order, rt_frag_elem: one contiguous 1-KB read each,
 //     L2-resident, 1 MB per layer) go straight into registers through rolling rings four / two k-steps ahead, so the LDS pipe only carries
 //     the activation fragments: 0.5 KB per MFMA in product 1, 0.25 KB in product 2 -- below the 0.5 KB / MFMA at which LDS and
@@ -43,6 +48,18 @@ constexpr int F_XT = RT_TILEB;                // 40,960 B
 constexpr int F_HT = FR * FC * 2;             // 20,480 B
 constexpr int F_LDS = F_XT + 2 * F_HT;        // 81,920 B = half the LDS of a CU
 
+// The merged phase's pinned interleave for one tile of epilogue 1 and its share of a k-step's MFMAs: LEAD vector instructions
+// first (they cover the latency of the fragment reads), then PER vector instructions behind each MFMA.
+template <int LEAD, int PER>
+__device__ __forceinline__ void ffn_pin() {
+  __builtin_amdgcn_sched_group_barrier(0x2, LEAD, 0);
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x2, PER, 0);
+  }
+}
+
 template <typename T>
 struct FfnArgs {
   const T* A; const T* W1; const T* W2; T* H; T* C; const float* bias1; const float* bias2; const T* gate; const T* residual;
@@ -68,7 +85,7 @@ struct FfnArgs {
 //   xt [0, 40 KB)        dy1 rows (epilogue 2) -> dyo rows in place (step 2) -> A operand of step 3
 //   hb [0, 17 KB)        epilogue 2's four images; then [0, 16 KB) the gain / bias sums, [16 KB, 33 KB) step 4's four images
 struct FfnNoTail {};
-template <typename T, int GATE, int BOUT, int EPI, bool LNF = false, bool KEEP = true, bool TAIL = false>
+template <typename T, int GATE, int BOUT, int EPI, bool LNF = false, bool KEEP = true, bool TAIL = false, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::conditional_t<TAIL, LnProjArgs<T>, FfnNoTail> q) {
   static_assert(!TAIL || (GATE == 2 && BOUT == 0 && EPI == 0 && !LNF && KEEP), "the norm-1 tail follows the backward form only");
   typedef typename H16<T>::frag frag;
@@ -80,6 +97,10 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::co
   const int l15 = lane & 15, g4 = lane >> 4;
   const int m0 = blockIdx.x * FR;
   const int nch = p.F / FC;
+  // The stored rows of chunk c - 1 leave under product 1 (c), one 16-B piece per thread behind five of its k-steps, instead of in a
+  // phase of their own behind the barrier -- where the registers allow it: the run-time epilogue (EPI = 4) and the row gate
+  // (GATE = 1) have none to spare and keep the store phase.
+  constexpr bool SPREAD = KEEP && EPI != 4 && GATE != 1;
 
   // ---- A tile (rows beyond M repeat row M - 1) ----
 #pragma unroll
@@ -108,8 +129,6 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::co
   };
 #pragma unroll
   for (int s = 0; s < 4; ++s) req_w1(0, s, s);
-#pragma unroll
-  for (int s = 0; s < 2; ++s) req_w2(0, s, s);
 
   f32x4 acc2[5][4];
 #pragma unroll
@@ -147,32 +166,47 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::co
     if (nch > 1) gnext1 = bits_p[256];
   }
   const int rbase = l15;                                     // row of tile i within the workgroup: rbase + 16 i
-  const int sw7 = rt_swz(l15);
-  // epilogue-1 lane constants: byte offset of this lane's 8-B slot (row l15, hidden column 32 wn + 16 j + 4 g4 of the chunk) in the
+  // epilogue-1 lane constants, formed per chunk behind an opaque lane id (not carried across the loop: the merged phase has no
+  // register to spare): byte offset of this lane's 8-B slot (row l15, hidden column 32 wn + 16 j + 4 g4 of the chunk) in the
   // swizzled chunk image -- tile row i adds the immediate 4096 i -- and the dropout PAIR index of (row m0 + l15, column 32 wn + 4 g4)
-  int ha[2];
+  struct E1Lane { int ha[2]; uint32_t pairc; };
+  auto e1_lane = [&](int c, int l15o, int g4o) __attribute__((always_inline)) {
+    E1Lane e;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int hcol = 32 * wn + 16 * j + 4 * g4;
-    ha[j] = l15 * 256 + (((hcol >> 3) ^ sw7) << 4) + ((hcol & 4) << 1);
-  }
-  const uint32_t pair0 = ((uint32_t)(m0 + l15) * (uint32_t)p.F + (uint32_t)(32 * wn + 4 * g4)) >> 1;
+    for (int j = 0; j < 2; ++j) {
+      const int hcol = 32 * wn + 16 * j + 4 * g4o;
+      e.ha[j] = l15o * 256 + (((hcol >> 3) ^ rt_swz(l15o)) << 4) + ((hcol & 4) << 1);
+    }
+    e.pairc = (((uint32_t)(m0 + l15o) * (uint32_t)p.F + (uint32_t)(32 * wn + 4 * g4o)) >> 1) + (uint32_t)(FC / 2) * (uint32_t)c;
+    return e;
+  };
   const uint32_t pairF = 8u * (uint32_t)p.F;                 // 16 rows further
 
-  for (int c = 0; c < nch; ++c) {
-    char* const hc = hb + (c & 1) * F_HT;
-    const int f0 = FC * c + 32 * wn + 4 * g4;                // hidden column of accumulator register q of tile j: f0 + 16 j + q
+  // ---- the chunk loop, skewed by one phase: epilogue 1 of chunk c runs BESIDE product 2 of chunk c - 1 ----
+  //   before the loop  product 1 (0), epilogue 1 (0)
+  //   iteration c      barrier, H store (c - 1) [under product 1 where SPREAD], product 1 (c), { epilogue 1 (c)  ||  product 2 (c - 1) }
+  //   behind the loop  barrier, H store (nch - 1), product 2 (nch - 1)
+  // Epilogue 1 is vector work only and product 2 a chain of LDS reads and MFMAs that leaves most issue slots empty; they use
+  // different accumulators and different halves of hb (epilogue 1 (c) writes hb[c & 1], product 2 (c - 1) reads hb[(c - 1) & 1]),
+  // so one barrier per chunk still does: it publishes chunk c and retires every read of the other half before epilogue 1
+  // (c + 1) overwrites it; the H store (c) and product 2 (c) read hb[c & 1] between that barrier and the next one.
+  f32x4 acc1[5][2];
+  float b1[2][4];
+  u32x2 gt[5][2];
+  // gate bits of a lane and chunk: word g (= tile rows 0-2 | 3-4 ... see below) collects, in the order the epilogue visits them, the
+  // flags of its 32-bit stores (two values each): flag of the even value in the low half, of the odd value in the high half,
+  // first store highest.  20 stores -> two words of 10 + 10 bits per half.
+  uint32_t gw[2] = {0u, 0u};
 
-    // epilogue-1 operands of this chunk, requested before the MFMAs that hide them
-    float b1[2][4];
+  // epilogue-1 operands of chunk c, requested before the product-1 MFMAs that hide them
+  auto req_e1 = [&](int c) __attribute__((always_inline)) {
+    const int f0 = FC * c + 32 * wn + 4 * g4;                // hidden column of accumulator register q of tile j: f0 + 16 j + q
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) b1[j][q] = 0.f;
       if (EPI == 3 || (EPI == 4 && p.bias1)) load4(p.bias1 + f0 + 16 * j, b1[j]);
     }
-
-    u32x2 gt[5][2];
     if (GATE == 1) {
       int rb = rbase;
       asm volatile("" : "+v"(rb));                             // addresses are recomputed per chunk, not kept (and spilled) across the loop
@@ -183,93 +217,146 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::co
         for (int j = 0; j < 2; ++j) gt[i][j] = *(const u32x2*)(p.gate + (size_t)m * (size_t)p.ldg + f0 + 16 * j);
       }
     }
-    // gate bits of a lane and chunk: word g (= tile rows 0-2 | 3-4 ... see below) collects, in the order the epilogue visits them, the
-    // flags of its 32-bit stores (two values each): flag of the even value in the low half, of the odd value in the high half,
-    // first store highest.  20 stores -> two words of 10 + 10 bits per half.
-    uint32_t gw[2] = {0u, 0u}, ow[2] = {0u, 0u};
     if (GATE == 2) {                                           // this chunk's word was requested two chunks ago
       gw[0] = (uint32_t)gnext0;
       gw[1] = (uint32_t)(gnext0 >> 32);
       gnext0 = gnext1;
       if (c + 2 < nch) gnext1 = bits_p[(size_t)(c + 2) * 256];
     }
+  };
 
-    // ---- product 1: acc1[i][j] = sum_k W1[hidden][k] * A[row][k] ----
-    f32x4 acc1[5][2];
+  // ---- product 1: acc1[i][j] = sum_k W1[hidden][k] * A[row][k] ----
+  auto product1 = [&](int c, int cst = -1) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 5; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc1[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int lo = lane;
+    asm volatile("" : "+v"(lo));                               // (its fragment addresses: recomputed per chunk, not kept across the loop)
+    const int l15o = lo & 15, g4o = lo >> 4, sw7o = rt_swz(l15o);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       frag xf[5];
-      rt_frags<T>(xt, rbase, g4, sw7, s, xf);
+      rt_frags<T>(xt, l15o, g4o, sw7o, s, xf);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc1[i][j] = H16<T>::mfma(w1r[s & 3][j], xf[i], acc1[i][j]);
       if (s < 4) req_w1(c, s + 4, s & 3);
       else if (c + 1 < nch) req_w1(c + 1, s - 4, s & 3);
-    }
-
-    // ---- epilogue 1 (MFMA layout: lane holds 4 consecutive hidden columns of row l15) -> 16-bit chunk image in LDS ----
-    // Vector-instruction count matters here: the launch is bound by VALU issue (4 cycles per instruction and wave, two waves per
-    // SIMD), not by the matrix pipe -- 817 vector instructions per wave and chunk against 160 MFMAs before this form.
-    const uint32_t pairc = pair0 + (uint32_t)(FC / 2) * (uint32_t)c;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int t = 2 * i + j;                                // store pair 2t, 2t+1 of this chunk
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          v[q] = acc1[i][j][q];
-          if (EPI == 3 || EPI == 4) v[q] += b1[j][q];
-          if (EPI == 3) v[q] = fmaxf(v[q], 0.f);
-          if (EPI == 4 && p.relu) v[q] = fmaxf(v[q], 0.f);
-        }
-        if (GATE == 1) {
-          float gv[4];
-          load4((const T*)&gt[i][j], gv);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = gv[q] > 0.f ? v[q] * p.gate_scale : 0.f;
-        }
-        if (GATE == 2) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int n = (2 * t + (q >> 1)) % 10;              // position among the word's 10 stores
-            int m;                                               // 0 or -1 (as asm: the compiler turns the builtin back into and + compare + select)
-            asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(gw[t / 5]), "n"((9 - n) + 16 * (q & 1)));
-            v[q] = __uint_as_float(__float_as_uint(v[q] * p.gate_scale) & (uint32_t)m);
-          }
-        }
-        if (p.dh.thresh) {                                      // = eg_dropout_run<4> at element (m0 + l15 + 16 i) * F + f0 + 16 j
-          const uint32_t e = pairc + (uint32_t)(8 * j) + (uint32_t)i * pairF;
-          const uint32_t h0 = eg_hash(seed_lo, seed_hi, p.dh.site, e), h1 = eg_hash(seed_lo, seed_hi, p.dh.site, e + 1u);
-          v[0] = (h0 & 0xFFFFu) >= p.dh.thresh ? v[0] * p.dh.scale : 0.0f;
-          v[1] = (h0 >> 16) >= p.dh.thresh ? v[1] * p.dh.scale : 0.0f;
-          v[2] = (h1 & 0xFFFFu) >= p.dh.thresh ? v[2] * p.dh.scale : 0.0f;
-          v[3] = (h1 >> 16) >= p.dh.thresh ? v[3] * p.dh.scale : 0.0f;
-        }
-        const u32x2 pk = pack4<T>(v);
-        *(u32x2*)(hc + ha[j] + 4096 * i) = pk;
-        if (BOUT) {                                            // "stored value > 0", taken from the stored 16-bit patterns:
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {                        // min(max(as int16, 0), 1) per half = 1 exactly for +x, x != 0
-            uint32_t z, f;                                       // (as asm: three instructions per store; the elementwise builtins
-            asm("v_pk_max_i16 %0, %1, 0" : "=v"(z) : "v"(pk[h]));                      // came back as compare / select / permute chains)
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(f) : "v"(z), "v"(0x00010001u));
-            ow[t / 5] = (ow[t / 5] << 1) | f;
-          }
-        }
+      if (SPREAD && cst >= 0 && s >= 1 && s <= 5) {            // one 16-B piece per thread of chunk cst's stored rows behind k-steps 1-5
+        const int ps = s - 1, r = 16 * ps + (tid >> 4), ch = tid & 15;
+        const u32x4 o = *(const u32x4*)(hb + (cst & 1) * F_HT + r * 256 + rt_piece(r, ch));
+        if (m0 + r < p.M) *(u32x4*)(p.H + (size_t)(m0 + r) * (size_t)p.ldh + FC * cst + 8 * ch) = o;
       }
     }
+  };
+
+  // ---- product 2: acc2[i][j] += sum_h W2[col][h] * H[row][h] over the chunk's 128 hidden columns; group g = 5 s + i is k-step s
+  //      of tile row i: one fragment read and four MFMAs ----
+  auto p2_frag = [&](const char* hc, int g, int l15o, int g4o) __attribute__((always_inline)) {
+    return *(const frag*)(hc + (l15o + 16 * (g % 5)) * (FC * 2) + (((4 * (g / 5) + g4o) ^ rt_swz(l15o)) << 4));
+  };
+  auto p2_group = [&](int g, const frag& hf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc2[g % 5][j] = H16<T>::mfma(w2r[(g / 5) & 1][j], hf, acc2[g % 5][j]);
+  };
+
+  // ---- epilogue 1 of tile t = 2 i + j (MFMA layout: lane holds 4 consecutive hidden columns of row l15) -> 16-bit chunk image in LDS ----
+  // Vector-instruction count matters here: 817 vector instructions per wave and chunk against 160 MFMAs before this form.
+  // DROP is p.dh.thresh != 0 as a type: a run-time branch per tile would end the scheduling region that product 2 shares.
+  auto e1_tile = [&](int t, char* hc, const E1Lane& el, uint32_t (&ow)[2]) __attribute__((always_inline)) {
+    const int i = t >> 1, j = t & 1;                          // store pair 2t, 2t+1 of this chunk
+    float v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      v[q] = acc1[i][j][q];
+      if (EPI == 3 || EPI == 4) v[q] += b1[j][q];
+      if (EPI == 3) v[q] = fmaxf(v[q], 0.f);
+      if (EPI == 4 && p.relu) v[q] = fmaxf(v[q], 0.f);
+    }
+    if (GATE == 1) {
+      float gv[4];
+      load4((const T*)&gt[i][j], gv);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = gv[q] > 0.f ? v[q] * p.gate_scale : 0.f;
+    }
+    if (GATE == 2) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = (2 * t + (q >> 1)) % 10;              // position among the word's 10 stores
+        int m;                                               // 0 or -1 (as asm: the compiler turns the builtin back into and + compare + select)
+        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(gw[t / 5]), "n"((9 - n) + 16 * (q & 1)));
+        v[q] = __uint_as_float(__float_as_uint(v[q] * p.gate_scale) & (uint32_t)m);
+      }
+    }
+    if (DROP) {                                             // = eg_dropout_run<4> at element (m0 + l15 + 16 i) * F + f0 + 16 j
+      const uint32_t e = el.pairc + (uint32_t)(8 * j) + (uint32_t)i * pairF;
+      const uint32_t h0 = eg_hash(seed_lo, seed_hi, p.dh.site, e), h1 = eg_hash(seed_lo, seed_hi, p.dh.site, e + 1u);
+      v[0] = (h0 & 0xFFFFu) >= p.dh.thresh ? v[0] * p.dh.scale : 0.0f;
+      v[1] = (h0 >> 16) >= p.dh.thresh ? v[1] * p.dh.scale : 0.0f;
+      v[2] = (h1 & 0xFFFFu) >= p.dh.thresh ? v[2] * p.dh.scale : 0.0f;
+      v[3] = (h1 >> 16) >= p.dh.thresh ? v[3] * p.dh.scale : 0.0f;
+    }
+    const u32x2 pk = pack4<T>(v);
+    *(u32x2*)(hc + el.ha[j] + 4096 * i) = pk;
+    if (BOUT) {                                              // "stored value > 0", taken from the stored 16-bit patterns:
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {                          // min(max(as int16, 0), 1) per half = 1 exactly for +x, x != 0
+        uint32_t z, f;                                         // (as asm: three instructions per store; the elementwise builtins
+        asm("v_pk_max_i16 %0, %1, 0" : "=v"(z) : "v"(pk[h]));                      // came back as compare / select / permute chains)
+        asm("v_pk_min_u16 %0, %1, %2" : "=v"(f) : "v"(z), "v"(0x00010001u));
+        ow[t / 5] = (ow[t / 5] << 1) | f;
+      }
+    }
+  };
+
+  // ---- the merged phase: tile t of epilogue 1 (c) beside groups 2t, 2t + 1 of product 2 (c - 1), each tile and its eight MFMAs a
+  //      scheduling region of their own (the regions keep epilogue 1's values dying tile by tile: one region over the whole
+  //      phase computed all ten tiles' values first and spilled).  Two fragments are live at a time, not a k-step's five.
+  //      Product 2 (c - 1) requests the W2 fragments of chunk c's first two k-steps without a test: chunk c exists. ----
+  auto merged = [&](int c, uint32_t (&ow)[2]) __attribute__((always_inline)) {
+    char* const hc = hb + (c & 1) * F_HT;
+    const char* const hp = hb + ((c & 1) ^ 1) * F_HT;
+    int lo = lane;
+    asm volatile("" : "+v"(lo));                               // product 2's addresses are recomputed per chunk, not kept across the loop
+    const int l15o = lo & 15, g4o = lo >> 4;
+    const E1Lane el = e1_lane(c, l15o, g4o);
+#pragma unroll
+    for (int t = 0; t < 10; ++t) {                             // tile t beside groups 2t, 2t + 1
+      const frag hf0 = p2_frag(hp, 2 * t, l15o, g4o), hf1 = p2_frag(hp, 2 * t + 1, l15o, g4o);
+      e1_tile(t, hc, el, ow);
+      p2_group(2 * t, hf0);
+      p2_group(2 * t + 1, hf1);
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        if ((2 * t + u) % 5 == 4) {                            // k-step s is through: its ring slot takes k-step s + 2
+          const int s = (2 * t + u) / 5;
+          if (s < 2) req_w2(c - 1, s + 2, s & 1);
+          else req_w2(c, s - 2, s & 1);
+        }
+      if (DROP) ffn_pin<16, 8>();
+      else ffn_pin<2, 2>();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // chunk 0 has no product 2 beside its epilogue 1
+  auto e1_alone = [&](uint32_t (&ow)[2]) __attribute__((always_inline)) {
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+    const E1Lane el = e1_lane(0, lo & 15, lo >> 4);
+#pragma unroll
+    for (int t = 0; t < 10; ++t) {
+      e1_tile(t, hb, el, ow);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // chunk c is complete in LDS: its gate bits, the barrier, and the stored result: whole 256-B row segments, 16 B per thread
+  auto publish = [&](int c, const uint32_t (&ow)[2], bool store = true) __attribute__((always_inline)) {
+    const char* const hc = hb + (c & 1) * F_HT;
     if (BOUT) p.bits_out[((size_t)blockIdx.x * nch + c) * 256 + wn * 64 + lane] = (unsigned long long)ow[0] | ((unsigned long long)ow[1] << 32);
     __syncthreads();        // chunk c is complete in LDS; nobody reads buffer (c+1)&1 (chunk c-1) any more
-
-    // ---- the stored result: whole 256-B row segments of the chunk, 16 B per thread ----
-    if constexpr (KEEP) {
+    if (KEEP && store) {
       int tq = tid >> 4;
       asm volatile("" : "+v"(tq));                             // (same: no loop-invariant address registers)
 #pragma unroll
@@ -279,19 +366,38 @@ __global__ __launch_bounds__(256, 2) void ffn_chain_kernel(FfnArgs<T> p, std::co
         if (m0 + r < p.M) *(u32x4*)(p.H + (size_t)(m0 + r) * (size_t)p.ldh + FC * c + 8 * ch) = o;
       }
     }
+  };
 
-    // ---- product 2: acc2[i][j] += sum_h W2[col][h] * H[row][h] over the chunk's 128 hidden columns ----
+  {
+    uint32_t ow[2] = {0u, 0u};
+    req_e1(0);
+    product1(0);
+    e1_alone(ow);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) req_w2(0, s, s);               // the W2 ring starts here: product 2 (0) is a whole product 1 away
+    for (int c = 1; c < nch; ++c) {
+      publish(c - 1, ow, !SPREAD);
+      ow[0] = 0u; ow[1] = 0u;
+      req_e1(c);
+      product1(c, SPREAD ? c - 1 : -1);
+      merged(c, ow);
+    }
+    publish(nch - 1, ow);
+    // product 2 of the last chunk (no further weight fragments)
+    const char* const hp = hb + ((nch - 1) & 1) * F_HT;
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+    const int l15o = lo & 15, g4o = lo >> 4;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       frag hf[5];
-      rt_frags<T, FC * 2>(hc, rbase, g4, sw7, s, hf);
 #pragma unroll
-      for (int i = 0; i < 5; ++i)
+      for (int i = 0; i < 5; ++i) hf[i] = p2_frag(hp, 5 * s + i, l15o, g4o);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc2[i][j] = H16<T>::mfma(w2r[s & 1][j], hf[i], acc2[i][j]);
-      if (s < 2) req_w2(c, s + 2, s & 1);
-      else if (c + 1 < nch) req_w2(c + 1, s - 2, s & 1);
+      for (int i = 0; i < 5; ++i) p2_group(5 * s + i, hf[i]);
+      if (s < 2) req_w2(nch - 1, s + 2, s & 1);
     }
+    __builtin_amdgcn_sched_barrier(0);                         // (the last MFMAs stay in front of the barrier, out of epilogue 2's registers)
   }
   __syncthreads();          // every wave has left the chunk buffers: they become the fp32 image of the final epilogue
 
@@ -403,11 +509,17 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   const FfnArgs<T> p = ffn_make_args<T>(d);
   const FfnNoTail nt;
   const dim3 grid((d->M + FR - 1) / FR);
-#define FFN_LAUNCH(G_, B_, E_, L_) eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_>, F_LDS>(grid, dim3(256), s, p, nt)
+  // DROP (dropout on the hidden rows) is a template flag: a run-time test inside the kernel splits the merged phase's scheduling regions
+#define FFN_LAUNCH_K(G_, B_, E_, L_, K_, T_, Q_)                                                                  \
+  do {                                                                                                            \
+    if (p.dh.thresh) eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_, K_, T_, true>, F_LDS>(grid, dim3(256), s, p, Q_);  \
+    else eg_launch_lds<ffn_chain_kernel<T, G_, B_, E_, L_, K_, T_, false>, F_LDS>(grid, dim3(256), s, p, Q_);             \
+  } while (0)
+#define FFN_LAUNCH(G_, B_, E_, L_) FFN_LAUNCH_K(G_, B_, E_, L_, true, false, nt)
   const int gsel = d->gate_bits_in ? 2 : d->gate ? 1 : 0;
   const bool bout = d->gate_bits_out != nullptr;
   const bool lnf = d->ln_out != nullptr;                                                                      // (forward form only, checked below)
-  if (!d->H) eg_launch_lds<ffn_chain_kernel<T, 0, 0, 3, true, false>, F_LDS>(grid, dim3(256), s, p, nt);         // lean (forward form, LNF, no bits: checked below)
+  if (!d->H) FFN_LAUNCH_K(0, 0, 3, true, false, false, nt);                                                       // lean (forward form, LNF, no bits: checked below)
   else if (gsel == 0 && d->bias1 && p.relu) {                                                                 // the forward pass
     if (lnf) { if (bout) FFN_LAUNCH(0, 1, 3, true); else FFN_LAUNCH(0, 0, 3, true); }
     else { if (bout) FFN_LAUNCH(0, 1, 3, false); else FFN_LAUNCH(0, 0, 3, false); }
@@ -418,7 +530,6 @@ static int ffn_launch(const eg_ffn_desc* d, hipStream_t s) {
   else if (gsel == 1) FFN_LAUNCH(1, 0, 4, false);
   else if (bout) FFN_LAUNCH(0, 1, 4, false);
   else FFN_LAUNCH(0, 0, 4, false);
-#undef FFN_LAUNCH
   EG_LAUNCH_CHECK("ffn_chain");
   return 0;
 }
@@ -428,7 +539,10 @@ template <typename T>
 static int ffn_tail_launch(const eg_ffn_desc* f, const eg_ln_bwd_proj_desc* n, hipStream_t s) {
   const FfnArgs<T> p = ffn_make_args<T>(f);
   const LnProjArgs<T> q = lp_make_args<T>(n);
-  eg_launch_lds<ffn_chain_kernel<T, 2, 0, 0, false, true, true>, F_LDS>(dim3((f->M + FR - 1) / FR), dim3(256), s, p, q);
+  const dim3 grid((f->M + FR - 1) / FR);
+  FFN_LAUNCH_K(2, 0, 0, false, true, true, q);
+#undef FFN_LAUNCH
+#undef FFN_LAUNCH_K
   EG_LAUNCH_CHECK("ffn_bwd_ln_proj");
   return 0;
 }
