@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 from eyegaze_multimodal_amd import _lib as L  # noqa: E402
 from eyegaze_multimodal_amd._lib import GemmDesc, call, ptr, rowmap  # noqa: E402
 from tests.helpers import hip_keep_mask  # noqa: E402
+from eyegaze_multimodal_amd.engine import scramble_seed  # noqa: E402
 from tests.test_gpu_ops import dev_state  # noqa: E402
 
 DEV = "cuda"
@@ -47,7 +48,7 @@ def run_case(M, N, residual, gate, act, drop, out_pre, ln, seed=0, K=256):
     y = torch.full((M, N), 7.0, device=DEV, dtype=torch.bfloat16)
     stats = torch.zeros(M, 2, device=DEV)
     gam, bet = torch.randn(N, generator=g).to(DEV), torch.randn(N, generator=g).to(DEV)
-    st = dev_state(seed=1234 + seed)
+    st = dev_state(seed=scramble_seed(1234 + seed))    # the words Engine.set_state publishes, which hip_keep_mask replays
     d = GemmDesc()
     d.A, d.W, d.C, d.bias = ptr(A), ptr(W), ptr(out), ptr(b)
     d.residual = ptr(R) if residual else None
@@ -65,21 +66,31 @@ def run_case(M, N, residual, gate, act, drop, out_pre, ln, seed=0, K=256):
     return t, dict(out=out.float().cpu(), pre=pre.float().cpu(), y=y.float().cpu(), stats=stats.cpu())
 
 
+def keep_mask(M, N, drop, seed=0):
+    """the kernel's keep decisions at site 11, element index m * N + n, replayed on the CPU (in slabs: the largest case has 48 M elements)"""
+    keep = np.empty(M * N, dtype=bool)
+    step = 1 << 22
+    for i in range(0, M * N, step):
+        idx = np.arange(i, min(i + step, M * N), dtype=np.uint64).astype(np.uint32)
+        keep[i:i + idx.size] = hip_keep_mask(1234 + seed, 11, idx, drop)
+    return torch.from_numpy(keep.reshape(M, N))
+
+
 def reference(t, M, N, residual, gate, act, drop, out_pre, ln, seed=0):
     v = t["A"].double().cpu() @ t["W"].double().cpu().T + t["b"].double().cpu()
     if act == 1:
         v = v.clamp_min(0)
     if gate:
         v = torch.where(t["G"].double().cpu() > 0, v * 1.25, torch.zeros_like(v))
+    keep = None
     if drop > 0:
-        idx = np.arange(M * N, dtype=np.uint64).astype(np.uint32)
-        keep = torch.from_numpy(hip_keep_mask(1234 + seed, 11, idx, drop).reshape(M, N))
-        # dev_state() stores the seed unscrambled; hip_keep_mask scrambles like Engine.set_state -> compare statistically below
-        v_keep = keep
+        keep = keep_mask(M, N, drop, seed)
+        scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(drop)))
+        v = torch.where(keep, v * scale, torch.zeros_like(v))
     pre = v.clone()
     if residual:
         v = v + t["R"].double().cpu()
-    return v, pre
+    return v, pre, keep
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "M%d_N%d_r%d_g%d_a%d_p%g_o%d_ln%d" % c)
@@ -101,13 +112,27 @@ def test_rs_gemm_is_bit_identical_to_the_tiled_kernel(case, tmp_path):
         assert torch.equal(got["stats"], ref["stats"])
 
 
-@pytest.mark.parametrize("case", [c for c in CASES if c[5] == 0.0], ids=lambda c: "M%d_N%d_r%d_g%d_a%d_p%g_o%d_ln%d" % c)
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "M%d_N%d_r%d_g%d_a%d_p%g_o%d_ln%d" % c)
 def test_rs_gemm_matches_fp64(case):
     M, N, residual, gate, act, drop, out_pre, ln = case
     t, got = run_case(*case)
-    v, pre = reference(t, *case)
+    v, pre, keep = reference(t, *case)
     err = float((got["out"].double() - v).abs().max())
     assert err <= 0.02 + 0.008 * float(v.abs().max()), err          # one bf16 rounding of the result
+    if out_pre:
+        errp = float((got["pre"].double() - pre).abs().max())
+        assert errp <= 0.02 + 0.008 * float(pre.abs().max()), errp
+    if keep is not None:
+        # the zero pattern is the replayed mask, element for element: a dropped element is an exact zero (seen in out_pre, or
+        # in the output where no residual is added), and a kept one is zero only where the value in front of the dropout is
+        masked = got["pre"] if out_pre else (got["out"] if not residual else None)
+        if masked is not None:
+            assert bool((masked[~keep] == 0).all()), "a dropped element is not an exact zero"
+            live = keep & (pre.abs() > 0.02)                         # far from zero: a kept element of this size cannot store as 0
+            assert bool((masked[live] != 0).all()), "a kept element was zeroed"
+        else:
+            base = (got["out"].double() - t["R"].double().cpu())    # residual added: the dropped elements are the residual itself
+            assert float(base[~keep].abs().max()) == 0.0, "a dropped element is not the residual alone"
     if ln:
         x = got["out"].double()
         mean, var = x.mean(-1, keepdim=True), x.var(-1, unbiased=False, keepdim=True)
