@@ -103,6 +103,7 @@ class GazeResizeDesc(C.Structure):
 
 
 GAZE_MAX_SIDE, GAZE_MIN_OUT, GAZE_MAX_OUT = 4096, 8, 512      # EG_GAZE_MAX_SIDE, EG_GAZE_MIN_OUT, EG_GAZE_MAX_OUT
+TSNE_MAX_N, TSNE_MAX_D = 16384, 4096                          # EG_TSNE_MAX_N, EG_TSNE_MAX_D
 
 
 class PackEntry(C.Structure):
@@ -189,6 +190,12 @@ SIGNATURES = {
     "eg_trial_spectral_entropy": [C.POINTER(RecordingRowsDesc), C.c_double, C.c_double, _P, _P, _P],
     "eg_image_entropy_workspace_doubles": [_I, _I],                  # returns int64_t: image_entropy_workspace_doubles() below
     "eg_image_entropy": [C.POINTER(ImageBatchDesc), C.c_double, _P, _L, _P, _P],
+    "eg_tsne_workspace_bytes": [_I],                                 # returns int64_t: tsne_workspace_bytes() below
+    "eg_tsne_sqdist": [_P, _I, _I, _P, _P],
+    "eg_tsne_affinities": [_P, _I, C.c_double, _P, _P, _P, _P],
+    "eg_tsne_joint": [_P, _I, _P, _L, _P, _P],
+    "eg_tsne_gradient": [_P, _P, C.c_double, _I, _P, _L, _P, _P, _P],
+    "eg_tsne_update": [_P, _P, _P, _P, _I, _F, _F, _F, _P, _P],
     "eg_gaze_resize_workspace_bytes": [_I, _L, _I],                  # returns int64_t: gaze_resize_workspace_bytes() below
     "eg_gaze_resize": [C.POINTER(GazeResizeDesc), _P, _L, _P, _P],
     "eg_gaze_batch": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _U, _U, _F, _F, _F, _P, _P, _P, _P, _P, _P],
@@ -342,6 +349,13 @@ def gaze_resize_workspace_bytes(n_images: int, sum_h: int, W: int) -> int:
     l = lib()
     l.eg_gaze_resize_workspace_bytes.restype = C.c_int64
     return int(l.eg_gaze_resize_workspace_bytes(n_images, sum_h, W))
+
+
+def tsne_workspace_bytes(N: int) -> int:
+    """Bytes of workspace eg_tsne_joint and eg_tsne_gradient need for N points (host only; -1: N out of range)"""
+    l = lib()
+    l.eg_tsne_workspace_bytes.restype = C.c_int64
+    return int(l.eg_tsne_workspace_bytes(N))
 
 
 def exported_symbols():

@@ -265,6 +265,45 @@ int eg_image_entropy(const eg_image_batch_desc* d, double eps, double* workspace
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact t-SNE of [N, D] embeddings into two components (sklearn.manifold.TSNE with method="exact"; 5_Metrics/eeg_metrics.py:676-703,
+ * DESIGN.md §8p) in stages.  Every stage is a deterministic function of its inputs: no atomics, every sum across lanes or
+ * workgroups in fp64 and in a fixed order, so two runs give the same bytes.  Inputs are only read.  All pointers are device
+ * pointers; matrices are dense row-major [N, N].  Every entry refuses on the host, before any launch: null pointers (stats of
+ * eg_tsne_gradient / eg_tsne_update may be null), N outside [2, EG_TSNE_MAX_N], and a workspace below eg_tsne_workspace_bytes(N).
+ *
+ * eg_tsne_sqdist: dist[i][j] = sum_d (x_id - x_jd)^2 from the differences themselves, each squared and added in fp64 in ascending
+ *   d, rounded once to f32: symmetric, zero diagonal.  Also refused: D outside [1, EG_TSNE_MAX_D].
+ * eg_tsne_affinities: sklearn's _binary_search_perplexity, one workgroup per row i.  beta = 1 and an open bracket at the start; a
+ *   step computes over j != i  p_j = exp(-dist_ij beta), S = sum p_j (1e-8 if 0), H = ln S + beta (sum dist_ij p_j) / S, all fp64,
+ *   and ends the search when |H - ln perplexity| <= 1e-5; otherwise H too large: beta is the lower end, doubled while the upper
+ *   end is open, else moved half way to it; H too small: the mirror image with halving.  A counted loop of at most 100 steps.
+ *   cond[i][j] = p_j / S at the last beta evaluated (0 on the diagonal), beta[i] = that beta, steps[i] = the number of times beta
+ *   moved (100: the search ran out).  Also refused: perplexity <= 0 or >= N, cond == dist.
+ * eg_tsne_joint: P_ij = max((c_ij + c_ji) / T, 2^-52) with T = max(2 sum_all c, 2^-52), zero diagonal, symmetric.  Three launches:
+ *   row sums, their fold, the tiles.  P may be written over the storage of dist; P == cond is refused.
+ * eg_tsne_gradient: sklearn's _kl_divergence at one degree of freedom, fp64 throughout: w_ij = 1 / (1 + |y_i - y_j|^2),
+ *   Z = sum_{i != j} w_ij, Q_ij = max(w_ij / Z, 2^-52), grad_i = 4 sum_j (e P_ij - Q_ij) w_ij (y_i - y_j) rounded once to f32, and
+ *   with stats: stats[0] = sum_{i != j} e P_ij ln(max(e P_ij, 2^-52) / Q_ij); e = exaggeration.  Launch 1 writes per-workgroup
+ *   sums of w, launch 2 folds them (every workgroup in the same order) and streams P once with the whole Y in LDS (8 N bytes), a
+ *   third folds the per-workgroup KL sums when stats is given.  Y on an 8-byte boundary.  Also refused: exaggeration <= 0.
+ * eg_tsne_update: sklearn's _gradient_descent body, every product and sum a rounded f32 operation: gains += 0.2 where
+ *   update grad < 0, else gains *= 0.8; gains = max(gains, min_gain); g = grad gains; update = momentum update - learning_rate g;
+ *   Y += update; with stats: stats[1] = sum g^2 in fp64.  Y, update and gains [N, 2] are updated in place, grad is only read.
+ *   One workgroup.  Also refused: learning_rate <= 0, momentum < 0, min_gain <= 0.
+ * ------------------------------------------------------------------------------------------- */
+#define EG_TSNE_MAX_N 16384
+#define EG_TSNE_MAX_D 4096
+/* Bytes of workspace eg_tsne_joint and eg_tsne_gradient need for N points (host only; -1: N out of range). */
+int64_t eg_tsne_workspace_bytes(int N);
+int eg_tsne_sqdist(const float* X, int N, int D, float* dist, void* stream);
+int eg_tsne_affinities(const float* dist, int N, double perplexity, float* cond, double* beta, int32_t* steps, void* stream);
+int eg_tsne_joint(const float* cond, int N, void* workspace, int64_t workspace_bytes, float* P, void* stream);
+int eg_tsne_gradient(const float* Y, const float* P, double exaggeration, int N, void* workspace, int64_t workspace_bytes,
+                     float* grad, double* stats, void* stream);
+int eg_tsne_update(float* Y, float* update, float* gains, const float* grad, int N, float momentum, float learning_rate,
+                   float min_gain, double* stats, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Gaze heat-map images as the multimodal trainer's input (1_Data/processed/multimodal_dataset.py:67-83): resized
  * once into a uint8 store, then one launch per training batch.  All of it is integer or table arithmetic and bit-exact.
  *
