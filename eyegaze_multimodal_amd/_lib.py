@@ -104,6 +104,7 @@ class GazeResizeDesc(C.Structure):
 
 GAZE_MAX_SIDE, GAZE_MIN_OUT, GAZE_MAX_OUT = 4096, 8, 512      # EG_GAZE_MAX_SIDE, EG_GAZE_MIN_OUT, EG_GAZE_MAX_OUT
 TSNE_MAX_N, TSNE_MAX_D = 16384, 4096                          # EG_TSNE_MAX_N, EG_TSNE_MAX_D
+GAZE_PAIR_FIELDS, ROW_COSINE_MAX_D = 14, 4096                 # EG_GAZE_PAIR_FIELDS, EG_ROW_COSINE_MAX_D
 
 
 class PackEntry(C.Structure):
@@ -199,6 +200,9 @@ SIGNATURES = {
     "eg_gaze_resize_workspace_bytes": [_I, _L, _I],                  # returns int64_t: gaze_resize_workspace_bytes() below
     "eg_gaze_resize": [C.POINTER(GazeResizeDesc), _P, _L, _P, _P],
     "eg_gaze_batch": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _U, _U, _F, _F, _F, _P, _P, _P, _P, _P, _P],
+    "eg_gaze_pair_stats_workspace_bytes": [_I],                      # returns int64_t: gaze_pair_stats_workspace_bytes() below
+    "eg_gaze_pair_stats": [_P, _I, _I, _I, _P, _I, _P, _F, _P, _L, _P, _P],
+    "eg_row_cosine": [_P, _P, _I, _I, _P, _P],
     "eg_window_augment": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P],
     "eg_attention_probs": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_attention_long_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U, _P, _P],
@@ -349,6 +353,13 @@ def gaze_resize_workspace_bytes(n_images: int, sum_h: int, W: int) -> int:
     l = lib()
     l.eg_gaze_resize_workspace_bytes.restype = C.c_int64
     return int(l.eg_gaze_resize_workspace_bytes(n_images, sum_h, W))
+
+
+def gaze_pair_stats_workspace_bytes(n_images: int) -> int:
+    """Bytes of workspace eg_gaze_pair_stats needs for a store of n_images (host only; -1: n_images <= 0)"""
+    l = lib()
+    l.eg_gaze_pair_stats_workspace_bytes.restype = C.c_int64
+    return int(l.eg_gaze_pair_stats_workspace_bytes(n_images))
 
 
 def tsne_workspace_bytes(N: int) -> int:

@@ -376,6 +376,42 @@ int eg_gaze_batch(const uint8_t* store, int n_images, int F, int W, const int32_
                   float hflip_p, float brightness, float contrast, const float* factors, float* img1, float* img2, float* rgb1,
                   float* rgb2, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaze pair analysis over the store (6_Utils/error_analysis.py:277-358 compute_gaze_distance / compute_gaze_overlap):
+ * the per-pair table of the reference's spatial-sensitivity analysis in two launches.  store [n_images, F, W, 3] uint8, pair_img
+ * [n_pairs, 2] int32, norm [3][256] f32 (the table of eg_gaze_batch, or float32(v) / 255 in every channel for raw ToTensor
+ * tensors), out [n_pairs][EG_GAZE_PAIR_FIELDS] f64; all device pointers.  A pixel is t_c = norm[c][v_c],
+ * g = ((t0 + t1) + t2) / 3.0f, the division correctly rounded and nothing fused: tensor.mean(dim=0), bit for bit.
+ *   launch 1, workgroup = image (EVERY image of the store, once): min and max of g in fp32, and in fp64 S = sum g,
+ *     Sy = sum fl32(g float(y)), Sx = sum fl32(g float(x)), A = sum |g| -- the products rounded to fp32 as torch rounds them, the
+ *     sums in ONE order that depends only on (F, W): per-thread strided partials, a fixed butterfly inside the wave, the waves in
+ *     ascending order.  -> workspace [n_images][8] f64: S, Sy, Sx, A, min, max, 0, 0.
+ *   launch 2, workgroup = pair (a, b): g of both images again, q = (g - min) / ((max - min) + 1e-8f) in rounded fp32 operations,
+ *     the masks q > threshold, integer counts na, nb, inter.  The row:
+ *       [0] distance = sqrt((cy_a - cy_b)^2 + (cx_a - cx_b)^2) in fp64, a centre being (Sy / S, Sx / S), or the reference's LITERAL
+ *           (112, 112) when S < 1e-8, whatever F and W are
+ *       [1] overlap = double(float(inter) / float(union)), union = na + nb - inter; 0.0 when union == 0
+ *       [2..5] cy_a, cx_a, cy_b, cx_b   [6..9] inter, union, na, nb   [10..13] S_a, S_b, A_a, A_b
+ * No atomics: a row's bytes depend on its two images alone, not on the batch, the run, or where in the store the images lie
+ * (16-byte loads where an image starts on a 16-byte boundary, byte loads where not, the same pixels to the same thread).
+ * A pair with an image index outside [0, n_images) is skipped on the device: its row is not written.  Inputs are only read.
+ * Refused on the host, before any launch: null pointers, n_images <= 0, n_pairs <= 0, F / W outside [EG_GAZE_MIN_OUT,
+ * EG_GAZE_MAX_OUT], a threshold that is not finite, a workspace below eg_gaze_pair_stats_workspace_bytes(n_images), workspace or
+ * out off an 8-byte boundary.
+ *
+ * eg_row_cosine: out[i] = float(dot / (max(sqrt(|a_i|^2), 1e-12) max(sqrt(|b_i|^2), 1e-12))) for rows of two [N, D] f32 arrays
+ * (error_analysis.py:460-464: F.normalize on both, then the sum of products), dot and both squared norms in fp64, one wave per
+ * row, lane l over columns l, l + 64, ... then a fixed butterfly.  Refused on the host: null pointers, N <= 0, D outside
+ * [1, EG_ROW_COSINE_MAX_D].
+ * ------------------------------------------------------------------------------------------- */
+#define EG_GAZE_PAIR_FIELDS 14
+#define EG_ROW_COSINE_MAX_D 4096
+/* Bytes of workspace eg_gaze_pair_stats needs: 64 per image (host only; -1: n_images <= 0). */
+int64_t eg_gaze_pair_stats_workspace_bytes(int n_images);
+int eg_gaze_pair_stats(const uint8_t* store, int n_images, int F, int W, const int32_t* pair_img, int n_pairs, const float* norm,
+                       float threshold, void* workspace, int64_t workspace_bytes, double* out, void* stream);
+int eg_row_cosine(const float* a, const float* b, int N, int D, float* out, void* stream);
+
 /* Training-time window augmentation in ONE launch (the reference lab's EEG recipe, 4_Experiments/experiments_list.md:304-310:
  * Gaussian noise, channel dropout, time masks).  in1/in2 -> out1/out2, each [N, C, T] f32, contiguous; out may alias in; player
  * pl = 0 for buffer 1 and 1 for buffer 2.  Every draw is counter-based: H(site, i) = eg_hash(state->seed_lo, state->seed_hi,
