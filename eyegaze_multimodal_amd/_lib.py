@@ -255,6 +255,9 @@ SIGNATURES = {
     "eg_stft_logmag": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_spec_conv1_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "eg_spec_conv1_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "eg_spec_conv1_band_rows": [_I, _I],                             # returns the band height itself: spec_conv1_band_rows() below
+    "eg_spec_conv1_fwd_banded": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "eg_spec_conv1_bwd_banded": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eg_spec_avgpool_fwd": [_P, _P, _I, _I, _I, _I, _P],
     "eg_spec_avgpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
     "eg_pack_conv2d_weight": [_P, _P, _I, _I, _I, _I, _P],
@@ -360,6 +363,11 @@ def gaze_pair_stats_workspace_bytes(n_images: int) -> int:
     l = lib()
     l.eg_gaze_pair_stats_workspace_bytes.restype = C.c_int64
     return int(l.eg_gaze_pair_stats_workspace_bytes(n_images))
+
+
+def spec_conv1_band_rows(F: int, nfr: int) -> int:
+    """Pooled rows per band of conv-1 for F x nfr images (host only): 0 = the whole-image kernels, -1 = no band fits the LDS"""
+    return int(lib().eg_spec_conv1_band_rows(F, nfr))
 
 
 def tsne_workspace_bytes(N: int) -> int:

@@ -1,5 +1,6 @@
 // 2-D CNN over the STFT image (dual_eeg_transformer.py:70-77, 124-127):
-//   Conv2d(1,32,3,p1)+ReLU+MaxPool2  -> direct kernel (one workgroup per image; K = 9 is too shallow for MFMA)
+//   Conv2d(1,32,3,p1)+ReLU+MaxPool2  -> direct kernel (one workgroup per image, or per band of pooled rows where the padded image
+//                                        exceeds 64 KiB of LDS: eg_spec_conv1_band_rows; K = 9 is too shallow for MFMA)
 //   Conv2d(32,64,3,p1)+ReLU          -> eg_gemm_nt over segmented channel-last rows (3 segments of 4 x 32 channels)
 //   AdaptiveAvgPool2d(4,4)+flatten   -> pooling kernel that emits PyTorch's (c, py, px) flatten order
 // Layouts (per image, "padded" = one zero row on top/bottom, one zero column left, three right):
@@ -141,6 +142,144 @@ __global__ __launch_bounds__(256) void spec_conv1_bwd_kernel(const float* __rest
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) s += red[(g8 * C1 + c) * 10 + j];
     partial[(size_t)im * 320 + (j < 9 ? c * 9 + j : 288 + c)] = s;
+  }
+}
+
+// Banded forms of the two kernels above for images whose zero-padded whole does not fit the LDS: a workgroup is (image, band of
+// band_rows pooled rows) and stages the input rows 2 y0 - 1 .. 2 (y0 + b) of its band, zero outside the image.  LDS row j of a band
+// is input row 2 y0 - 1 + j, so pooled row y0 + yl reads LDS rows 2 yl .. 2 yl + 3: the whole-image kernels' addressing with y -> yl.
+// Per output the multiply-add chain is theirs (bias, then ky, kx, fmaf), so p1 is theirs bit for bit.  (Kernels of their own, not
+// a band parameter of the ones above: those serve every shape that ran before this route existed and stay as they were compiled.)
+__device__ __forceinline__ void conv1_stage_band(float* I, const float* __restrict__ img, int im, int F, int nfr, int y0, int nb) {
+  const int PW = nfr + 2, top = 2 * y0 - 1;
+  for (int i = threadIdx.x; i < (2 * nb + 2) * PW; i += blockDim.x) {
+    const int y = top + i / PW, x = i % PW - 1;
+    I[i] = (y >= 0 && y < F && x >= 0 && x < nfr) ? img[((size_t)im * F + y) * nfr + x] : 0.f;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void spec_conv1_fwd_banded_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, T* __restrict__ p1, int F,
+                                                                    int nfr, int band_rows, int nbands) {
+  extern __shared__ float sm[];
+  const int Hp = F / 2, Wp = nfr / 2, PW = nfr + 2;
+  float* I = sm;                                   // [2 * band_rows + 2][PW]
+  float* wl = I + (2 * band_rows + 2) * PW;        // [32][9]
+  float* bl = wl + C1 * 9;                         // [32]
+  const int im = blockIdx.x / nbands, y0 = (blockIdx.x % nbands) * band_rows;
+  const int nb = min(band_rows, Hp - y0);          // the last band may be ragged
+  conv1_stage_band(I, img, im, F, nfr, y0, nb);
+  for (int i = threadIdx.x; i < C1 * 9; i += blockDim.x) wl[i] = w[i];
+  if (threadIdx.x < C1) bl[threadIdx.x] = bias[threadIdx.x];
+  __syncthreads();
+  const int ch = threadIdx.x & 31;
+  float wk[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) wk[i] = wl[ch * 9 + i];
+  const float bb = bl[ch];
+  T* ob = p1 + (size_t)im * (Hp + 2) * (Wp + 4) * C1;
+  for (int yl = threadIdx.x >> 5; yl < nb; yl += 8) {
+    const float* r0 = I + (2 * yl) * PW;
+    T* orow = ob + ((size_t)(y0 + yl + 1) * (Wp + 4) + 1) * C1 + ch;
+    float pt[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pt[r][2] = r0[r * PW]; pt[r][3] = r0[r * PW + 1]; }
+    for (int x = 0; x < Wp; ++x) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        pt[r][0] = pt[r][2]; pt[r][1] = pt[r][3];
+        pt[r][2] = r0[r * PW + 2 * x + 2]; pt[r][3] = r0[r * PW + 2 * x + 3];
+      }
+      float best = 0.f;
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          float a = bb;
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) a = fmaf(wk[ky * 3 + kx], pt[dy + ky][dx + kx], a);
+          best = fmaxf(best, a);
+        }
+      Elem<T>::st(orow + (size_t)x * C1, best);
+    }
+  }
+}
+
+// partial[im * nbands + band][320] = the band's (dW[32][9] | db[32]); every row written whole by its workgroup (a ragged or short
+// band leaves idle lane groups with zero sums), no atomics
+template <typename T>
+__global__ __launch_bounds__(256) void spec_conv1_bwd_banded_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, const T* __restrict__ dp1,
+                                                                    float* __restrict__ partial, int F, int nfr, int band_rows,
+                                                                    int nbands) {
+  extern __shared__ float sm[];
+  const int Hp = F / 2, Wp = nfr / 2, PW = nfr + 2;
+  float* I = sm;
+  float* wl = I + (2 * band_rows + 2) * PW;
+  float* bl = wl + C1 * 9;
+  float* red = bl + C1;  // [8][32][10]
+  const int im = blockIdx.x / nbands, y0 = (blockIdx.x % nbands) * band_rows;
+  const int nb = min(band_rows, Hp - y0);
+  conv1_stage_band(I, img, im, F, nfr, y0, nb);
+  for (int i = threadIdx.x; i < C1 * 9; i += blockDim.x) wl[i] = w[i];
+  if (threadIdx.x < C1) bl[threadIdx.x] = bias[threadIdx.x];
+  __syncthreads();
+  const int ch = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  float wk[9], acc[10];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) wk[i] = wl[ch * 9 + i];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) acc[i] = 0.f;
+  const float bb = bl[ch];
+  const T* gb = dp1 + (size_t)im * (Hp + 2) * Wp * C1;
+  for (int yl = grp; yl < nb; yl += 8) {
+    const float* r0 = I + (2 * yl) * PW;
+    const T* grow = gb + (size_t)(y0 + yl) * Wp * C1 + ch;
+    float pt[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pt[r][2] = r0[r * PW]; pt[r][3] = r0[r * PW + 1]; }
+    for (int x = 0; x < Wp; ++x) {
+      const float g = Elem<T>::ld(grow + (size_t)x * C1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        pt[r][0] = pt[r][2]; pt[r][1] = pt[r][3];
+        pt[r][2] = r0[r * PW + 2 * x + 2]; pt[r][3] = r0[r * PW + 2 * x + 3];
+      }
+      float best = -INFINITY;
+      int by = 0, bx = 0;
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          float a = bb;
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) a = fmaf(wk[ky * 3 + kx], pt[dy + ky][dx + kx], a);
+          if (a > best) { best = a; by = dy; bx = dx; }      // the first maximum in (dy, dx) order
+        }
+      if (best > 0.f) {
+        const float* q = r0 + by * PW + 2 * x + bx;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = fmaf(g, q[ky * PW + kx], acc[ky * 3 + kx]);
+        acc[9] += g;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 10; ++i) red[(grp * C1 + ch) * 10 + i] = acc[i];
+  __syncthreads();
+  for (int i = threadIdx.x; i < C1 * 10; i += blockDim.x) {
+    const int c = i / 10, j = i % 10;
+    float s = 0.f;
+#pragma unroll
+    for (int g8 = 0; g8 < 8; ++g8) s += red[(g8 * C1 + c) * 10 + j];
+    partial[(size_t)blockIdx.x * 320 + (j < 9 ? c * 9 + j : 288 + c)] = s;
   }
 }
 
@@ -507,16 +646,23 @@ static int spec_shape_ok(const char* who, int nimg, int F, int nfr) {
   return 0;
 }
 
+// conv-1's dynamic LDS: `rows` staged rows of nfr + 2 floats, the weights and bias, and (backward) the [8][32][10] reduction.
+// 64 KiB is what a launch gets without raising the kernel's dynamic LDS attribute
+constexpr int CONV1_LDS_MAX = 65536;
+static long long conv1_lds_bwd(long long rows, int nfr) { return (rows * (nfr + 2) + C1 * 10 + 8 * C1 * 10) * 4; }
+
 extern "C" int eg_spec_conv1_fwd(const float* img, const float* w, const float* bias, void* p1, int nimg, int F, int nfr,
                                  int dtype, void* stream) {
   if (eg_dtype_check("eg_spec_conv1_fwd", dtype, true)) return 1;
   EG_CHECK(img && w && bias && p1, "eg_spec_conv1_fwd: null pointer");
   if (spec_shape_ok("eg_spec_conv1_fwd", nimg, F, nfr)) return 1;
-  const int lds = ((F + 2) * (nfr + 2) + C1 * 10) * 4;
+  const long long lds = ((long long)(F + 2) * (nfr + 2) + C1 * 10) * 4;
+  EG_CHECK(lds <= CONV1_LDS_MAX, "eg_spec_conv1_fwd: image %dx%d needs %lld bytes of LDS whole (limit %d): use "
+           "eg_spec_conv1_fwd_banded with eg_spec_conv1_band_rows", F, nfr, lds, CONV1_LDS_MAX);
   hipStream_t s = (hipStream_t)stream;
   eg_dispatch_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(spec_conv1_fwd_kernel<T>, dim3(nimg), dim3(256), lds, s, img, w, bias, (T*)p1, F, nfr);
+    hipLaunchKernelGGL(spec_conv1_fwd_kernel<T>, dim3(nimg), dim3(256), (int)lds, s, img, w, bias, (T*)p1, F, nfr);
   });
   EG_LAUNCH_CHECK("spec_conv1_fwd");
   return 0;
@@ -527,13 +673,72 @@ extern "C" int eg_spec_conv1_bwd(const float* img, const float* w, const float* 
   if (eg_dtype_check("eg_spec_conv1_bwd", dtype, true)) return 1;
   EG_CHECK(img && w && bias && dp1 && partial, "eg_spec_conv1_bwd: null pointer");
   if (spec_shape_ok("eg_spec_conv1_bwd", nimg, F, nfr)) return 1;
-  const int lds = ((F + 2) * (nfr + 2) + C1 * 10 + 8 * C1 * 10) * 4;
+  const long long lds = conv1_lds_bwd(F + 2, nfr);
+  EG_CHECK(lds <= CONV1_LDS_MAX, "eg_spec_conv1_bwd: image %dx%d needs %lld bytes of LDS whole (limit %d): use "
+           "eg_spec_conv1_bwd_banded with eg_spec_conv1_band_rows", F, nfr, lds, CONV1_LDS_MAX);
   hipStream_t s = (hipStream_t)stream;
   eg_dispatch_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(spec_conv1_bwd_kernel<T>, dim3(nimg), dim3(256), lds, s, img, w, bias, (const T*)dp1, partial, F, nfr);
+    hipLaunchKernelGGL(spec_conv1_bwd_kernel<T>, dim3(nimg), dim3(256), (int)lds, s, img, w, bias, (const T*)dp1, partial, F, nfr);
   });
   EG_LAUNCH_CHECK("spec_conv1_bwd");
+  return 0;
+}
+
+// The ONE band rule, a function of the image shape alone (never of the device: the split of the gradient sum, and so its rounding,
+// must not depend on the machine).  0: the whole-image kernels serve the shape (their backward fits 64 KiB -- every shape the
+// spectrogram tokens produce).  Else the tallest band of 16 or 8 pooled rows (all eight lane groups busy; 16 rows = two rows per
+// group keep nimg * nbands workgroups above the CU count at the reference's batch) whose backward fits 64 KiB.  -1: none does.
+extern "C" int eg_spec_conv1_band_rows(int F, int nfr) {
+  if (F < 8 || nfr < 8) return -1;
+  if (conv1_lds_bwd(F + 2, nfr) <= CONV1_LDS_MAX) return 0;
+  for (int b = 16; b >= 8; b -= 8)
+    if (b <= F / 2 && conv1_lds_bwd(2 * b + 2, nfr) <= CONV1_LDS_MAX) return b;
+  return -1;
+}
+
+static int conv1_band_ok(const char* who, int nimg, int F, int nfr, int band_rows, long long lds) {
+  EG_CHECK(band_rows >= 1 && band_rows <= F / 2, "%s: band_rows %d outside [1, Hp = %d]", who, band_rows, F / 2);
+  EG_CHECK(lds <= CONV1_LDS_MAX, "%s: a band of %d pooled rows of a %dx%d image needs %lld bytes of LDS (limit %d)", who, band_rows,
+           F, nfr, lds, CONV1_LDS_MAX);
+  const int nbands = (F / 2 + band_rows - 1) / band_rows;
+  EG_CHECK((long long)nimg * nbands <= 0x7fffffffLL, "%s: %d images x %d bands exceed the grid", who, nimg, nbands);
+  return 0;
+}
+
+extern "C" int eg_spec_conv1_fwd_banded(const float* img, const float* w, const float* bias, void* p1, int nimg, int F, int nfr,
+                                        int band_rows, int dtype, void* stream) {
+  if (eg_dtype_check("eg_spec_conv1_fwd_banded", dtype, true)) return 1;
+  EG_CHECK(img && w && bias && p1, "eg_spec_conv1_fwd_banded: null pointer");
+  if (spec_shape_ok("eg_spec_conv1_fwd_banded", nimg, F, nfr)) return 1;
+  const long long lds = conv1_lds_bwd(2 * (long long)band_rows + 2, nfr) - 8 * C1 * 10 * 4;
+  if (conv1_band_ok("eg_spec_conv1_fwd_banded", nimg, F, nfr, band_rows, lds)) return 1;
+  const int nbands = (F / 2 + band_rows - 1) / band_rows;
+  hipStream_t s = (hipStream_t)stream;
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_conv1_fwd_banded_kernel<T>, dim3(nimg * nbands), dim3(256), (int)lds, s, img, w, bias, (T*)p1, F, nfr,
+                       band_rows, nbands);
+  });
+  EG_LAUNCH_CHECK("spec_conv1_fwd_banded");
+  return 0;
+}
+
+extern "C" int eg_spec_conv1_bwd_banded(const float* img, const float* w, const float* bias, const void* dp1, float* partial,
+                                        int nimg, int F, int nfr, int band_rows, int dtype, void* stream) {
+  if (eg_dtype_check("eg_spec_conv1_bwd_banded", dtype, true)) return 1;
+  EG_CHECK(img && w && bias && dp1 && partial, "eg_spec_conv1_bwd_banded: null pointer");
+  if (spec_shape_ok("eg_spec_conv1_bwd_banded", nimg, F, nfr)) return 1;
+  const long long lds = conv1_lds_bwd(2 * (long long)band_rows + 2, nfr);
+  if (conv1_band_ok("eg_spec_conv1_bwd_banded", nimg, F, nfr, band_rows, lds)) return 1;
+  const int nbands = (F / 2 + band_rows - 1) / band_rows;
+  hipStream_t s = (hipStream_t)stream;
+  eg_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(spec_conv1_bwd_banded_kernel<T>, dim3(nimg * nbands), dim3(256), (int)lds, s, img, w, bias, (const T*)dp1,
+                       partial, F, nfr, band_rows, nbands);
+  });
+  EG_LAUNCH_CHECK("spec_conv1_bwd_banded");
   return 0;
 }
 

@@ -209,7 +209,8 @@ def _conv2_flat(eng) -> bool:
 
 
 def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
-    """The reference's 2-D CNN over one-channel images (D:70-86, D:123-130): Conv2d(1->32,3x3)+ReLU+MaxPool2 (one kernel),
+    """The reference's 2-D CNN over one-channel images (D:70-86, D:123-130): Conv2d(1->32,3x3)+ReLU+MaxPool2 (one kernel: a workgroup
+    per image, or per band of sp["band_rows"] pooled rows where the image is too large for one workgroup's LDS),
     Conv2d(32->64,3x3)+ReLU as a segmented-row GEMM, AdaptiveAvgPool(4,4), Linear(1024->2d)+ReLU+Dropout, Linear(2d->d) whose
     epilogue writes rows addressed by c_map at out_ptr (+ residual rows r_map).  Images are eng.a["spimg"] [nimg, F, nfr] f32;
     parameters are `pre`spec_conv.{0,3}.* / `pre`proj.{0,3}.*.  Shared by the spectrogram tokens of DualEEGTransformer and by the
@@ -217,8 +218,12 @@ def spec_cnn_forward(eng, pre, p01, conv2, out_ptr, c_map, r_map, residual_ptr):
     from .engine import SITE_SPEC
     a, w, fp, dt, st, sp, d = eng.a, eng.w, eng.fp, eng.dtype, eng.stream, eng.sp, eng.cfg.d_model
     F, nfr, Hp, Wp, nimg = sp["F"], sp["nfr"], sp["Hp"], sp["Wp"], sp["nimg"]
-    call("eg_spec_conv1_fwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
-         ptr(a["sp_p1"]), nimg, F, nfr, dt, st)
+    if sp["band_rows"]:         # an image too large for one workgroup's LDS: (image, band) workgroups, the same p1 bit for bit
+        call("eg_spec_conv1_fwd_banded", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
+             ptr(a["sp_p1"]), nimg, F, nfr, sp["band_rows"], dt, st)
+    else:
+        call("eg_spec_conv1_fwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
+             ptr(a["sp_p1"]), nimg, F, nfr, dt, st)
     row = (Wp + 4) * 32
     if _conv2_flat(eng):
         # 16-bit operands: nine row offsets of one LDS image of p1 (csrc/spec.hip) instead of a segmented-row product that re-reads
@@ -251,7 +256,12 @@ def spec_cnn_alloc(eng, nimg, F, nfr):
     d, f32 = eng.cfg.d_model, torch.float32
     a = eng.a
     Hp, Wp = F // 2, nfr // 2
-    eng.sp = dict(F=F, nfr=nfr, Hp=Hp, Wp=Wp, nimg=nimg, rows=nimg * (Hp + 2) * Wp)
+    # conv-1's route, asked once: 0 = one workgroup per image, else pooled rows per (image, band) workgroup (eg_spec_conv1_band_rows)
+    band_rows = L.spec_conv1_band_rows(F, nfr)
+    if band_rows < 0:
+        raise L.EgError(f"image {F}x{nfr} unsupported: no conv-1 band fits the LDS (width above 748)")
+    eng.sp = dict(F=F, nfr=nfr, Hp=Hp, Wp=Wp, nimg=nimg, rows=nimg * (Hp + 2) * Wp, band_rows=band_rows,
+                  nbands=-(-Hp // band_rows) if band_rows else 1)
     a["spimg"] = eng._t(nimg, F, nfr, dtype=f32)
     a["sp_p1"] = eng._t(nimg * (Hp + 2) * (Wp + 4) * 32 + 4 * (Wp + 4) * 32)   # + slack rows read by the unused tail rows
     a["sp_out2"] = eng._t(nimg * (Hp + 2) * Wp, 64)
@@ -265,7 +275,7 @@ def spec_cnn_alloc_bwd(eng):
     g["sp_dp1"] = eng._t(sp["rows"], 32)
     g["sp_dpooled"] = eng._t(sp["nimg"], 1024)
     g["sp_dhp0"] = eng._t(sp["nimg"], 2 * d)
-    g["sp_part"] = eng._t(sp["nimg"], 320, dtype=torch.float32)
+    g["sp_part"] = eng._t(sp["nimg"] * sp["nbands"], 320, dtype=torch.float32)
 
 
 def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01, until=None):
@@ -304,10 +314,15 @@ def spec_cnn_backward(eng, pre, dy_ptr, dmap, sc01, until=None):
              2 * eng.cus, dt, st)
     else:
         eng.gemm(ptr(g["sp_d2"]), ptr(w["spc2T"]), ptr(g["sp_dp1"]), rows, 32, 768, a=rowmap(64, row64, Wp), seg=(256, row64))
-    call("eg_spec_conv1_bwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
-         ptr(g["sp_dp1"]), ptr(g["sp_part"]), nimg, F, nfr, dt, st)
-    call("eg_reduce_partials", ptr(g["sp_part"]), fp.g_ptr(pre + "spec_conv.0.weight"), 288, nimg, 320, 0, st)
-    call("eg_reduce_partials", ptr(g["sp_part"]) + 288 * 4, fp.g_ptr(pre + "spec_conv.0.bias"), 32, nimg, 320, 0, st)
+    if sp["band_rows"]:
+        call("eg_spec_conv1_bwd_banded", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
+             ptr(g["sp_dp1"]), ptr(g["sp_part"]), nimg, F, nfr, sp["band_rows"], dt, st)
+    else:
+        call("eg_spec_conv1_bwd", ptr(a["spimg"]), fp.p_ptr(pre + "spec_conv.0.weight"), fp.p_ptr(pre + "spec_conv.0.bias"),
+             ptr(g["sp_dp1"]), ptr(g["sp_part"]), nimg, F, nfr, dt, st)
+    nrow = nimg * sp["nbands"]
+    call("eg_reduce_partials", ptr(g["sp_part"]), fp.g_ptr(pre + "spec_conv.0.weight"), 288, nrow, 320, 0, st)
+    call("eg_reduce_partials", ptr(g["sp_part"]) + 288 * 4, fp.g_ptr(pre + "spec_conv.0.bias"), 32, nrow, 320, 0, st)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -982,6 +982,21 @@ int eg_spec_conv1_fwd(const float* img, const float* w, const float* bias, void*
                       void* stream);
 int eg_spec_conv1_bwd(const float* img, const float* w, const float* bias, const void* dp1, float* partial, int nimg,
                       int F, int nfr, int dtype, void* stream);
+/* eg_spec_conv1_fwd / _bwd stage one whole zero-padded image per workgroup: ((F+2)*(nfr+2) + 320) * 4 bytes of LDS forward, 10240
+ * more backward.  A shape that needs more than 64 KiB is refused on the host before any launch; the banded entry points serve it:
+ * a workgroup is (image, band of band_rows pooled rows) and stages the 2*band_rows + 2 input rows of its band
+ * (((2*band_rows+2)*(nfr+2) + 320) * 4 bytes forward, 10240 more backward, at most 64 KiB).  Same operator, layouts and per-output
+ * multiply-add chain: the interior of p1 is eg_spec_conv1_fwd's bit for bit (the pad frame is not written), and
+ *   eg_spec_conv1_bwd_banded writes partial [nimg * nbands, 320], nbands = ceil(Hp / band_rows), row im*nbands + band =
+ *   the band's (dW[32][9] | db[32]), every row whole by one workgroup (no atomics; sum with eg_reduce_partials over nimg*nbands).
+ * band_rows: any value in [1, Hp] whose LDS fits.  eg_spec_conv1_band_rows(F, nfr) is the production choice, a function of the
+ * shape alone: 0 = the whole-image backward fits 64 KiB, use eg_spec_conv1_fwd / _bwd (every shape up to e.g. 64 x 17, 72 x 120);
+ * else 16, or 8 where 16 rows do not fit (nfr > 395); -1 = no band fits (nfr > 748).  224 x 224: 16 (7 bands), 512 x 512: 8 (32). */
+int eg_spec_conv1_band_rows(int F, int nfr);      /* host only, no device needed */
+int eg_spec_conv1_fwd_banded(const float* img, const float* w, const float* bias, void* p1, int nimg, int F, int nfr,
+                             int band_rows, int dtype, void* stream);
+int eg_spec_conv1_bwd_banded(const float* img, const float* w, const float* bias, const void* dp1, float* partial, int nimg,
+                             int F, int nfr, int band_rows, int dtype, void* stream);
 int eg_spec_avgpool_fwd(const void* out2, void* pooled, int nimg, int Hp, int Wp, int dtype, void* stream);
 int eg_spec_avgpool_bwd(const void* out2, const void* dpooled, void* d2, int nimg, int Hp, int Wp, int dtype, void* stream);
 int eg_pack_conv2d_weight(const float* w, void* dst, int N, int Cin, int transposed, int dtype, void* stream);
